@@ -69,7 +69,37 @@ def parse(argv=None):
     ap.add_argument("--no-reference", action="store_true", help="skip the parity / torch_rocm_baseline / dropin legs")
     ap.add_argument("--no-other-configs", action="store_true", help="skip the other_configs leg (sd15, flux, ddpm, wan) of the default run")
     ap.add_argument("--save-tuning", default=None, help="write the GEMM variant table measured during warm-up here")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed region, write rank 0's output of the last timed step as DIR/<name>.npy (float32, at most 64 MB "
+                         "in all: a larger output is written as a fixed, seeded sample, DIR/<name>_sample.npy)")
     return ap.parse_args(argv)
+
+
+DUMP_BUDGET_ELEMS = 1 << 23                 # 32 MiB of float32: --dump-outputs stays well inside its 64 MB bound
+DUMP_SAMPLE_SEED = 0
+
+
+def dump_outputs(out_dir, arrays: dict) -> dict:
+    """--dump-outputs: every array as float32 `out_dir/<name>.npy`; an array larger than DUMP_BUDGET_ELEMS is written as the elements at
+    DUMP_BUDGET_ELEMS flat indices drawn from a generator seeded with DUMP_SAMPLE_SEED (sorted; the same indices for the same shape),
+    `out_dir/<name>_sample.npy`.  Returns {file name: shape written} for the result line."""
+    import numpy as np
+    out_dir = Path(out_dir)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    written = {}
+    for name, t in arrays.items():
+        flat = t.detach().reshape(-1)
+        if flat.numel() > DUMP_BUDGET_ELEMS:
+            g = torch.Generator("cpu").manual_seed(DUMP_SAMPLE_SEED)
+            idx = torch.randint(flat.numel(), (DUMP_BUDGET_ELEMS,), generator=g).sort().values
+            arr, fname = flat[idx.to(flat.device)], f"{name}_sample.npy"
+        else:
+            arr, fname = t.detach(), f"{name}.npy"
+        arr = arr.float().cpu().numpy()
+        np.save(out_dir / fname, arr)
+        written[fname] = list(arr.shape)
+    log(f"--dump-outputs: {', '.join(f'{k} {v}' for k, v in written.items())} -> {out_dir}")
+    return written
 
 
 # ---- device plumbing (one place, so the world-size-2 CPU test can run main() on the kernel stand-ins) ----------------
@@ -788,11 +818,11 @@ def _other_cpu_baseline(config, unit_tflop, n_steps):
             "sample": what + ", fp32, huggingface/diffusers 0.40.0.dev0 on torch CPU"}
 
 
-def measure_other_config(config, dev, rank, world, args, units, warmup, n_steps=None, extrapolate_from=None, legs=True):
+def measure_other_config(config, dev, rank, world, args, units, warmup, n_steps=None, extrapolate_from=None, legs=True, dump=None):
     """One BASELINE config other than the headline under the driver contract's timing rule: `warmup` untimed units, `units` timed
     units between synchronisations (+ barriers when world > 1), max over ranks.  ``extrapolate_from`` = k: a unit is timed with k
     sampler steps and scaled to the config's step count (flagged) -- the 50-step Wan video inside the default run.
-    ``legs``: per-family `roofline.kernels` and the `cpu_baseline` (rank 0, world == 1)."""
+    ``legs``: per-family `roofline.kernels` and the `cpu_baseline` (rank 0, world == 1).  ``dump``: --dump-outputs directory."""
     from diffusers_amd import distributed as D
     metric, unit_name, what, default_steps, tflop_of = OTHER_CONFIGS[config]
     n = n_steps or default_steps
@@ -815,6 +845,7 @@ def measure_other_config(config, dev, rank, world, args, units, warmup, n_steps=
         torch.distributed.barrier()
     _sync()
     elapsed = D.max_over_ranks(time.perf_counter() - t0, dev)
+    dumped = dump_outputs(dump, {"images": out}) if dump and rank == 0 else None
     scale = n / run_steps if extrapolate_from else 1.0
     side = {}
     if config == "wan":
@@ -847,6 +878,8 @@ def measure_other_config(config, dev, rank, world, args, units, warmup, n_steps=
                       "algorithmic_tflop_per_unit": tfl, **side},
            "roofline": {"bound": "mfma", "achieved": ach, "peak": MFMA_PEAK_TFLOPS, "unit": "TFLOP/s", "frac": ach / MFMA_PEAK_TFLOPS,
                         "traffic": None, "kernel": "whole unit (end to end): algorithmic TFLOP of SURVEY.md 8d / wall time"}}
+    if dumped:
+        res["dumped_outputs"] = dumped
     if extrapolate_from:
         res["config"]["extrapolated"] = (f"timed with {run_steps} sampler steps per unit and scaled to {n} (the steps are cost-identical; "
                                          f"`python bench.py --config {config}` runs the full unit)")
@@ -878,7 +911,8 @@ def run_other_config(args, argv):
     rank, world, local = D.init_from_env()
     dev = _device(local)
     log(f"rank {rank}/{world}: {args.config} on {dev}")
-    result = measure_other_config(args.config, dev, rank, world, args, args.steps, args.warmup, n_steps=args.denoise_steps)
+    result = measure_other_config(args.config, dev, rank, world, args, args.steps, args.warmup, n_steps=args.denoise_steps,
+                                  dump=args.dump_outputs)
     if rank == 0:
         print(json.dumps(result), flush=True)
     if _pg():
@@ -1099,6 +1133,8 @@ def main(argv=None):
         torch.distributed.barrier()
     _sync()
     elapsed = D.max_over_ranks(time.perf_counter() - t0, dev)
+    # the legs below reuse the pipeline's buffers: the timed path's last image is written out before any of them runs
+    dumped = dump_outputs(args.dump_outputs, {"images": img}) if args.dump_outputs and rank == 0 else None
     per_rank = [args.steps / mine_s]
     if _pg():
         tt = torch.tensor([args.steps / mine_s], dtype=torch.float64, device=dev)
@@ -1143,6 +1179,8 @@ def main(argv=None):
                    "cpu_binding": ("per-rank NUMA-local core share (distributed.bind_rank_to_cpus)" if world > 1 and
                                    os.environ.get("DIFFUSERS_AMD_BIND", "1") != "0" else "none")},
     }
+    if dumped:
+        result["dumped_outputs"] = dumped
 
     if rank == 0 and not args.tiny:
         if not args.no_roofline:

@@ -24,6 +24,15 @@ OUT = HERE / "_ref" / "diffusers_ref.zip"
 EXPECT_VERSION = "0.40.0.dev0"
 
 
+def reference_present(src: Path = SRC) -> bool:
+    """The reference package is on this machine AND readable by this user.  Path.exists() is not enough: for a path under a
+    directory this user may not enter (another user's home) it raises PermissionError instead of returning False."""
+    try:
+        return (src / "__init__.py").is_file()
+    except OSError:
+        return False
+
+
 def reference_version(src: Path = SRC) -> str:
     for line in (src / "__init__.py").read_text().splitlines():
         if line.startswith("__version__"):
@@ -33,7 +42,7 @@ def reference_version(src: Path = SRC) -> str:
 
 def build(force: bool = False) -> Path | None:
     """Returns the archive path, or None when the reference tree is not on this machine (the GPU box: use what shipped)."""
-    if not SRC.exists():
+    if not reference_present():
         return OUT if OUT.exists() else None
     ver = reference_version()
     if ver != EXPECT_VERSION:

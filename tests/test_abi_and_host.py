@@ -217,8 +217,9 @@ def test_attention_backend_registers_with_reference_registry():
     import importlib
     import inspect
     import sys
-    ref_src = Path("/root/reference/src")
-    if not ref_src.exists():
+    from oracle import build_ref
+    ref_src = build_ref.SRC.parent
+    if not build_ref.reference_present():
         pytest.skip("reference sources not present")
     sys.path.insert(0, str(ref_src))
     try:

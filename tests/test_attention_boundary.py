@@ -13,14 +13,14 @@ tests/ops_emulation.py -- checks the binding, the layouts and the strides) and o
 oracle/_ref/diffusers_ref.zip, the HIP kernels)."""
 import importlib
 import sys
-from pathlib import Path
 
 import pytest
 import torch
 
-from oracle import ref_runtime as RR
+from oracle import build_ref, ref_runtime as RR
 
-REF = Path("/root/reference/src")
+REF = build_ref.SRC.parent
+HAVE_REF = build_ref.reference_present()
 bf16 = torch.bfloat16
 
 
@@ -30,7 +30,7 @@ def _rel(a, b):
 
 
 def _load_ref():
-    if REF.exists():
+    if HAVE_REF:
         sys.path.insert(0, str(REF))
         try:
             import diffusers
@@ -137,7 +137,7 @@ TINY_FLUX = dict(patch_size=1, in_channels=64, out_channels=None, num_layers=2, 
                  axes_dims_rope=(8, 28, 28))
 
 
-@pytest.mark.skipif(not REF.exists(), reason="reference sources not present")
+@pytest.mark.skipif(not HAVE_REF, reason="reference sources not present")
 def test_backend_binds_through_the_public_api_cpu(monkeypatch):
     _run_flux_backend(monkeypatch, "cpu", TINY_FLUX, s_img=64, s_txt=16, gate=lambda f: max(1.5 * f, 2.5e-2))
 
@@ -186,7 +186,7 @@ def _run_wan_backend(monkeypatch, dev, gate):
     assert rg <= gate(rf), (rg, rf)
 
 
-@pytest.mark.skipif(not REF.exists(), reason="reference sources not present")
+@pytest.mark.skipif(not HAVE_REF, reason="reference sources not present")
 def test_backend_under_the_reference_wan_model_cpu(monkeypatch):
     _run_wan_backend(monkeypatch, "cpu", gate=lambda f: max(1.5 * f, 2.5e-2))
 
@@ -222,7 +222,7 @@ def _run_backend_gates(monkeypatch, dev):
             getattr(ad._AttentionBackendRegistry, k).update(v)
 
 
-@pytest.mark.skipif(not REF.exists(), reason="reference sources not present")
+@pytest.mark.skipif(not HAVE_REF, reason="reference sources not present")
 def test_backend_slots_and_refusals_cpu(monkeypatch):
     _run_backend_gates(monkeypatch, "cpu")
 
@@ -263,7 +263,7 @@ def _run_backend_layouts(monkeypatch, dev):
     assert cnt.n == 3
 
 
-@pytest.mark.skipif(not REF.exists(), reason="reference sources not present")
+@pytest.mark.skipif(not HAVE_REF, reason="reference sources not present")
 def test_backend_layouts_cpu(monkeypatch):
     _run_backend_layouts(monkeypatch, "cpu")
 
@@ -360,7 +360,7 @@ TINY_UNET = dict(sample_size=16, in_channels=4, out_channels=4, block_out_channe
                  projection_class_embeddings_input_dim=256)
 
 
-@pytest.mark.skipif(not REF.exists(), reason="reference sources not present")
+@pytest.mark.skipif(not HAVE_REF, reason="reference sources not present")
 def test_processor_on_the_reference_unet_cpu(monkeypatch):
     _run_processor(monkeypatch, "cpu", TINY_UNET, hw=16, gate=lambda f: max(1.5 * f, 2.5e-2))
 
@@ -388,7 +388,7 @@ SD15_HEADS_UNET = dict(sample_size=16, in_channels=4, out_channels=4, block_out_
                        up_block_types=("CrossAttnUpBlock2D", "CrossAttnUpBlock2D"))
 
 
-@pytest.mark.skipif(not REF.exists(), reason="reference sources not present")
+@pytest.mark.skipif(not HAVE_REF, reason="reference sources not present")
 def test_processor_pads_the_sd15_head_sizes_cpu(monkeypatch):
     """SD1.5's geometry: 8 heads of 40 / 80 channels (`attention_head_dim=8` is the head COUNT there) -- not flash-kernel sizes: the
     processor zero-pads the projections to 64 / 96 per head once per module, as the engine's own model classes do at load time."""
@@ -401,7 +401,7 @@ def test_processor_pads_the_sd15_head_sizes(monkeypatch):
 
 
 # ---- hardening of the two binding shims ------------------------------------------------------------
-@pytest.mark.skipif(not REF.exists(), reason="reference sources not present")
+@pytest.mark.skipif(not HAVE_REF, reason="reference sources not present")
 def test_run_time_enum_member_is_visible_through_every_public_view(monkeypatch):
     """`_extend_enum` writes CPython's private Enum tables; every PUBLIC view must then agree: lookup by value and by name, attribute
     access (the documented `AttentionBackendName.MI355X`; Python >= 3.12 resolves it through the class dict), iteration and
@@ -503,7 +503,7 @@ def _run_processor_cache_rules(monkeypatch, dev):
     assert got.shape == want.shape and _rel(got, want) < 2e-2
 
 
-@pytest.mark.skipif(not REF.exists(), reason="reference sources not present")
+@pytest.mark.skipif(not HAVE_REF, reason="reference sources not present")
 def test_processor_cache_rules_cpu(monkeypatch):
     _run_processor_cache_rules(monkeypatch, "cpu")
 

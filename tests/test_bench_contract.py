@@ -62,15 +62,15 @@ def test_product_package_never_imports_the_oracle_or_test_stand_ins():
 def test_recorded_bench_line_has_the_schema():
     txt = (ROOT / "profiles" / "README.md").read_text()
     assert "0.659 images/s" in txt
-    line = ROOT / "gpurun_out" / "bench.json"
-    if not line.exists():          # scratch directory: present in the build container only
-        return
-    rec = json.loads(line.read_text().strip().splitlines()[-1])
-    assert LINE_KEYS <= set(rec) and ROOFLINE_KEYS <= set(rec["roofline"])
-    if "cpu_baseline" in rec:       # absent when the scratch line came from a --no-cpu-baseline experiment run
-        assert CPU_KEYS <= set(rec["cpu_baseline"])
-    assert rec["higher_is_better"] is True and rec["scaling"] == "weak" and rec["n_gpus"] == 1
-    assert 0 < rec["roofline"]["frac"] < 1 and rec["roofline"]["bound"] in ("mfma", "hbm")
+    lines = sorted((ROOT / "profiles").glob("*bench_line*.json"))
+    assert lines, "no bench line recorded under profiles/"
+    for line in lines:
+        rec = json.loads(line.read_text().strip().splitlines()[-1])
+        assert LINE_KEYS <= set(rec) and ROOFLINE_KEYS <= set(rec["roofline"]), line.name
+        if "cpu_baseline" in rec:       # absent when the line came from a --no-cpu-baseline experiment run
+            assert CPU_KEYS <= set(rec["cpu_baseline"]), line.name
+        assert rec["higher_is_better"] is True and rec["scaling"] == "weak" and rec["n_gpus"] == 1, line.name
+        assert 0 < rec["roofline"]["frac"] < 1 and rec["roofline"]["bound"] in ("mfma", "hbm"), line.name
 
 
 def test_reference_archive_recipe(tmp_path):

@@ -3,7 +3,6 @@ LoRA adapters fused into the packed weights in place.  Packing is host arithmeti
 at the end runs the loaded / fused / unfused model's forward on hardware against the oracle on the same (merged) weights."""
 import json
 import sys
-from pathlib import Path
 
 import pytest
 import torch
@@ -11,9 +10,10 @@ import torch
 from diffusers_amd import init as dinit, loading, packed_cache
 from diffusers_amd.autoencoder_kl import AutoencoderKL
 from diffusers_amd.unet_2d_condition import UNet2DConditionModel
+from oracle import build_ref
 
 bf16 = torch.bfloat16
-REF_SRC = Path("/root/reference/src")
+REF_SRC = build_ref.SRC.parent
 
 
 def _tiny_unet_checkpoint(tmp_path, seed=0, variant=None, shards=1):
@@ -196,7 +196,7 @@ def test_in_memory_models_need_a_base_for_lora():
     assert m._lora == {"scale": 1.0, "modules": 1}
 
 
-@pytest.mark.skipif(not REF_SRC.exists(), reason="needs the reference checkout (build container only)")
+@pytest.mark.skipif(not build_ref.reference_present(), reason="needs the reference checkout (build container only)")
 def test_loads_what_the_reference_save_pretrained_writes(tmp_path):
     """The REAL reference classes write the directory (ModelMixin.save_pretrained, modeling_utils.py:629-884); the engine
     reads it back -- U-Net (config round trip incl. private keys) and the VAE (decoder half of a full AutoencoderKL)."""

@@ -8,13 +8,14 @@
    SDXL / SD / Flux / Wan pipelines, whose own ``__call__`` drives them (kernels = the torch stand-ins of
    tests/ops_emulation.py; the kernels themselves are tested on the GPU)."""
 import sys
-from pathlib import Path
 
 import pytest
 import torch
 
-REF = Path("/root/reference/src")
-pytestmark = pytest.mark.skipif(not REF.exists(), reason="reference sources not present")
+from oracle import build_ref
+
+REF = build_ref.SRC.parent
+pytestmark = pytest.mark.skipif(not build_ref.reference_present(), reason="reference sources not present")
 
 
 def _tokenizer(max_len=16):
