@@ -108,6 +108,7 @@ SIGNATURES = {
     "da_gemm_bf16": (_i, [C.POINTER(GemmParams), _vp]),
     "da_gemm_pair_bf16": (_i, [C.POINTER(GemmParams), C.POINTER(GemmParams), _vp]),
     "da_gemm_stats_parts": (_i, [C.POINTER(GemmParams)]),
+    "da_conv_chunk_channels": (_i, [C.POINTER(GemmParams), _i]),
     "da_gemm_tune": (_i, [C.POINTER(GemmParams), C.POINTER(GemmParams), _vp, _i, _vp, C.c_size_t, C.POINTER(C.c_int),
                           C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_float)]),
     "da_attention_bf16": (_i, [C.POINTER(AttentionParams), _vp]),

@@ -19,6 +19,7 @@
 // through a per-tile descriptor, or global_load_lds_dwordx4 with per-lane pointers; swizzle applied on the per-lane SOURCE
 // offset, LDS image lane-linear) -- see the staging-mode notes in gemm_kernel.cuh.
 #include "gemm_kernel.cuh"
+#include "gemm2_shared.cuh"
 
 namespace da_gemm {
 int dispatch_conv(const da_gemm_params& p, int tile, int staging, hipStream_t s);  // gemm_conv.hip
@@ -63,6 +64,18 @@ int pick_tile(const da_gemm_params& p) {
   return DA_TILE_64x64;
 }
 
+// the geometry of a conv launch (p.conv != 0; operand pointers are checked by the caller)
+int validate_conv(const da_gemm_params& p) {
+  if (p.C1 <= 0 || (p.C1 & 63) || (p.C2 & 63) || p.C2 < 0) return DA_ERR_UNSUPPORTED;
+  if (p.conv != 1 && p.conv != 3) return DA_ERR_UNSUPPORTED;
+  if (p.K != p.conv * p.conv * (p.C1 + p.C2)) return DA_ERR_INVALID;
+  if (p.stride != 1 && p.stride != 2) return DA_ERR_UNSUPPORTED;
+  if (p.up != 0 && p.up != 1) return DA_ERR_INVALID;
+  if (p.Hin <= 0 || p.Win <= 0 || p.Hout <= 0 || p.Wout <= 0) return DA_ERR_INVALID;
+  if (p.M % (p.Hout * p.Wout)) return DA_ERR_INVALID;
+  return DA_OK;
+}
+
 int validate(da_gemm_params& p) {
   if (p.M <= 0 || p.N <= 0 || p.K <= 0) return DA_ERR_INVALID;
   if ((p.K & 63) || (p.N & 3) || (p.ldc & 3)) return DA_ERR_UNSUPPORTED;
@@ -73,14 +86,9 @@ int validate(da_gemm_params& p) {
   if (p.alpha == 0.0f) p.alpha = 1.0f;
   if (p.out_scale == 0.0f) p.out_scale = 1.0f;
   if (p.conv) {
-    if (p.C1 <= 0 || (p.C1 & 63) || (p.C2 & 63) || p.C2 < 0) return DA_ERR_UNSUPPORTED;
+    const int v = validate_conv(p);
+    if (v != DA_OK) return v;
     if (p.C2 > 0 && !p.A2) return DA_ERR_INVALID;
-    if (p.conv != 1 && p.conv != 3) return DA_ERR_UNSUPPORTED;
-    if (p.K != p.conv * p.conv * (p.C1 + p.C2)) return DA_ERR_INVALID;
-    if (p.stride != 1 && p.stride != 2) return DA_ERR_UNSUPPORTED;
-    if (p.up != 0 && p.up != 1) return DA_ERR_INVALID;
-    if (p.Hin <= 0 || p.Win <= 0 || p.Hout <= 0 || p.Wout <= 0) return DA_ERR_INVALID;
-    if (p.M % (p.Hout * p.Wout)) return DA_ERR_INVALID;
   } else {
     if ((p.lda & 7) || (p.ldw & 7)) return DA_ERR_UNSUPPORTED;
   }
@@ -183,6 +191,15 @@ extern "C" int da_gemm_stats_parts(const da_gemm_params* pp) {
   if (tile == DA_TILE_AUTO) tile = pick_tile(*pp);
   if (tile <= 0 || tile >= kNumTiles) return 0;
   return stats_parts(*pp, tile);
+}
+
+extern "C" int da_conv_chunk_channels(const da_gemm_params* pp, int tile) {
+  if (!pp || !pp->conv || pp->M <= 0 || pp->N <= 0) return -DA_ERR_INVALID;
+  const da_gemm_params& p = *pp;   // (host only: the operand pointers are not read and may be NULL)
+  const int v = validate_conv(p);
+  if (v != DA_OK) return -v;
+  if (!is_k2(tile) || !tile_ok(p, tile)) return -DA_ERR_UNSUPPORTED;
+  return da_gemm2::conv_chunk_channels(p, kTiles[tile].bm, kTiles[tile].bn);
 }
 
 extern "C" int da_gemm_pair_bf16(const da_gemm_params* pa, const da_gemm_params* pb, void* stream) {

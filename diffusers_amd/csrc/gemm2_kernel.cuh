@@ -1234,11 +1234,7 @@ template <int KG, int WM, int WN, int MT, int NT, int NSLOT, bool CONV, bool PP 
           bool LNF = false, int XA = 0>
 int launch(const da_gemm_params& p, hipStream_t s) {
   constexpr int BM = 16 * MT * WM, BN = 16 * NT * WN;
-  const int tiles_m = (p.M + BM - 1) / BM, tiles_n = (p.N + BN - 1) / BN;
-  const int gx = choose_xcd_gx2(tiles_m, tiles_n, BM, BN, CONV ? xcd_conv_weighting(p) : 1, CONV ? (long long)(p.C1 + p.C2) * 2 : 0), gy = 8 / gx;
-  const int tm_per = (tiles_m + gy - 1) / gy, tn_per = (tiles_n + gx - 1) / gx;
-  const int grid = 8 * tm_per * tn_per;
-  const long long rows_xcd = (long long)BM * (tm_per < (32 + tn_per - 1) / tn_per ? tm_per : (32 + tn_per - 1) / tn_per);
+  const LaunchGeom geom = launch_geom(p, BM, BN, CONV);
   constexpr size_t lds = (size_t)NSLOT * KG * (BM + BN) * 128 + 1024 + (LNF ? 2 * BN * 4 : 0);   // ring + the scratch KiB (ragged pieces, prefetch) + s / c
   auto kern = igemm2_bf16_kernel<KG, WM, WN, MT, NT, NSLOT, CONV, PP, STREAMW, GIL, LNF, XA>;
   static bool attr_set = false;  // per instantiation
@@ -1247,7 +1243,7 @@ int launch(const da_gemm_params& p, hipStream_t s) {
       return DA_ERR_LAUNCH;
     attr_set = true;
   }
-  DA_LAUNCH(kern, dim3(grid), dim3(512), lds, s, p, gx | (CONV ? conv_chunk_slices(p, rows_xcd) << 8 : 0));
+  DA_LAUNCH(kern, dim3(geom.grid), dim3(512), lds, s, p, geom.gx | (CONV ? conv_chunk_slices(p, geom.rows_xcd) << 8 : 0));
   DA_CHECK_LAUNCH();
   return DA_OK;
 }

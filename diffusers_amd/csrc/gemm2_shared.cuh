@@ -119,8 +119,11 @@ inline int choose_xcd_gx2(int tiles_m, int tiles_n, int BM, int BN, int wrow = 1
 // M 32768 x N 320 x K 5760 fetches 74 MB instead of 403 and runs 114 instead of 120 us, K 8640: 111 instead of 605 MB, 166 instead of
 // 173 us; M 8192 x N 640 x K 17280 235 instead of 454 MB at the same time; every other launch of the step is untouched; the image is
 // the same speed within the pair-to-pair spread (same box: 0.9870 / 0.9863 tap-major, 0.9865 / 0.9897 auto).
+// DA_CONV_CHUNK is read on every call (as DA_CONV_IN_QUAD, misc.hip): tests compare the orders in one process.  A captured graph keeps
+// the chunk in effect when it was captured -- the value travels in the kernel argument.
 inline int conv_chunk_slices(const da_gemm_params& p, long long rows_xcd = 0) {
-  static const int forced = [] { const char* v = getenv("DA_CONV_CHUNK"); return v ? (v[0] == 'a' ? -1 : atoi(v)) : -1; }();
+  const char* v = getenv("DA_CONV_CHUNK");
+  const int forced = v ? (v[0] == 'a' ? -1 : atoi(v)) : -1;
   if (p.conv <= 1) return 0;
   if (forced < 0) {
     const long long ctot = p.C1 + p.C2;
@@ -136,6 +139,27 @@ inline int conv_chunk_slices(const da_gemm_params& p, long long rows_xcd = 0) {
 inline int xcd_conv_weighting(const da_gemm_params& p) {
   static const int on = [] { const char* v = getenv("DA_XCD_CONV"); return v ? atoi(v) : 1; }();
   return (on && p.conv > 1) ? p.conv * p.conv : 1;
+}
+
+// Launch geometry of a BM x BN tile of this family: XCD columns `gx`, the grid, and `rows_xcd` (activation rows of the tiles
+// co-resident on one XCD, conv_chunk_slices' input).  launch() and da_conv_chunk_channels() both take it from here.
+struct LaunchGeom {
+  int gx, grid;
+  long long rows_xcd;
+};
+inline LaunchGeom launch_geom(const da_gemm_params& p, int BM, int BN, bool conv) {
+  const int tiles_m = (p.M + BM - 1) / BM, tiles_n = (p.N + BN - 1) / BN;
+  const int gx = choose_xcd_gx2(tiles_m, tiles_n, BM, BN, conv ? xcd_conv_weighting(p) : 1, conv ? (long long)(p.C1 + p.C2) * 2 : 0), gy = 8 / gx;
+  const int tm_per = (tiles_m + gy - 1) / gy, tn_per = (tiles_n + gx - 1) / gx;
+  const long long rows_xcd = (long long)BM * (tm_per < (32 + tn_per - 1) / tn_per ? tm_per : (32 + tn_per - 1) / tn_per);
+  return {gx, 8 * tm_per * tn_per, rows_xcd};
+}
+
+// Channels per chunk of the K order a conv launch of a BM x BN tile walks (0: tap-major), as the kernel derives it from
+// conv_chunk_slices (a chunk of >= C1 + C2 channels is the tap-major order).
+inline int conv_chunk_channels(const da_gemm_params& p, int BM, int BN) {
+  const int ch = 64 * conv_chunk_slices(p, launch_geom(p, BM, BN, true).rows_xcd);
+  return (p.conv > 1 && ch < p.C1 + p.C2) ? ch : 0;
 }
 
 // 31-bit offset budget of the buffer-addressed staging (as da_gemm::buffer_staging_fits, for tiles up to 256 rows)

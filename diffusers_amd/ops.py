@@ -563,10 +563,46 @@ def conv2d_nhwc(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] =
     ``k_valid`` > 0 (single source only): channels >= k_valid of x AND of every tap of w are zero padding up to the 64-wide
     K granule; the kernel skips the MFMA steps that would multiply them (da_gemm_params.k_valid)."""
     _req(x, "x"), _req(w, "w")
+    if x2 is not None:
+        _req(x2, "x2")
+    p = _conv_params(x, w, ksize, x2, stride, up, pad, pad_after)
+    B, Hout, Wout, Cout = x.shape[0], p.Hout, p.Wout, p.N
+    if out is None:
+        out = torch.empty((B, Hout, Wout, Cout), device=x.device, dtype=bf16)
+    else:
+        _req(out, "out")
+        if tuple(out.shape) != (B, Hout, Wout, Cout) or not out.is_contiguous():
+            raise ValueError("conv2d_nhwc: out must be contiguous [B][Hout][Wout][Cout]")
+    inplace = residual is not None and residual.data_ptr() == out.data_ptr()
+    p.A, p.A2, p.W, p.C = x.data_ptr(), _ptr(x2), w.data_ptr(), out.data_ptr()
+    p.bias, p.rowvec, p.residual = _ptr(bias), _ptr(rowvec), _ptr(residual)
+    if residual is not None:
+        _req(residual, "residual")
+        if tuple(residual.shape) != (B, Hout, Wout, Cout) or not residual.is_contiguous():
+            raise ValueError("conv2d_nhwc: residual must be contiguous [B][Hout][Wout][Cout]")
+        p.ldr = Cout
+    if rowvec is not None:
+        _req(rowvec, "rowvec")
+        p.ld_rowvec = _rows2d(rowvec, "rowvec")
+        p.rows_per_batch = Hout * Wout
+    p.alpha, p.out_scale, p.act, p.out_f32 = 1.0, out_scale, act, 0
+    C1, C2 = p.C1, p.C2
+    if not 0 <= k_valid <= C1 or (k_valid and C2):
+        raise ValueError(f"conv2d_nhwc: k_valid {k_valid} outside [0, C1 = {C1}] (or given with a second source)")
+    p.k_valid = 0 if k_valid == C1 else k_valid
+    _prefetch_hook(p, x, w)
+    st = _stream()
+    _select_variant(p, tile, staging, st, inplace=inplace, split_k=split_k, device=x.device)
+    _launch_gemm(p, st, "da_gemm_bf16(conv)")
+    return out
+
+
+def _conv_params(x: torch.Tensor, w: torch.Tensor, ksize: int, x2: Optional[torch.Tensor], stride: int, up: bool,
+                 pad: Optional[int], pad_after: int) -> "L.GemmParams":
+    """The geometry of a conv2d_nhwc launch (shapes only: no operand pointer is set)."""
     B, H, W_, C1 = x.shape
     C2 = 0
     if x2 is not None:
-        _req(x2, "x2")
         if x2.shape[:3] != x.shape[:3]:
             raise ValueError("conv2d_nhwc: x2 spatial shape mismatch")
         C2 = x2.shape[3]
@@ -582,38 +618,25 @@ def conv2d_nhwc(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] =
     # downsampling.py:139-141); out-of-range taps read zeros, so only the output extent changes
     Hout = (Hv + 2 * pad + pad_after - ksize) // stride + 1
     Wout = (Wv + 2 * pad + pad_after - ksize) // stride + 1
-    if out is None:
-        out = torch.empty((B, Hout, Wout, Cout), device=x.device, dtype=bf16)
-    else:
-        _req(out, "out")
-        if tuple(out.shape) != (B, Hout, Wout, Cout) or not out.is_contiguous():
-            raise ValueError("conv2d_nhwc: out must be contiguous [B][Hout][Wout][Cout]")
-    inplace = residual is not None and residual.data_ptr() == out.data_ptr()
     p = L.GemmParams()
-    p.A, p.A2, p.W, p.C = x.data_ptr(), _ptr(x2), w.data_ptr(), out.data_ptr()
-    p.bias, p.rowvec, p.residual = _ptr(bias), _ptr(rowvec), _ptr(residual)
     p.M, p.N, p.K = B * Hout * Wout, Cout, K
     p.lda, p.ldw, p.ldc = 0, K, Cout
-    if residual is not None:
-        _req(residual, "residual")
-        if tuple(residual.shape) != (B, Hout, Wout, Cout) or not residual.is_contiguous():
-            raise ValueError("conv2d_nhwc: residual must be contiguous [B][Hout][Wout][Cout]")
-        p.ldr = Cout
-    if rowvec is not None:
-        _req(rowvec, "rowvec")
-        p.ld_rowvec = _rows2d(rowvec, "rowvec")
-        p.rows_per_batch = Hout * Wout
-    p.alpha, p.out_scale, p.act, p.out_f32, p.conv = 1.0, out_scale, act, 0, ksize
+    p.conv = ksize
     p.Hin, p.Win, p.C1, p.C2, p.Hout, p.Wout = H, W_, C1, C2, Hout, Wout
     p.stride, p.up, p.pad = stride, int(up), pad
-    if not 0 <= k_valid <= C1 or (k_valid and C2):
-        raise ValueError(f"conv2d_nhwc: k_valid {k_valid} outside [0, C1 = {C1}] (or given with a second source)")
-    p.k_valid = 0 if k_valid == C1 else k_valid
-    _prefetch_hook(p, x, w)
-    st = _stream()
-    _select_variant(p, tile, staging, st, inplace=inplace, split_k=split_k, device=x.device)
-    _launch_gemm(p, st, "da_gemm_bf16(conv)")
-    return out
+    return p
+
+
+def conv_chunk_channels(x: torch.Tensor, w: torch.Tensor, tile: int, *, ksize: int = 3, x2: Optional[torch.Tensor] = None,
+                        stride: int = 1, up: bool = False, pad: Optional[int] = None, pad_after: int = 0) -> int:
+    """Channels per chunk of the K order that conv2d_nhwc(x, w, ksize=..., x2=..., tile=tile) walks on a K2 / K1 tile, 0 for
+    the tap-major order (da_conv_chunk_channels), under DA_CONV_CHUNK as it is set now.  Host only: the tensors give shapes and
+    may live on any device (``meta`` included)."""
+    p = _conv_params(x, w, ksize, x2, stride, up, pad, pad_after)
+    r = int(L.load().da_conv_chunk_channels(C.byref(p), int(tile)))
+    if r < 0:
+        L.check(-r, f"da_conv_chunk_channels(tile {L.TILE_NAMES[tile] if 0 <= tile < len(L.TILE_NAMES) else tile})")
+    return r
 
 
 def linear_small_m(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None, *, act_in: int = L.ACT_NONE,

@@ -234,6 +234,15 @@ typedef struct da_gemm_params {
 /* number of stats partials per row the launch *p (tile resolved as da_gemm_bf16 resolves it) writes to stats_out */
 int da_gemm_stats_parts(const da_gemm_params* p);
 
+/* Host-only query (no launch; operand pointers are not read): the channels per chunk of the K order that the K2 / K1 k x k conv launch
+ * of *p on `tile` (a DA_TILE_K2_* / DA_TILE_K1_* code) walks -- for each chunk of that many channels all k * k taps, then the next
+ * chunk -- or 0 for the tap-major order (all channels of tap 0, then tap 1, ...; always for 1 x 1 convs).  The two orders sum K
+ * differently, so outputs may differ in the last bit.  Decided per launch from the shape and tile (a tap sweep that outgrows the L2 is
+ * chunked) and from the environment variable DA_CONV_CHUNK as it is set at the time of the call: unset or "a..." = that rule, "0" =
+ * tap-major, "<n>" = chunks of n / 64 64-channel slices.  Returns -DA_ERR_INVALID / -DA_ERR_UNSUPPORTED for params that are not a
+ * valid conv or a tile outside that family. */
+int da_conv_chunk_channels(const da_gemm_params* p, int tile);
+
 #define DA_LN_MAX_PARTS 64   /* slots per row of a statistics buffer */
 #define DA_LN_PAIR_LOADS 6   /* 16-byte loads per lane half in the consumer: rows with up to 24 partials (N <= 24 column tiles) */
 #define DA_SPLITK_FLAGS 4096

@@ -512,3 +512,62 @@ def test_torch_library_ops_are_registered_with_fake_kernels():
     # schema: functional ops (nothing mutated), so functionalisation / export need no special handling
     for n in T.OPS:
         assert not getattr(ns, n).default._schema.is_mutable
+
+
+def test_conv_chunk_query_is_host_only_and_reads_the_knob_per_call(monkeypatch):
+    """da_conv_chunk_channels (ops.conv_chunk_channels): the K order a K2 / K1 conv launch walks, from the same launch geometry as the
+    launch (gemm2_shared.cuh launch_geom / conv_chunk_slices) -- no GPU needed.  Auto: tap-major (0) unless a tap sweep outgrows the
+    L2; the shipped table's deep-K entries are chunked on their own tiles with the chunks below; DA_CONV_CHUNK is read on every call."""
+    import json
+    from diffusers_amd import _lib as L
+    from diffusers_amd import ops
+    from diffusers_amd.build import build_extension
+    build_extension()
+    monkeypatch.delenv("DA_CONV_CHUNK", raising=False)
+    conv_tiles = [t for t in range(L.FIRST_K2_TILE, L.TILE_K3_256x256)
+                  if t not in (L.TILE_K2_80x128, L.TILE_K1_256x256, L.TILE_K1_256x320)]
+
+    def meta(*s):
+        return torch.empty(s, device="meta", dtype=torch.bfloat16)
+
+    def q(B, H, W, C1, C2, Co, tile, ks=3, **kw):
+        x2 = meta(B, H, W, C2) if C2 else None
+        return ops.conv_chunk_channels(meta(B, H, W, C1), meta(Co, ks * ks * (C1 + C2)), tile, ksize=ks, x2=x2, **kw)
+
+    # tap-major: 1 x 1 convs and the shallow shapes of test_k2_conv_variants, on every tile
+    for s in ((2, 32, 32, 1280, 0, 1280), (2, 16, 16, 640, 320, 640), (2, 24, 24, 320, 0, 320), (1, 20, 20, 64, 0, 96),
+              (1, 16, 16, 320, 0, 320, 3, dict(stride=2)), (1, 12, 12, 256, 0, 128, 3, dict(up=True)),
+              (1, 9, 7, 128, 192, 80), (2, 16, 16, 640, 0, 1280, 1), (1, 16, 16, 64, 64, 128, 1), (2, 128, 128, 960, 0, 320, 1)):
+        shape, ks, kw = s[:6], (s[6] if len(s) > 6 else 3), (s[7] if len(s) > 7 else {})
+        for t in conv_tiles:
+            assert q(*shape, t, ks=ks, **kw) == 0, (s, L.TILE_NAMES[t])
+    # the shipped table's chunked entries, on the table's own tile
+    entries = json.loads((ROOT / "diffusers_amd" / "tuned" / "gfx950.json").read_text())["entries"]
+    for key, shape, want in (("conv3:M32768:N320:C640+0:H128x128:s1:u0:a0:r0", (2, 128, 128, 640, 0, 320), 256),
+                             ("conv3:M32768:N320:C960+0:H128x128:s1:u0:a0:r0", (2, 128, 128, 960, 0, 320), 256),
+                             ("conv3:M8192:N640:C1920+0:H64x64:s1:u0:a0:r0", (2, 64, 64, 1920, 0, 640), 1024),
+                             ("conv3:M65536:N256:C512+0:H256x256:s1:u0:a0:r0", (1, 256, 256, 512, 0, 256), 256),
+                             ("conv3:M262144:N256:C512+0:H512x512:s1:u0:a0:r0", (1, 512, 512, 512, 0, 256), 256)):
+        tile = entries[key][0]
+        got = q(*shape, tile)
+        assert got == want and got % 64 == 0 and 256 <= got < shape[3] + shape[4], (key, L.TILE_NAMES[tile], got)
+    # the chunk is a function of the tile: one deep-K shape, three chunks (test_gemm_k2_gpu.py invariant (2) holds per chunk size)
+    deep = (2, 128, 128, 320, 320, 320)
+    assert [q(*deep, t) for t in (L.TILE_K1_128x320, L.TILE_K1_256x128, L.TILE_K1_128x256)] == [256, 320, 0]
+    # DA_CONV_CHUNK between two calls of one process
+    for v, want in (("0", 0), ("128", 128), ("192", 192), ("100", 64), ("1024", 0), ("auto", 256), (None, 256)):
+        if v is None:
+            monkeypatch.delenv("DA_CONV_CHUNK")
+        else:
+            monkeypatch.setenv("DA_CONV_CHUNK", v)
+        assert q(2, 128, 128, 640, 0, 320, L.TILE_K1_256x160) == want, v
+        assert q(2, 128, 128, 640, 0, 320, L.TILE_K1_256x160, ks=1) == 0, v
+    # refused: tiles outside the family or without a conv build, params that are not a conv
+    for t in (L.TILE_128x128, L.TILE_K2_80x128, L.TILE_K3_256x256, 0, 99):
+        with pytest.raises(RuntimeError, match="DA_ERR_UNSUPPORTED"):
+            q(2, 64, 64, 640, 0, 320, t)
+    lib = L.load()
+    p = L.GemmParams()
+    assert lib.da_conv_chunk_channels(C.byref(p), L.TILE_K2_128x128) == -1   # conv = 0: -DA_ERR_INVALID
+    p.M, p.N, p.K, p.conv, p.C1, p.Hin, p.Win, p.Hout, p.Wout, p.stride = 64, 64, 9 * 96, 3, 96, 8, 8, 8, 8, 1
+    assert lib.da_conv_chunk_channels(C.byref(p), L.TILE_K2_128x128) == -3   # C1 not a multiple of 64

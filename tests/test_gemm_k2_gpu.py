@@ -3,8 +3,10 @@ alternate K slices, 16x16x32 MFMA, slice pairs with a mid-pair rendezvous, parti
 
 What must hold: (1) right against a plain PyTorch fp32 reference of the same op, with the tolerance of the first family's
 tests; (2) every K2 (tile, ring depth) variant BIT-identical to every other one (same per-element summation: (even K
-slices) + (odd K slices)); (3) within one bf16 ulp of the first family's result (fp32 summation order is the only
-difference); (4) every fused epilogue of da_gemm_params; (5) the implicit-GEMM gather in every conv form the U-Net / VAE use
+slices) + (odd K slices)) for ONE order of the K slices -- a k x k conv's chunk size (gemm2_shared.cuh conv_chunk_slices)
+depends on the tile; auto mode chunks deep-K shapes only, none of the shapes below (test_conv_chunk_gpu.py pins each chunk size);
+(3) within one bf16 ulp of the first family's result (fp32 summation order is the only difference); (4) every fused
+epilogue of da_gemm_params; (5) the implicit-GEMM gather in every conv form the U-Net / VAE use
 (3x3, 1x1, stride 2, fused nearest-2x, two-source channel concat), including odd K slice counts and ragged M / N edges."""
 import pytest
 import torch
@@ -42,8 +44,9 @@ def k2_variants(L, conv=False, geglu=False):
 
 def run_all(fn, L, what, conv=False, geglu=False, min_ok=5):
     """fn(tile, staging) for every variant of gemm2_kernel.cuh; unsupported (tile, ring depth) pairs must say so.  Variants of
-    one summation order are BIT-identical: the KG = 2 tiles (k2:*, (even K slices) + (odd K slices)) among themselves, the
-    KG = 1 tiles (k1:*, all slices in order) among themselves; the two orders agree within one bf16 ulp.  Returns the k2 result."""
+    one summation order (for a k x k conv: one chunk size of its K order) are BIT-identical: the KG = 2 tiles (k2:*, (even K
+    slices) + (odd K slices)) among themselves, the KG = 1 tiles (k1:*, all slices in order) among themselves; the two orders
+    agree within one bf16 ulp.  Returns the k2 result."""
     base, n_ok = {}, 0
     for t, st in k2_variants(L, conv, geglu):
         try:
