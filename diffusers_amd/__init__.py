@@ -28,6 +28,8 @@ _EXPORTS = {
     "UniPCMultistepScheduler": "schedulers",
     "StableDiffusionPipeline": "pipelines",
     "StableDiffusionXLPipeline": "pipelines",
+    "StableDiffusionImg2ImgPipeline": "pipelines",
+    "StableDiffusionXLImg2ImgPipeline": "pipelines",
     "from_reference_config": "config_utils",
     "CLIPTextModel": "text_encoders",
     "CLIPTextModelWithProjection": "text_encoders",

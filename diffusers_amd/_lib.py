@@ -144,6 +144,8 @@ SIGNATURES = {
     "da_linear_small_m_bf16": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "da_conv_thin_in_bf16": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _f, _f, _vp]),
     "da_conv_thin_out_bf16": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
+    "da_vae_conv_in_image": (_i, [_vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    "da_vae_posterior_latents": (_i, [_vp, _ll, _ll, _ll, _vp, _vp, _vp, _vp, _vp, _i, _ll, _i, _i, _i, _f, _f, _f, _f, _vp]),
     "da_plan_create": (_i, [C.POINTER(PlanOp), _i, C.POINTER(C.c_void_p)]),
     "da_plan_launch": (_i, [_vp, _vp, C.POINTER(C.c_int)]),
     "da_plan_relocate": (_i, [_vp, _i, C.POINTER(C.c_void_p), C.POINTER(C.c_ulonglong), C.POINTER(C.c_void_p),
@@ -153,6 +155,11 @@ SIGNATURES = {
     "da_plan_arg_count": (_i, [_i]),
     "da_plan_arg_kinds": (C.c_char_p, [_i]),
 }
+
+# include/diffusers_amd.h: image sources of da_vae_conv_in_image, modes / flags of da_vae_posterior_latents
+IMAGE_F32_NCHW, IMAGE_F32_NHWC, IMAGE_U8_NHWC = 0, 1, 2
+POSTERIOR_MOMENTS, POSTERIOR_MEAN, POSTERIOR_SAMPLE, POSTERIOR_NOISE = 0, 1, 2, 3
+LATENTS_SHIFT, LATENTS_SCALE = 1, 2
 
 ABI_VERSION = 6              # include/diffusers_amd.h DA_ABI_VERSION
 _lib = None

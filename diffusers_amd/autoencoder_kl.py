@@ -1,8 +1,11 @@
-"""AutoencoderKL.decode on the gfx950 kernels.
+"""AutoencoderKL.decode and AutoencoderKL.encode on the gfx950 kernels.
 
 Mirrors models/autoencoders/autoencoder_kl.py:199-240 (decode/_decode) and models/autoencoders/vae.py:279-311
-(Decoder.forward) with UNetMidBlock2D (unet_2d_blocks.py:736-748) and UpDecoderBlock2D (:2637-2645).  Only the decode
-path is on the BASELINE hot path; ``encode`` raises.  Input latents NCHW bf16, output image NCHW bf16, as the reference.
+(Decoder.forward) with UNetMidBlock2D (unet_2d_blocks.py:736-748) and UpDecoderBlock2D (:2637-2645).  Input latents NCHW
+bf16, output image NCHW bf16, as the reference.  The encoder half (autoencoder_kl.py:146-185, Encoder.forward vae.py:140-184
+with DownEncoderBlock2D, unet_2d_blocks.py:1421-1502) is packed when the state_dict holds it: its two ends are fused kernels
+(the caller's image -> conv_in: ops.vae_conv_in_image; conv_out's result -> quant_conv -> posterior -> latents:
+ops.vae_posterior_latents), the trunk reuses the decoder's layers.
 """
 from __future__ import annotations
 
@@ -14,7 +17,8 @@ import torch
 from . import ops
 from .config_utils import check_to
 from .loading import PretrainedMixin
-from .layers import GroupNorm, ResnetBlock2D, Upsample2D, Weights
+from . import _lib as L
+from .layers import Downsample2D, GroupNorm, ResnetBlock2D, Upsample2D, Weights
 from .unet_2d_condition import FrozenConfig
 
 bf16 = torch.bfloat16
@@ -98,6 +102,127 @@ class VaeAttention:
         return y.view(B, H, W_, C)
 
 
+@dataclass
+class AutoencoderKLOutput:
+    latent_dist: "DiagonalGaussianDistribution"
+
+
+class _Encoder:
+    """Encoder.forward (vae.py:140-184) on NHWC bf16: conv_in, DownEncoderBlock2D x n (resnets, Downsample2D(padding=0) but on the
+    last block), mid block (resnet, attention, resnet), conv_norm_out + SiLU, conv_out -> 2 L channels; + quant_conv's weights."""
+
+    def __init__(self, w: Weights, c, groups: int, eps: float):
+        boc = tuple(c.block_out_channels)
+        self.latent_channels = c.latent_channels
+        self.conv_in_w = ops.pack_conv_weight(w.get("encoder.conv_in.weight"))
+        self.conv_in_b = w.get("encoder.conv_in.bias")
+        self.down = []
+        for i in range(len(boc)):
+            pre = f"encoder.down_blocks.{i}"
+            self.down.append({"resnets": [ResnetBlock2D(w, f"{pre}.resnets.{j}", groups, eps) for j in range(c.layers_per_block)],
+                              "down": Downsample2D(w, f"{pre}.downsamplers.0", padding=0) if i != len(boc) - 1 else None})
+        self.mid_res0 = ResnetBlock2D(w, "encoder.mid_block.resnets.0", groups, eps)
+        self.mid_attn = VaeAttention(w, "encoder.mid_block.attentions.0", groups, eps) if c.mid_block_add_attention else None
+        self.mid_res1 = ResnetBlock2D(w, "encoder.mid_block.resnets.1", groups, eps)
+        self.conv_norm_out = GroupNorm(w, "encoder.conv_norm_out", groups, eps)
+        self.conv_out_w = ops.pack_conv_weight(w.get("encoder.conv_out.weight"))
+        self.conv_out_b = w.get("encoder.conv_out.bias")
+        self.quant_w = self.quant_b = None
+        if c.use_quant_conv:
+            qw = w.get("quant_conv.weight")
+            self.quant_w = qw.reshape(qw.shape[0], qw.shape[1]).contiguous()
+            self.quant_b = w.get("quant_conv.bias")
+
+    def __call__(self, img: torch.Tensor, *, nchw: bool, normalize: bool):
+        """Image (fp32 NCHW / NHWC or uint8 NHWC) -> the conv_out result and its strides (ops.conv_thin_out_moments)."""
+        x = ops.vae_conv_in_image(img, self.conv_in_w, self.conv_in_b, nchw=nchw, normalize=normalize)
+        for st in self.down:
+            for rn in st["resnets"]:
+                x = rn(x)
+            if st["down"] is not None:
+                x = st["down"](x)
+        x = self.mid_res0(x)
+        if self.mid_attn is not None:
+            x = self.mid_attn(x)
+        x = self.mid_res1(x)
+        x = self.conv_norm_out(x, silu=True)
+        return ops.conv_thin_out_moments(x, self.conv_out_w, self.conv_out_b)
+
+
+class DiagonalGaussianDistribution:
+    """vae.py:685-718 over the encoder's conv_out result.  ``sample`` / ``mode`` run quant_conv, the posterior and the sampling in one
+    kernel (csrc/vae_encode.hip); ``parameters`` / ``mean`` / ``logvar`` / ``std`` / ``var`` are the reference's attributes (the
+    quant_conv output from the same kernel, the rest as the reference's bf16 torch ops on it)."""
+
+    def __init__(self, encoder: _Encoder, raw: torch.Tensor, strides, shape, noise_dtype):
+        self._enc, self._raw, self._strides = encoder, raw, strides
+        self._B, self._H, self._W = shape
+        self._noise_dtype = noise_dtype
+        self._params = None
+        self.deterministic = False
+
+    @property
+    def latent_shape(self):
+        return (self._B, self._enc.latent_channels, self._H, self._W)
+
+    def _run(self, mode, **kw) -> torch.Tensor:
+        e = self._enc
+        y = ops.vae_posterior_latents(self._raw, self._strides, batch=self._B, hw=self._H * self._W,
+                                      latent_channels=e.latent_channels, mode=mode, wq=e.quant_w, bq=e.quant_b, **kw)
+        return y.view(self._B, -1, self._H, self._W)
+
+    @property
+    def parameters(self) -> torch.Tensor:
+        if self._params is None:
+            self._params = self._run(L.POSTERIOR_MOMENTS)
+        return self._params
+
+    @property
+    def mean(self):
+        return self.parameters[:, :self._enc.latent_channels]
+
+    @property
+    def logvar(self):
+        return torch.clamp(self.parameters[:, self._enc.latent_channels:], -30.0, 20.0)
+
+    @property
+    def std(self):
+        return torch.exp(0.5 * self.logvar)
+
+    @property
+    def var(self):
+        return torch.exp(self.logvar)
+
+    def draw_noise(self, generator=None, dtype=None) -> torch.Tensor:
+        """ε of ``sample``: randn_tensor (utils/torch_utils.py) of the latent shape -- on the generator's device, one draw per
+        generator when a list is given -- in the VAE's compute dtype (fp32 for a ``force_upcast`` VAE, as the reference's upcast
+        path draws), then bf16 for the kernel."""
+        shape, dev = self.latent_shape, self._raw.device
+        dtype = dtype or self._noise_dtype
+        if isinstance(generator, (list, tuple)):
+            if len(generator) != shape[0]:
+                raise ValueError(f"{len(generator)} generators for a batch of {shape[0]}")
+            draws = [torch.randn((1,) + shape[1:], generator=g, device=g.device, dtype=dtype) for g in generator]
+            eps = torch.cat([d.to(dev) for d in draws], 0)
+        else:
+            gdev = generator.device if generator is not None else dev
+            eps = torch.randn(shape, generator=generator, device=gdev, dtype=dtype)
+        return eps.to(device=dev, dtype=bf16).contiguous()
+
+    def sample(self, generator=None) -> torch.Tensor:
+        return self.latents(self.draw_noise(generator))
+
+    def mode(self) -> torch.Tensor:
+        return self.latents(None)
+
+    def latents(self, eps1: Optional[torch.Tensor], *, scale: Optional[float] = None, shift: Optional[float] = None,
+                noise: Optional[torch.Tensor] = None, a: float = 1.0, b: float = 0.0) -> torch.Tensor:
+        """Engine extension: ``mean + std * eps1`` (``eps1`` None: the mode), then ``(z - shift) * scale`` and
+        ``a z + b noise`` (scheduler.add_noise), each as the reference's bf16 op, in one pass."""
+        mode = L.POSTERIOR_MEAN if eps1 is None else L.POSTERIOR_SAMPLE
+        return self._run(mode, eps1=eps1, eps2=noise, scale=scale, shift=shift, a=a, b=b)
+
+
 class AutoencoderKL(PretrainedMixin):
     """Drop-in for the reference ``AutoencoderKL`` decode path (inference, bf16, HIP device only)."""
 
@@ -117,9 +242,11 @@ class AutoencoderKL(PretrainedMixin):
         self.device = None
         self._built = False
         self.post_quant_conv = None
+        self.encoder = None
 
     def load_state_dict(self, state_dict: Dict[str, torch.Tensor], device="cuda", strict: bool = False):
-        """Packs the decoder half (``decoder.*``, ``post_quant_conv.*``) of a reference AutoencoderKL state_dict."""
+        """Packs the decoder half (``decoder.*``, ``post_quant_conv.*``) of a reference AutoencoderKL state_dict, and the encoder
+        half (``encoder.*``, ``quant_conv.*``) when the state_dict holds it."""
         c = self.config
         w = Weights(state_dict, device)
         self.device = torch.device(device)
@@ -168,10 +295,11 @@ class AutoencoderKL(PretrainedMixin):
         self.conv_norm_out = GroupNorm(w, "decoder.conv_norm_out", groups, eps)
         self.conv_out_w = ops.pack_conv_weight(w.get("decoder.conv_out.weight"))
         self.conv_out_b = w.get("decoder.conv_out.bias")
+        self.encoder = _Encoder(w, c, groups, eps) if w.has("encoder.conv_in.weight") else None
         if strict:
-            extra = [k for k in w.unused() if k.startswith("decoder.") or k.startswith("post_quant_conv.")]
+            extra = [k for k in w.unused() if k.startswith(("decoder.", "post_quant_conv.", "encoder.", "quant_conv."))]
             if extra:
-                raise RuntimeError(f"unexpected decoder keys: {extra[:8]}")
+                raise RuntimeError(f"unexpected VAE keys: {extra[:8]}")
         self._built = True
         return self
 
@@ -181,8 +309,37 @@ class AutoencoderKL(PretrainedMixin):
     def eval(self):
         return self
 
-    def encode(self, *a, **k):
-        raise NotImplementedError("diffusers_amd.AutoencoderKL implements the decode hot path only")
+    def encode(self, x: torch.Tensor, return_dict: bool = True):
+        """autoencoder_kl.py:146-185: ``x`` NCHW in [-1, 1] (the reference's preprocessed image; fp32 or bf16, taken at bf16 as the
+        bf16 reference VAE does) -> ``AutoencoderKLOutput(latent_dist=DiagonalGaussianDistribution)``."""
+        self._require_encoder()
+        ops.require_hip(x, "x", dtypes=(bf16, torch.float32))
+        if x.dim() != 4 or x.shape[1] != self.config.in_channels:
+            raise ValueError(f"AutoencoderKL.encode: NCHW input with {self.config.in_channels} channels expected, got {tuple(x.shape)}")
+        dist = self.encode_image(x.float().contiguous(), nchw=True, normalize=False)
+        if not return_dict:
+            return (dist,)
+        return AutoencoderKLOutput(latent_dist=dist)
+
+    def _require_encoder(self):
+        if self.encoder is None:
+            raise NotImplementedError("AutoencoderKL.encode: the encoder half of this VAE was not loaded (its state_dict held no "
+                                      "encoder.* weights; build it with factory.build_vae(..., with_encoder=True) or load a "
+                                      "checkpoint that has them)")
+
+    def encode_image(self, img: torch.Tensor, *, nchw: bool, normalize: bool) -> DiagonalGaussianDistribution:
+        """Engine extension: the caller's image -- fp32 NCHW / NHWC or uint8 NHWC (read as x / 255), ``normalize``: 2 x - 1
+        (VaeImageProcessor.preprocess) -- straight into the encoder.  Sizes must be multiples of 2 ** (len(block_out_channels) - 1)."""
+        self._require_encoder()
+        ops.require_hip(img, "image", dtypes=(torch.float32, torch.uint8))
+        B = img.shape[0]
+        H, W_ = (img.shape[2], img.shape[3]) if nchw else (img.shape[1], img.shape[2])
+        f = 2 ** (len(self.config.block_out_channels) - 1)
+        if H % f or W_ % f:
+            raise ValueError(f"AutoencoderKL.encode: image size {H} x {W_} is not a multiple of {f} (the engine does not resize)")
+        raw, strides = self.encoder(img, nchw=nchw, normalize=normalize)
+        return DiagonalGaussianDistribution(self.encoder, raw, strides, (B, H // f, W_ // f),
+                                            torch.float32 if self.config.force_upcast else bf16)
 
     def decode(self, z: torch.Tensor, return_dict: bool = True, generator=None, *, latents_div: float = 1.0,
                latents_add: float = 0.0, postprocess: Optional[str] = None):

@@ -159,10 +159,27 @@ __global__ __launch_bounds__(256) void conv_thin_in_kernel(const uint16_t* __res
 // value from memory per 8 multiply-adds; here the weight vectors feed 32 multiply-adds (four pixels) and a kernel row's six input
 // columns are loaded once for the four pixels that share them.  Per output element the operations and their order are the ones of
 // the kernel above (bias, then taps in (kh, kw, c) order, the same input conversions): bit-identical.
-template <int CIN>
-__global__ __launch_bounds__(256) void conv_thin_in4_kernel(const uint16_t* __restrict__ x, const uint16_t* __restrict__ w,
+// SRC selects the loader: SRC_BF16 is the conv above; the image sources (the VAE encoder's conv_in, da_vae_conv_in_image) read the
+// caller's fp32 or uint8 image and convert every value as VaeImageProcessor.preprocess + the pipeline's cast do: uint8 -> x / 255
+// (__fdiv_rn: numpy's correctly rounded division of pil_to_numpy), then 2 x - 1 in fp32 when `normalize`, then the bf16 round.  Only the
+// loader differs; the loads stay unconditional from clamped addresses, so the result equals the SRC_BF16 kernel run on the converted image.
+enum { SRC_BF16 = 0, SRC_F32 = 1, SRC_U8 = 2 };
+template <int SRC>
+struct ThinInSrc;
+template <>
+struct ThinInSrc<SRC_BF16> { typedef uint16_t T; };
+template <>
+struct ThinInSrc<SRC_F32> { typedef float T; };
+template <>
+struct ThinInSrc<SRC_U8> { typedef uint8_t T; };
+
+template <int CIN, int SRC = SRC_BF16>
+__global__ __launch_bounds__(256) void conv_thin_in4_kernel(const void* __restrict__ x_any, const uint16_t* __restrict__ w,
                                                             const uint16_t* __restrict__ bias, uint16_t* __restrict__ y, int B, int H,
-                                                            int W, int Cout, int in_nchw, float in_div, float in_add, int coc) {
+                                                            int W, int Cout, int in_nchw, float in_div, float in_add, int coc,
+                                                            int normalize) {
+  typedef typename ThinInSrc<SRC>::T src_t;
+  const src_t* __restrict__ x = (const src_t*)x_any;
   extern __shared__ __attribute__((aligned(16))) float wsm[];  // [9 * CIN][coc]
   constexpr int kk = 9 * CIN;
   const int co0 = blockIdx.y * coc;
@@ -209,22 +226,37 @@ __global__ __launch_bounds__(256) void conv_thin_in4_kernel(const uint16_t* __re
       // select afterwards: behind `if (ok)` every load sat in its own exec-masked branch with its own s_waitcnt -- 72 serialised round
       // trips per thread, which WAS the kernel (U-Net conv_in 4 -> 320 at 128 x 128: 58 us for 21 MB of output; round 6).  Same values.
       // (layout strides instead of a per-element NCHW / NHWC select, and ONE uniform branch around the conversions: straight-line loads)
-      uint16_t raw[6][CIN];
+      src_t raw[6][CIN];
       const int iyc = min(max(iy, 0), H - 1);
-      const uint16_t* xrow = x + (size_t)b * sB + (size_t)iyc * sY;
+      const src_t* xrow = x + (size_t)b * sB + (size_t)iyc * sY;
 #pragma unroll
       for (int j = 0; j < 6; ++j) {
         const int ixc = min(max(x0 + j - 1, 0), W - 1);
 #pragma unroll
         for (int c = 0; c < CIN; ++c) raw[j][c] = xrow[(size_t)ixc * sX + (size_t)c * sC];
       }
-      if (convert_in) {
+      if (SRC != SRC_BF16) {
 #pragma unroll
         for (int j = 0; j < 6; ++j) {
           const bool ok = row_ok && (unsigned)(x0 + j - 1) < (unsigned)W;
 #pragma unroll
           for (int c = 0; c < CIN; ++c) {
-            float xv = bf2f(raw[j][c]);
+            float xv = (float)raw[j][c];
+            // (pins the load here: without it the compiler sinks the load of the one value only a padded-edge tap reads into that
+            // tap's exec-masked branch, with a wait of its own)
+            asm volatile("" : "+v"(xv));
+            if (SRC == SRC_U8) xv = __fdiv_rn(xv, 255.0f);
+            if (normalize) xv = __fsub_rn(__fmul_rn(2.0f, xv), 1.0f);
+            xin[j][c] = ok ? bf2f(f2bf(xv)) : 0.f;
+          }
+        }
+      } else if (convert_in) {
+#pragma unroll
+        for (int j = 0; j < 6; ++j) {
+          const bool ok = row_ok && (unsigned)(x0 + j - 1) < (unsigned)W;
+#pragma unroll
+          for (int c = 0; c < CIN; ++c) {
+            float xv = bf2f((uint16_t)raw[j][c]);
             if (in_div != 1.0f) xv = bf2f(f2bf(__fdiv_rn(xv, in_div)));
             if (in_add != 0.0f) xv = bf2f(f2bf(__fadd_rn(xv, in_add)));
             xin[j][c] = ok ? xv : 0.f;
@@ -235,7 +267,7 @@ __global__ __launch_bounds__(256) void conv_thin_in4_kernel(const uint16_t* __re
         for (int j = 0; j < 6; ++j) {
           const bool ok = row_ok && (unsigned)(x0 + j - 1) < (unsigned)W;
 #pragma unroll
-          for (int c = 0; c < CIN; ++c) xin[j][c] = ok ? bf2f(raw[j][c]) : 0.f;
+          for (int c = 0; c < CIN; ++c) xin[j][c] = ok ? bf2f((uint16_t)raw[j][c]) : 0.f;
         }
       }
       if (!row_ok) continue;
@@ -596,17 +628,42 @@ extern "C" int da_conv_thin_in_bf16(const void* x, const void* w, const void* bi
     size_t qblocks = ((size_t)B * H * ((W + 3) / 4) * (coc / 8) + 255) / 256;
     if (qblocks > cap) qblocks = cap;
     if (Cin == 4)
-      DA_LAUNCH(conv_thin_in4_kernel<4>, dim3((unsigned)qblocks, (unsigned)nchunk), dim3(256), lds, (hipStream_t)stream, (const uint16_t*)x,
-                (const uint16_t*)w, (const uint16_t*)bias, (uint16_t*)y, B, H, W, Cout, in_nchw, in_div, in_add, coc);
+      DA_LAUNCH(conv_thin_in4_kernel<4>, dim3((unsigned)qblocks, (unsigned)nchunk), dim3(256), lds, (hipStream_t)stream, x,
+                (const uint16_t*)w, (const uint16_t*)bias, (uint16_t*)y, B, H, W, Cout, in_nchw, in_div, in_add, coc, 0);
     else
-      DA_LAUNCH(conv_thin_in4_kernel<3>, dim3((unsigned)qblocks, (unsigned)nchunk), dim3(256), lds, (hipStream_t)stream, (const uint16_t*)x,
-                (const uint16_t*)w, (const uint16_t*)bias, (uint16_t*)y, B, H, W, Cout, in_nchw, in_div, in_add, coc);
+      DA_LAUNCH(conv_thin_in4_kernel<3>, dim3((unsigned)qblocks, (unsigned)nchunk), dim3(256), lds, (hipStream_t)stream, x,
+                (const uint16_t*)w, (const uint16_t*)bias, (uint16_t*)y, B, H, W, Cout, in_nchw, in_div, in_add, coc, 0);
     DA_CHECK_LAUNCH();
     return DA_OK;
   }
   DA_LAUNCH(conv_thin_in_kernel, dim3((unsigned)blocks, (unsigned)nchunk), dim3(256), lds, (hipStream_t)stream,
             (const uint16_t*)x, (const uint16_t*)w, (const uint16_t*)bias, (uint16_t*)y, B, H, W, Cin, Cout, ksize,
             in_nchw, in_div, in_add, coc);
+  DA_CHECK_LAUNCH();
+  return DA_OK;
+}
+
+extern "C" int da_vae_conv_in_image(const void* x, int src, const void* w, const void* bias, void* y, int B, int H, int W,
+                                    int Cout, int normalize, void* stream) {
+  if (!x || !w || !y || B <= 0 || H <= 0 || W <= 0 || src < DA_IMAGE_F32_NCHW || src > DA_IMAGE_U8_NHWC) return DA_ERR_INVALID;
+  if (Cout <= 0 || (Cout & 7)) return DA_ERR_UNSUPPORTED;
+  // the launch geometry of the four-pixel branch of da_conv_thin_in_bf16 (Cin = 3, k = 3): same chunks, same grid
+  const int kk = 9 * 3;
+  int coc = ((64 * 1024) / (kk * (int)sizeof(float))) & ~7;
+  if (coc > Cout) coc = Cout;
+  const int nchunk = (Cout + coc - 1) / coc;
+  const size_t lds = (size_t)coc * kk * sizeof(float);
+  const size_t cap = 768 / nchunk > 0 ? 768 / nchunk : 1;
+  size_t qblocks = ((size_t)B * H * ((W + 3) / 4) * (coc / 8) + 255) / 256;
+  if (qblocks > cap) qblocks = cap;
+  const dim3 grid((unsigned)qblocks, (unsigned)nchunk);
+  hipStream_t s = (hipStream_t)stream;
+  if (src == DA_IMAGE_U8_NHWC)
+    DA_LAUNCH((conv_thin_in4_kernel<3, SRC_U8>), grid, dim3(256), lds, s, x, (const uint16_t*)w, (const uint16_t*)bias, (uint16_t*)y, B, H,
+              W, Cout, 0, 1.0f, 0.0f, coc, normalize);
+  else
+    DA_LAUNCH((conv_thin_in4_kernel<3, SRC_F32>), grid, dim3(256), lds, s, x, (const uint16_t*)w, (const uint16_t*)bias, (uint16_t*)y, B,
+              H, W, Cout, src == DA_IMAGE_F32_NCHW ? 1 : 0, 1.0f, 0.0f, coc, normalize);
   DA_CHECK_LAUNCH();
   return DA_OK;
 }

@@ -6,7 +6,8 @@ from typing import Optional
 from . import init as dinit
 from .autoencoder_kl import AutoencoderKL
 from .autoencoder_kl_wan import AutoencoderKLWan
-from .pipelines import DDPMPipeline, FluxPipeline, StableDiffusionPipeline, StableDiffusionXLPipeline, WanPipeline
+from .pipelines import (DDPMPipeline, FluxPipeline, StableDiffusionImg2ImgPipeline, StableDiffusionPipeline,
+                        StableDiffusionXLImg2ImgPipeline, StableDiffusionXLPipeline, WanPipeline)
 from .schedulers import DDPMScheduler
 from .unet_2d import UNet2DModel
 from .transformer_wan import WanTransformer3DModel
@@ -29,10 +30,15 @@ def build_unet(cfg: dict, seed: int = 0, device="cuda", init_device: Optional[st
     return unet, state_dict
 
 
-def build_vae(cfg: dict, seed: int = 1, device="cuda", init_device: Optional[str] = None, state_dict=None):
+def build_vae(cfg: dict, seed: int = 1, device="cuda", init_device: Optional[str] = None, state_dict=None,
+              with_encoder: bool = False):
+    """``with_encoder``: the encoder half (+ quant_conv) as well, for ``encode`` (random_state_dict seeds per key: the decoder
+    weights are the same either way)."""
     vae = AutoencoderKL(**cfg)
     if state_dict is None:
         shapes = dinit.vae_decoder_param_shapes(vae.config)
+        if with_encoder:
+            shapes.update(dinit.vae_encoder_param_shapes(vae.config))
         state_dict = dinit.random_state_dict(shapes, seed=seed, device=init_device or "cpu")
     vae.load_state_dict(state_dict, device=device)
     return vae, state_dict
@@ -47,25 +53,30 @@ def build_wan_vae(cfg: dict, seed: int = 21, device="cuda", init_device: Optiona
     return vae, state_dict
 
 
-def build_sdxl_pipeline(device="cuda", tiny: bool = False, seed: int = 0, init_device: Optional[str] = None):
+def build_sdxl_pipeline(device="cuda", tiny: bool = False, seed: int = 0, init_device: Optional[str] = None,
+                        with_encoder: bool = False, img2img: bool = False):
     """SDXL-base (BASELINE config 3) or its tiny sibling.  Full size: weights are generated on ``init_device``
-    (default: the HIP device, ~2.6 B parameters in seconds) and freed after packing."""
+    (default: the HIP device, ~2.6 B parameters in seconds) and freed after packing.  ``with_encoder``: the VAE's encoder as
+    well; ``img2img``: the same components in a StableDiffusionXLImg2ImgPipeline (implies ``with_encoder``)."""
     ucfg = dinit.TINY_SDXL_UNET if tiny else dinit.SDXL_UNET
     vcfg = dinit.TINY_VAE if tiny else dinit.SDXL_VAE
     idev = init_device or ("cpu" if tiny else str(device))
     unet, _ = build_unet(ucfg, seed=seed, device=device, init_device=idev)
-    vae, _ = build_vae(vcfg, seed=seed + 1, device=device, init_device=idev)
+    vae, _ = build_vae(vcfg, seed=seed + 1, device=device, init_device=idev, with_encoder=with_encoder or img2img)
     sch = EulerDiscreteScheduler(**SDXL_SCHEDULER)
-    return StableDiffusionXLPipeline(vae=vae, unet=unet, scheduler=sch)
+    cls = StableDiffusionXLImg2ImgPipeline if img2img else StableDiffusionXLPipeline
+    return cls(vae=vae, unet=unet, scheduler=sch)
 
 
-def build_sd15_pipeline(device="cuda", tiny: bool = False, seed: int = 0, init_device: Optional[str] = None):
+def build_sd15_pipeline(device="cuda", tiny: bool = False, seed: int = 0, init_device: Optional[str] = None,
+                        with_encoder: bool = False, img2img: bool = False):
     ucfg = dinit.TINY_SD15_UNET if tiny else dinit.SD15_UNET
     vcfg = dinit.TINY_VAE if tiny else dinit.SD_VAE
     idev = init_device or ("cpu" if tiny else str(device))
     unet, _ = build_unet(ucfg, seed=seed, device=device, init_device=idev)
-    vae, _ = build_vae(vcfg, seed=seed + 1, device=device, init_device=idev)
-    return StableDiffusionPipeline(vae=vae, unet=unet, scheduler=DDIMScheduler(**SD15_SCHEDULER))
+    vae, _ = build_vae(vcfg, seed=seed + 1, device=device, init_device=idev, with_encoder=with_encoder or img2img)
+    cls = StableDiffusionImg2ImgPipeline if img2img else StableDiffusionPipeline
+    return cls(vae=vae, unet=unet, scheduler=DDIMScheduler(**SD15_SCHEDULER))
 
 
 def build_flux_transformer(cfg: dict, seed: int = 5, device="cuda", init_device: Optional[str] = None, state_dict=None):

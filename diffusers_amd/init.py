@@ -157,6 +157,42 @@ def vae_decoder_param_shapes(cfg) -> "OrderedDict[str, Tuple[int, ...]]":
     return sh
 
 
+def vae_encoder_param_shapes(cfg) -> "OrderedDict[str, Tuple[int, ...]]":
+    """Encoder half (+ quant_conv) of AutoencoderKL's state_dict: Encoder (vae.py:61-184) with DownEncoderBlock2D
+    (unet_2d_blocks.py:1421-1502, downsample_padding=0) and the mid block; disjoint from vae_decoder_param_shapes."""
+    sh: "OrderedDict[str, Tuple[int, ...]]" = OrderedDict()
+    boc = tuple(cfg["block_out_channels"])
+    lat = cfg["latent_channels"]
+    sh["encoder.conv_in.weight"] = (boc[0], cfg["in_channels"], 3, 3)
+    sh["encoder.conv_in.bias"] = (boc[0],)
+    out_c = boc[0]
+    for i in range(len(boc)):
+        prev, out_c = out_c, boc[i]
+        for j in range(cfg["layers_per_block"]):
+            _resnet(sh, f"encoder.down_blocks.{i}.resnets.{j}", prev if j == 0 else out_c, out_c, 0)
+        if i != len(boc) - 1:
+            sh[f"encoder.down_blocks.{i}.downsamplers.0.conv.weight"] = (out_c, out_c, 3, 3)
+            sh[f"encoder.down_blocks.{i}.downsamplers.0.conv.bias"] = (out_c,)
+    top = boc[-1]
+    _resnet(sh, "encoder.mid_block.resnets.0", top, top, 0)
+    if cfg["mid_block_add_attention"]:
+        a = "encoder.mid_block.attentions.0"
+        sh[f"{a}.group_norm.weight"] = (top,)
+        sh[f"{a}.group_norm.bias"] = (top,)
+        for nm in ("to_q", "to_k", "to_v", "to_out.0"):
+            sh[f"{a}.{nm}.weight"] = (top, top)
+            sh[f"{a}.{nm}.bias"] = (top,)
+    _resnet(sh, "encoder.mid_block.resnets.1", top, top, 0)
+    sh["encoder.conv_norm_out.weight"] = (top,)
+    sh["encoder.conv_norm_out.bias"] = (top,)
+    sh["encoder.conv_out.weight"] = (2 * lat, top, 3, 3)
+    sh["encoder.conv_out.bias"] = (2 * lat,)
+    if cfg["use_quant_conv"]:
+        sh["quant_conv.weight"] = (2 * lat, 2 * lat, 1, 1)
+        sh["quant_conv.bias"] = (2 * lat,)
+    return sh
+
+
 def _lin(sh, p, n_out, n_in, bias=True):
     sh[f"{p}.weight"] = (n_out, n_in)
     if bias:

@@ -1232,3 +1232,90 @@ def conv_thin_out(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor]
     L.check(L.load().da_conv_thin_out_bf16(x.data_ptr(), w.data_ptr(), _ptr(bias), y.data_ptr(), B, H, W_, Cin, Cout,
                                            int(out_f32), _stream()), "da_conv_thin_out_bf16")
     return y if postprocess is None else image_postprocess(y, postprocess)
+
+
+# ---- the two ends of the VAE encoder (csrc/misc.hip image loader, csrc/vae_encode.hip) -------------------------------------
+_IMAGE_SRC = {(torch.float32, True): L.IMAGE_F32_NCHW, (torch.float32, False): L.IMAGE_F32_NHWC, (torch.uint8, False): L.IMAGE_U8_NHWC}
+
+
+def vae_conv_in_image(img: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor], *, nchw: bool,
+                      normalize: bool) -> torch.Tensor:
+    """VaeImageProcessor.preprocess's conversion + the pipeline's bf16 cast + the encoder's conv_in (3 -> Cout, 3x3, pad 1) in one
+    pass.  img: fp32 NCHW [B][3][H][W], fp32 NHWC or uint8 NHWC [B][H][W][3] (uint8 is read as x / 255); w: [Cout][27] (packed
+    with pack_conv_weight); returns NHWC bf16 [B][H][W][Cout]."""
+    require_hip(img, "image", dtypes=(torch.float32, torch.uint8))
+    _req(w, "w")
+    src = _IMAGE_SRC.get((img.dtype, bool(nchw)))
+    if src is None:
+        raise ValueError(f"vae_conv_in_image: {img.dtype} {'NCHW' if nchw else 'NHWC'} images are not a supported source "
+                         "(fp32 NCHW, fp32 NHWC, uint8 NHWC)")
+    if not img.is_contiguous() or img.dim() != 4:
+        raise ValueError("vae_conv_in_image: a contiguous 4-D image is required")
+    B, C, H, W_ = img.shape if nchw else (img.shape[0], img.shape[3], img.shape[1], img.shape[2])
+    if C != 3 or w.shape[1] != 27:
+        raise ValueError(f"vae_conv_in_image: 3-channel images and a 3 -> Cout 3x3 weight only (image has {C} channels)")
+    Cout = w.shape[0]
+    y = torch.empty((B, H, W_, Cout), device=img.device, dtype=bf16)
+    L.check(L.load().da_vae_conv_in_image(img.data_ptr(), src, w.data_ptr(), _ptr(bias), y.data_ptr(), B, H, W_, Cout,
+                                          int(bool(normalize)), _stream()), "da_vae_conv_in_image")
+    return y
+
+
+def conv_thin_out_moments(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor]):
+    """The encoder's conv_out (Cin -> 2 L, 3x3) WITHOUT the NCHW layout pass of conv_thin_out: returns ``(y, (sB, sC, sP))`` --
+    the implicit-GEMM result [B][H][W][THIN_OUT_PAD] (sC = 1, sP = 16) where conv_thin_out takes that route, else conv_thin_out's
+    NCHW output (sC = H W, sP = 1) -- for vae_posterior_latents to read in place.  Same values as conv_thin_out."""
+    _req(x, "x"), _req(w, "w")
+    B, H, W_, Cin = x.shape
+    Cout = w.shape[0]
+    if Cin % 64 == 0 and Cout <= 8 and B * H * W_ >= 4096 and w.shape[1] == 9 * Cin:
+        wp, bp = pad_thin_out(w, bias)
+        y16 = conv2d_nhwc(x, wp, bp, ksize=3)
+        return y16, (H * W_ * THIN_OUT_PAD, 1, THIN_OUT_PAD)
+    y = conv_thin_out(x, w, bias)
+    return y, (Cout * H * W_, H * W_, 1)
+
+
+def vae_posterior_latents(x: torch.Tensor, strides, *, batch: int, hw: int, latent_channels: int, mode: int,
+                          wq: Optional[torch.Tensor] = None, bq: Optional[torch.Tensor] = None, eps1: Optional[torch.Tensor] = None,
+                          eps2: Optional[torch.Tensor] = None, shift: Optional[float] = None, scale: Optional[float] = None,
+                          a: float = 1.0, b: float = 0.0) -> torch.Tensor:
+    """csrc/vae_encode.hip (operation order in its header comment).  ``x``: the conv_out result read through ``strides`` = (sB, sC, sP)
+    in elements (conv_thin_out_moments), or -- mode POSTERIOR_NOISE -- latents; ``wq`` [2L][2L] / ``bq`` [2L]: quant_conv; ``eps1``:
+    the sample noise, ``eps2``: scheduler.add_noise's noise with the coefficients ``a`` (sample) and ``b`` (noise), [B][L][H][W] bf16.
+    Returns NCHW bf16 [B][2L or L][HW] (the caller reshapes)."""
+    _req(x, "x")
+    Lc = int(latent_channels)
+    sB, sC, sP = (int(v) for v in strides)
+    cin = Lc if mode == L.POSTERIOR_NOISE else 2 * Lc
+    last = (batch - 1) * sB + (cin - 1) * sC + (hw - 1) * sP
+    if min(sB, sC, sP) < 0 or last >= x.numel():
+        raise ValueError(f"vae_posterior_latents: strides {strides} reach element {last} of a {x.numel()}-element input")
+    n_lat = batch * Lc * hw
+    for t, nm in ((eps1, "eps1"), (eps2, "eps2")):
+        if t is not None:
+            _req(t, nm)
+            if t.numel() != n_lat or not t.is_contiguous():
+                raise ValueError(f"vae_posterior_latents: {nm} must be a contiguous [B][L][H][W] tensor of {n_lat} elements")
+    if wq is not None:
+        _req(wq, "wq"), _req(bq, "bq")
+        if tuple(wq.shape) != (2 * Lc, 2 * Lc) or tuple(bq.shape) != (2 * Lc,):
+            raise ValueError("vae_posterior_latents: quant_conv weight [2L][2L] and bias [2L] required")
+    flags = (L.LATENTS_SHIFT if shift is not None else 0) | (L.LATENTS_SCALE if scale is not None else 0)
+    out = torch.empty((batch, 2 * Lc if mode == L.POSTERIOR_MOMENTS else Lc, hw), device=x.device, dtype=bf16)
+    L.check(L.load().da_vae_posterior_latents(x.data_ptr(), sB, sC, sP, _ptr(wq), _ptr(bq), _ptr(eps1), _ptr(eps2), out.data_ptr(),
+                                              batch, hw, Lc, mode, flags, float(shift or 0.0), float(scale if scale is not None else 1.0),
+                                              float(a), float(b), _stream()), "da_vae_posterior_latents")
+    return out
+
+
+def add_noise(x: torch.Tensor, noise: torch.Tensor, a: float, b: float) -> torch.Tensor:
+    """Scheduler.add_noise's arithmetic on bf16 latents: bf16(bf16(a x) + bf16(b noise)), any shape (contiguous [B][C][...])."""
+    _req(x, "original_samples"), _req(noise, "noise")
+    if x.shape != noise.shape or x.dim() < 2:
+        raise ValueError(f"add_noise: samples {tuple(x.shape)} and noise {tuple(noise.shape)} must have one shape (B, C, ...)")
+    x, noise = x.contiguous(), noise.contiguous()
+    B, C = x.shape[0], x.shape[1]
+    hw = x[0, 0].numel()
+    out = vae_posterior_latents(x, (C * hw, hw, 1), batch=B, hw=hw, latent_channels=C, mode=L.POSTERIOR_NOISE, eps2=noise, a=a, b=b)
+    return out.view(x.shape)

@@ -34,6 +34,10 @@ _SHAPES: Dict[str, Callable] = {
     "WanTransformer3DModel": dinit.wan_param_shapes,
     "UNet2DModel": dinit.unet2d_param_shapes,
 }
+# optional halves a checkpoint may or may not hold: (packed-path prefix, inventory) -- in the skeleton when the file has them
+_OPTIONAL_SHAPES: Dict[str, Tuple[str, Callable]] = {
+    "AutoencoderKL": ("encoder.", dinit.vae_encoder_param_shapes),
+}
 
 
 def _walk(obj, path: str, visit, seen: set) -> None:
@@ -128,6 +132,11 @@ def load_packed(cls, path, device="cuda", expect_fingerprint: str = ""):
     cfg = {k: _tuples(v) for k, v in json.loads(meta["config"]).items()}
     model = cls(**cfg)
     shapes = _SHAPES[cls.__name__](dict(model.config))
+    opt = _OPTIONAL_SHAPES.get(cls.__name__)
+    if opt is not None:
+        with safe_open(str(path), framework="pt", device="cpu") as f:
+            if any(k.startswith(opt[0]) for k in f.keys()):
+                shapes.update(opt[1](dict(model.config)))
     skeleton_sd = {k: torch.empty(tuple(s), dtype=torch.bfloat16, device="meta") for k, s in shapes.items()}
     model.load_state_dict(skeleton_sd, device="meta")
     dev = torch.device(device)

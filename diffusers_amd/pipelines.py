@@ -228,12 +228,13 @@ class _StepCallbacks:
             raise ValueError(f"`callback_on_step_end_tensor_inputs` has to be in {self._callback_tensor_inputs}, but found {bad}")
         self._step_callback = (callback_on_step_end, names) if callback_on_step_end is not None else None
 
-    def _after_step(self, i: int, latents: torch.Tensor) -> bool:
-        """Runs the armed callback after step ``i``; False = the loop stops here."""
+    def _after_step(self, i: int, latents: torch.Tensor, begin: int = 0) -> bool:
+        """Runs the armed callback after step ``i`` of the loop (schedule entry ``begin + i``: img2img loops start at the
+        scheduler's begin index); False = the loop stops here."""
         if self._step_callback is None:
             return True
         fn, names = self._step_callback
-        out = fn(self, i, self.scheduler.timesteps[i], {k: latents for k in names})
+        out = fn(self, i, self.scheduler.timesteps[begin + i], {k: latents for k in names})
         if out is not None:
             new = out.pop("latents", latents)
             if new is not latents:
@@ -299,14 +300,16 @@ class _LatentDiffusionBase(_StepCallbacks, PipelineLoadingMixin):
                 self._noise_table.data_ptr() if self._noise_table is not None else 0, float(self._eta),
                 float(self._guidance_rescale), id(self.unet))       # (a captured step points into THIS model's packed weights)
 
-    def _denoise(self, latents, cond, num_steps, guidance_scale, do_cfg, use_graph):
+    def _denoise(self, latents, cond, num_steps, guidance_scale, do_cfg, use_graph, begin: int = 0):
+        """``num_steps`` steps from schedule entry ``begin`` (img2img / the refiner hand-off start past 0).  The captured step reads
+        its row from the device step counter, so every start replays the same graph: warm-up, capture and replay rewind to ``begin``."""
         sch = self.scheduler
-        sch.reset(0)
+        sch.reset(begin)
         if not use_graph:
             for i in range(num_steps):
                 with ops.weight_prefetch(_pf(self), "apply" if i else "record"):
                     self._step(latents, cond, guidance_scale, do_cfg)
-                if not self._after_step(i, latents):
+                if not self._after_step(i, latents, begin):
                     break
             return latents
         key = self._make_graph_key(latents, cond, guidance_scale, do_cfg) + (use_graph == "plan",)
@@ -320,12 +323,12 @@ class _LatentDiffusionBase(_StepCallbacks, PipelineLoadingMixin):
                     self._step(latents, cond, guidance_scale, do_cfg)
             torch.cuda.current_stream().wait_stream(s)
             latents.copy_(saved)
-            sch.reset(0)
+            sch.reset(begin)
             g = _capture_step(self, lambda: self._step(latents, cond, guidance_scale, do_cfg), use_graph)
             self._graph, self._graph_key = g, key
             self._static = {"latents": latents, "cond": cond, "noise_table": self._noise_table}
             latents.copy_(saved)
-            sch.reset(0)
+            sch.reset(begin)
         else:
             # same shapes: refresh the graph's static inputs (device-to-device copies, no re-capture)
             self._static["latents"].copy_(latents)
@@ -341,9 +344,9 @@ class _LatentDiffusionBase(_StepCallbacks, PipelineLoadingMixin):
         for i in range(num_steps):
             self._graph.replay()
             done = i + 1
-            if not self._after_step(i, latents):
+            if not self._after_step(i, latents, begin):
                 break
-        sch._step_index = done
+        sch._step_index = begin + done
         return latents
 
     def _decode(self, latents, output_type):
@@ -546,6 +549,351 @@ class StableDiffusionPipeline(_LatentDiffusionBase):
             self._static["noise_table"] = table
             self._noise_table = table
         latents = self._denoise(latents, cond, num_inference_steps, guidance_scale, do_cfg, use_graph)
+        images = self._decode(latents, output_type)
+        if not return_dict:
+            return (images,)
+        return PipelineOutput(images=images)
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# image-to-image (pipeline_stable_diffusion_xl_img2img.py, pipeline_stable_diffusion_img2img.py)
+# ----------------------------------------------------------------------------------------------------------------------
+def get_timesteps(scheduler, num_inference_steps: int, strength: float, denoising_start: Optional[float] = None):
+    """The img2img pipelines' ``get_timesteps``: the schedule's tail that runs -- from ``strength`` (t_start = n - min(int(n strength), n)),
+    or, given ``denoising_start``, the entries below its cut-off (the refiner side of a base + refiner hand-off) -- as
+    ``(timesteps, num_steps, begin)``; ``scheduler.set_begin_index(begin)`` is called as the reference does."""
+    order = scheduler.order
+    if denoising_start is None:
+        init_timestep = min(int(num_inference_steps * strength), num_inference_steps)
+        t_start = max(num_inference_steps - init_timestep, 0)
+        begin = t_start * order
+        scheduler.set_begin_index(begin)
+        return scheduler.timesteps[begin:], num_inference_steps - t_start, begin
+    n_train = scheduler.config.num_train_timesteps
+    cutoff = int(round(n_train - denoising_start * n_train))
+    n = int((scheduler.timesteps < cutoff).sum().item())
+    if order == 2 and n % 2 == 0:
+        n += 1
+    begin = len(scheduler.timesteps) - n
+    scheduler.set_begin_index(begin)
+    return scheduler.timesteps[begin:], n, begin
+
+
+def _denoising_value_valid(v) -> bool:
+    return isinstance(v, float) and 0.0 < v < 1.0
+
+
+def _randn(shape, generator, device, dtype):
+    """utils/torch_utils.py randn_tensor: drawn on the generator's device (on ``device`` without one), one draw per generator of a
+    list, then moved to ``device``."""
+    if isinstance(generator, (list, tuple)):
+        if len(generator) != shape[0]:
+            raise ValueError(f"{len(generator)} generators for a batch of {shape[0]}")
+        return torch.cat([torch.randn((1,) + tuple(shape[1:]), generator=g, device=g.device, dtype=dtype).to(device)
+                          for g in generator], 0)
+    gdev = generator.device if generator is not None else device
+    return torch.randn(tuple(shape), generator=generator, device=gdev, dtype=dtype).to(device)
+
+
+def prepare_image(image, vae_scale_factor: int, latent_channels: int, device):
+    """``image`` as the encoder reads it: ``("latents", NCHW tensor)`` for latents (``latent_channels`` channels: encode is skipped,
+    as the reference does), else ``("image", tensor, nchw, normalize)`` for ops.vae_conv_in_image.  VaeImageProcessor.preprocess
+    (image_processor.py:581-715): a torch tensor is NCHW in [0, 1] -- or already in [-1, 1] (its minimum < 0), then it is not
+    normalised again; a numpy array is NHWC (float in [0, 1], or uint8 read as x / 255 like a PIL image); a PIL image is taken via
+    numpy.  The engine does not resize: sizes that are not a multiple of the VAE's scale factor are refused."""
+    if isinstance(image, (list, tuple)):
+        if not image:
+            raise ValueError("`image` is an empty list")
+        if all(torch.is_tensor(i) for i in image):
+            image = torch.cat([i if i.dim() == 4 else i.unsqueeze(0) for i in image], 0)
+        else:
+            image = np.stack([np.asarray(_pil_rgb(i)) if not isinstance(i, np.ndarray) else i for i in image], 0)
+    if not torch.is_tensor(image) and not isinstance(image, np.ndarray):
+        if hasattr(image, "convert"):                       # PIL.Image
+            image = np.asarray(_pil_rgb(image))
+        else:
+            raise ValueError(f"`image` has to be of type `torch.Tensor`, `np.ndarray`, `PIL.Image.Image` or a list of them, "
+                             f"but is {type(image)}")
+    if torch.is_tensor(image):
+        t = image if image.dim() == 4 else image.unsqueeze(0)
+        if t.dim() != 4:
+            raise ValueError(f"`image` tensor must be NCHW or CHW, got shape {tuple(image.shape)}")
+        if t.shape[1] == latent_channels:
+            return ("latents", t.to(device=device, dtype=bf16).contiguous())
+        if t.shape[1] != 3:
+            raise ValueError(f"`image` tensor has {t.shape[1]} channels: 3 (an image) or {latent_channels} (latents) expected")
+        H, W_, nchw = t.shape[2], t.shape[3], True
+        t = t.to(device=device, dtype=torch.float32).contiguous()
+    else:
+        a = image if image.ndim == 4 else image[None]
+        if a.ndim != 4 or a.shape[-1] != 3:
+            raise ValueError(f"`image` array must be NHWC / HWC with 3 channels, got shape {tuple(image.shape)}")
+        if a.dtype != np.uint8:
+            a = a.astype(np.float32)
+        H, W_, nchw = a.shape[1], a.shape[2], False
+        t = torch.from_numpy(np.ascontiguousarray(a)).to(device)
+    if H % vae_scale_factor or W_ % vae_scale_factor:
+        raise ValueError(f"`image` is {H} x {W_}: height and width must be multiples of the VAE scale factor {vae_scale_factor} "
+                         "(the engine does not resize images)")
+    normalize = t.dtype == torch.uint8 or not bool(t.min() < 0)
+    return ("image", t, nchw, normalize)
+
+
+def _pil_rgb(img):
+    return img.convert("RGB") if hasattr(img, "mode") and img.mode != "RGB" else img
+
+
+class _Img2ImgMixin:
+    """prepare_latents of the img2img pipelines: encode (or take latents), sample the posterior, scale, repeat to the batch, add noise --
+    the posterior, scaling and add_noise fused into one kernel when the batch needs no repetition."""
+
+    def get_timesteps(self, num_inference_steps, strength, device=None, denoising_start=None):
+        ts, n, _ = get_timesteps(self.scheduler, num_inference_steps, strength, denoising_start)
+        return ts, n
+
+    def _img2img_latents(self, image, timestep, batch: int, generator, add_noise: bool, noise_dtype):
+        vc = self.vae.config
+        if vc.get("latents_mean") is not None or vc.get("latents_std") is not None:
+            raise NotImplementedError("AutoencoderKL configs with latents_mean / latents_std are not supported by the engine "
+                                      "pipelines (pass `image` as latents you normalised yourself)")
+        dev = self.device
+        prep = prepare_image(image, self.vae_scale_factor, self.unet.config.in_channels, dev)
+        if prep[0] == "latents":
+            init = prep[1].clone()        # (the loop updates its latents in place: never the caller's tensor)
+            dist = None
+        else:
+            _, img, nchw, normalize = prep
+            if isinstance(generator, (list, tuple)) and img.shape[0] < batch and batch % img.shape[0] == 0:
+                img = torch.cat([img] * (batch // img.shape[0]), 0)
+            dist = self.vae.encode_image(img, nchw=nchw, normalize=normalize)
+            eps1 = dist.draw_noise(generator, dtype=noise_dtype)
+            if dist.latent_shape[0] == batch and add_noise:
+                noise = _randn(dist.latent_shape, generator, dev, bf16)
+                a, b = self.scheduler._add_noise_coeffs(timestep, bf16)
+                if len(set(zip(a, b))) == 1:
+                    return dist.latents(eps1, scale=float(vc.scaling_factor), noise=noise, a=a[0], b=b[0])
+                init = dist.latents(eps1, scale=float(vc.scaling_factor))
+                return self.scheduler.add_noise(init, noise, timestep)
+            init = dist.latents(eps1, scale=float(vc.scaling_factor))
+        n = init.shape[0]
+        if batch > n and batch % n == 0:
+            init = torch.cat([init] * (batch // n), 0)
+        elif batch != n:
+            raise ValueError(f"Cannot duplicate `image` of batch size {n} to {batch} text prompts.")
+        if add_noise:
+            noise = _randn(init.shape, generator, dev, bf16)
+            init = self.scheduler.add_noise(init, noise, timestep)
+        return init.contiguous()
+
+
+def _check_strength(strength):
+    if strength < 0 or strength > 1:
+        raise ValueError(f"The value of strength should in [0.0, 1.0] but is {strength}")
+
+
+def _no_steps(strength, n):
+    if n < 1:
+        raise ValueError(f"After adjusting the num_inference_steps by strength parameter: {strength}, the number of pipeline "
+                         f"steps is {n} which is < 1 and not appropriate for this pipeline.")
+
+
+class StableDiffusionXLImg2ImgPipeline(_Img2ImgMixin, StableDiffusionXLPipeline):
+    """pipeline_stable_diffusion_xl_img2img.py (__call__ :1011-1561): the SDXL img2img / refiner pipeline on the engine.  Same
+    captured denoising step as StableDiffusionXLPipeline, started at the scheduler's begin index."""
+
+    def __init__(self, vae, unet, scheduler, text_encoder=None, text_encoder_2=None, tokenizer=None, tokenizer_2=None,
+                 image_encoder=None, feature_extractor=None, requires_aesthetics_score: bool = False,
+                 force_zeros_for_empty_prompt: bool = True):
+        super().__init__(vae, unet, scheduler, text_encoder, text_encoder_2, tokenizer, tokenizer_2, force_zeros_for_empty_prompt)
+        if image_encoder is not None:
+            raise NotImplementedError("IP-Adapter image encoders are outside this engine")
+        self.requires_aesthetics_score = bool(requires_aesthetics_score)
+
+    def _get_add_time_ids(self, original_size, crops_coords_top_left, target_size, aesthetic_score, negative_aesthetic_score,
+                          negative_original_size, negative_crops_coords_top_left, negative_target_size, dtype=bf16,
+                          text_encoder_projection_dim=None):
+        """:799-853: with ``requires_aesthetics_score`` (the refiner) the ids end in the aesthetic score instead of the target size."""
+        if self.requires_aesthetics_score:
+            add_time_ids = list(original_size + crops_coords_top_left + (aesthetic_score,))
+            add_neg_time_ids = list(negative_original_size + negative_crops_coords_top_left + (negative_aesthetic_score,))
+        else:
+            add_time_ids = list(original_size + crops_coords_top_left + target_size)
+            add_neg_time_ids = list(negative_original_size + crops_coords_top_left + negative_target_size)
+        c = self.unet.config
+        passed = c.addition_time_embed_dim * len(add_time_ids) + text_encoder_projection_dim
+        expected = c.projection_class_embeddings_input_dim
+        if expected > passed and expected - passed == c.addition_time_embed_dim:
+            raise ValueError(f"Model expects an added time embedding vector of length {expected}, but a vector of {passed} was "
+                             "created. Please make sure to enable `requires_aesthetics_score` with "
+                             "`pipe.register_to_config(requires_aesthetics_score=True)` to make sure `aesthetic_score` "
+                             f"{aesthetic_score} and `negative_aesthetic_score` {negative_aesthetic_score} is correctly used by the model.")
+        if expected < passed and passed - expected == c.addition_time_embed_dim:
+            raise ValueError(f"Model expects an added time embedding vector of length {expected}, but a vector of {passed} was "
+                             "created. Please make sure to disable `requires_aesthetics_score` with "
+                             "`pipe.register_to_config(requires_aesthetics_score=False)` to make sure `target_size` "
+                             f"{target_size} is correctly used by the model.")
+        if expected != passed:
+            raise ValueError(f"Model expects an added time embedding vector of length {expected}, but a vector of {passed} was "
+                             "created. The model has an incorrect config. Please check `unet.config.time_embedding_type` and "
+                             "`text_encoder_2.config.projection_dim`.")
+        # (built in the prompt embeddings' dtype, as the reference does; the U-Net reads them as fp32)
+        return (torch.tensor([add_time_ids], dtype=dtype).float(), torch.tensor([add_neg_time_ids], dtype=dtype).float())
+
+    @torch.no_grad()
+    def __call__(self, prompt=None, prompt_2=None, image=None, strength: float = 0.3, num_inference_steps: int = 50,
+                 timesteps=None, sigmas=None, denoising_start: Optional[float] = None, denoising_end: Optional[float] = None,
+                 guidance_scale: float = 5.0, negative_prompt=None, negative_prompt_2=None, num_images_per_prompt: int = 1,
+                 eta: float = 0.0, generator=None, latents: Optional[torch.Tensor] = None, prompt_embeds=None,
+                 negative_prompt_embeds=None, pooled_prompt_embeds=None, negative_pooled_prompt_embeds=None,
+                 output_type: str = "pt", return_dict: bool = True, guidance_rescale: float = 0.0,
+                 original_size: Optional[Tuple[int, int]] = None, crops_coords_top_left: Tuple[int, int] = (0, 0),
+                 target_size: Optional[Tuple[int, int]] = None, negative_original_size: Optional[Tuple[int, int]] = None,
+                 negative_crops_coords_top_left: Tuple[int, int] = (0, 0), negative_target_size: Optional[Tuple[int, int]] = None,
+                 aesthetic_score: float = 6.0, negative_aesthetic_score: float = 2.5, clip_skip=None,
+                 callback_on_step_end=None, callback_on_step_end_tensor_inputs=None, use_graph: bool = True):
+        _check_strength(strength)
+        if image is None and latents is None:
+            raise ValueError("`image` input cannot be undefined.")
+        if eta != 0.0:
+            raise NotImplementedError("eta applies to DDIM; the SDXL img2img engine pipeline runs the Euler scheduler")
+        if (denoising_end is not None and denoising_start is not None and _denoising_value_valid(denoising_end)
+                and _denoising_value_valid(denoising_start) and denoising_start >= denoising_end):
+            raise ValueError(f"`denoising_start`: {denoising_start} cannot be larger than or equal to `denoising_end`: "
+                             f"{denoising_end} when using type float.")
+        if timesteps is not None and sigmas is not None:
+            raise ValueError("Only one of `timesteps` or `sigmas` can be passed. Please choose one to set custom values")
+        do_cfg = guidance_scale > 1.0
+        self._guidance_rescale = float(guidance_rescale)
+        self._arm_callback(callback_on_step_end, callback_on_step_end_tensor_inputs)
+        if prompt is not None:
+            if prompt_embeds is not None:
+                raise ValueError("Cannot forward both `prompt` and `prompt_embeds`. Please make sure to only forward one "
+                                 "of the two.")
+            prompt_embeds, negative_prompt_embeds, pooled_prompt_embeds, negative_pooled_prompt_embeds = \
+                self.encode_prompt(prompt, prompt_2, self.device, num_images_per_prompt, do_cfg, negative_prompt,
+                                   negative_prompt_2, clip_skip)
+        else:
+            prompt_embeds, negative_prompt_embeds, pooled_prompt_embeds, negative_pooled_prompt_embeds = (
+                _per_prompt(t, num_images_per_prompt) for t in (prompt_embeds, negative_prompt_embeds, pooled_prompt_embeds,
+                                                                negative_pooled_prompt_embeds))
+        if prompt_embeds is None or pooled_prompt_embeds is None:
+            raise ValueError("Provide either `prompt` (with the text encoders given to the pipeline) or `prompt_embeds` "
+                             "and `pooled_prompt_embeds`.")
+        if do_cfg and (negative_prompt_embeds is None or negative_pooled_prompt_embeds is None):
+            raise ValueError("classifier-free guidance needs `negative_prompt_embeds` and "
+                             "`negative_pooled_prompt_embeds`")
+        dev = self.device
+        B = prompt_embeds.shape[0]
+        if timesteps is not None:
+            self.scheduler.set_timesteps(timesteps=timesteps, device=dev)
+        elif sigmas is not None:
+            self.scheduler.set_timesteps(sigmas=sigmas, device=dev)
+        else:
+            self.scheduler.set_timesteps(num_inference_steps, device=dev)
+        num_inference_steps = len(self.scheduler.timesteps)
+        ts, n_steps, begin = get_timesteps(self.scheduler, num_inference_steps, strength,
+                                           denoising_start if _denoising_value_valid(denoising_start) else None)
+        _no_steps(strength, n_steps)
+        latent_timestep = ts[:1].repeat(B)
+        add_noise = not _denoising_value_valid(denoising_start)
+        if latents is None:
+            # the reference's upcast path (force_upcast): the posterior noise is drawn in fp32
+            latents = self._img2img_latents(image, latent_timestep, B, generator, add_noise,
+                                            torch.float32 if self.vae.config.force_upcast else bf16)
+        else:
+            latents = latents.to(device=dev, dtype=bf16).clone()
+        if latents.shape[0] != B:
+            raise ValueError(f"`latents` holds {latents.shape[0]} samples, the prompt embeddings (x num_images_per_prompt) {B}")
+        if _denoising_value_valid(denoising_end):
+            cutoff = int(round(self.scheduler.config.num_train_timesteps - denoising_end * self.scheduler.config.num_train_timesteps))
+            n_steps = len([t for t in ts.tolist() if t >= cutoff])
+        height, width = latents.shape[-2] * self.vae_scale_factor, latents.shape[-1] * self.vae_scale_factor
+        original_size = original_size or (height, width)
+        target_size = target_size or (height, width)
+        negative_original_size = negative_original_size or original_size
+        negative_target_size = negative_target_size or target_size
+        pe = prompt_embeds.to(device=dev, dtype=bf16)
+        te = pooled_prompt_embeds.to(device=dev, dtype=bf16)
+        ids, neg_ids = self._get_add_time_ids(original_size, tuple(crops_coords_top_left), target_size, aesthetic_score,
+                                              negative_aesthetic_score, negative_original_size,
+                                              tuple(negative_crops_coords_top_left), negative_target_size,
+                                              text_encoder_projection_dim=int(te.shape[-1]))
+        ids = ids.to(dev).repeat(B, 1)
+        if do_cfg:
+            pe = torch.cat([negative_prompt_embeds.to(device=dev, dtype=bf16), pe], dim=0)
+            te = torch.cat([negative_pooled_prompt_embeds.to(device=dev, dtype=bf16), te], dim=0)
+            ids = torch.cat([neg_ids.to(dev).repeat(B, 1), ids], dim=0)
+        cond = self.unet.precompute_conditioning(pe.contiguous(), {"text_embeds": te, "time_ids": ids})
+        latents = self._denoise(latents, cond, n_steps, guidance_scale, do_cfg, use_graph, begin=begin)
+        images = self._decode(latents, output_type)
+        if not return_dict:
+            return (images,)
+        return PipelineOutput(images=images)
+
+
+class StableDiffusionImg2ImgPipeline(_Img2ImgMixin, StableDiffusionPipeline):
+    """pipeline_stable_diffusion_img2img.py (__call__ :860-1132): SD1.5 img2img on the engine (DDIM by default, eta included)."""
+
+    @torch.no_grad()
+    def __call__(self, prompt=None, image=None, strength: float = 0.8, num_inference_steps: int = 50, timesteps=None,
+                 sigmas=None, guidance_scale: float = 7.5, negative_prompt=None, num_images_per_prompt: int = 1,
+                 eta: float = 0.0, generator=None, prompt_embeds=None, negative_prompt_embeds=None, output_type: str = "pt",
+                 return_dict: bool = True, clip_skip=None, guidance_rescale: float = 0.0, callback_on_step_end=None,
+                 callback_on_step_end_tensor_inputs=None, use_graph: bool = True):
+        _check_strength(strength)
+        if image is None:
+            raise ValueError("`image` input cannot be undefined.")
+        if eta < 0.0 or eta > 1.0:
+            raise ValueError("eta (DDIM) must be in [0, 1]")
+        self._guidance_rescale = float(guidance_rescale)
+        self._arm_callback(callback_on_step_end, callback_on_step_end_tensor_inputs)
+        do_cfg = guidance_scale > 1.0
+        if prompt is not None:
+            if prompt_embeds is not None:
+                raise ValueError("Cannot forward both `prompt` and `prompt_embeds`. Please make sure to only forward one "
+                                 "of the two.")
+            prompt_embeds, negative_prompt_embeds = self.encode_prompt(prompt, self.device, num_images_per_prompt, do_cfg,
+                                                                        negative_prompt, clip_skip)
+        else:
+            prompt_embeds, negative_prompt_embeds = (_per_prompt(t, num_images_per_prompt) for t in (prompt_embeds, negative_prompt_embeds))
+        if prompt_embeds is None:
+            raise ValueError("Provide either `prompt` (with the text encoder given to the pipeline) or `prompt_embeds`.")
+        if do_cfg and negative_prompt_embeds is None:
+            raise ValueError("classifier-free guidance needs `negative_prompt_embeds`")
+        dev = self.device
+        B = prompt_embeds.shape[0]
+        if timesteps is not None or sigmas is not None:
+            if not isinstance(self.scheduler, EulerDiscreteScheduler):
+                raise ValueError(f"The current scheduler class {type(self.scheduler)}'s `set_timesteps` does not support custom "
+                                 "timestep or sigma schedules. Please check whether you are using the correct scheduler.")
+            self.scheduler.set_timesteps(timesteps=timesteps, sigmas=sigmas, device=dev)
+        else:
+            self.scheduler.set_timesteps(num_inference_steps, device=dev)
+        num_inference_steps = len(self.scheduler.timesteps)
+        ts, n_steps, begin = get_timesteps(self.scheduler, num_inference_steps, strength)
+        _no_steps(strength, n_steps)
+        latent_timestep = ts[:1].repeat(B)
+        # (no upcast in this pipeline: the posterior noise is drawn in the VAE's dtype)
+        latents = self._img2img_latents(image, latent_timestep, B, generator, True, bf16)
+        pe = prompt_embeds.to(device=dev, dtype=bf16)
+        if do_cfg:
+            pe = torch.cat([negative_prompt_embeds.to(device=dev, dtype=bf16), pe], dim=0)
+        cond = self.unet.precompute_conditioning(pe.contiguous(), None)
+        self._eta, self._noise_table = float(eta), None
+        if eta > 0:
+            if not hasattr(self.scheduler, "_get_variance"):
+                raise ValueError("eta > 0 is a DDIMScheduler option")
+            # one draw per step that runs, in order (scheduling_ddim.py:500-507), in the rows the device step counter selects
+            gdev = generator.device if generator is not None else dev
+            table = torch.zeros((num_inference_steps,) + tuple(latents.shape), device=dev, dtype=bf16)
+            for i in range(n_steps):
+                table[begin + i] = torch.randn(latents.shape, generator=generator, device=gdev, dtype=bf16).to(dev)
+            if self._static.get("noise_table") is not None and self._static["noise_table"].shape == table.shape:
+                self._static["noise_table"].copy_(table)
+                table = self._static["noise_table"]
+            self._static["noise_table"] = table
+            self._noise_table = table
+        latents = self._denoise(latents, cond, n_steps, guidance_scale, do_cfg, use_graph, begin=begin)
         images = self._decode(latents, output_type)
         if not return_dict:
             return (images,)

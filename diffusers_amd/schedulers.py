@@ -40,6 +40,14 @@ def _betas(beta_schedule, beta_start, beta_end, n, trained_betas=None):
     raise NotImplementedError(f"{beta_schedule} is not implemented")
 
 
+def _alpha_noise_coeffs(alphas_cumprod, timesteps, dtype):
+    """DDIM / DDPM add_noise (scheduling_ddim.py, scheduling_ddpm.py): sqrt(abar_t) and sqrt(1 - abar_t) of abar cast to the
+    latents' dtype, each op in that dtype."""
+    ac = alphas_cumprod.to(dtype=dtype)
+    t = torch.as_tensor(timesteps).reshape(-1).cpu().long()
+    return [float(v) for v in ac[t] ** 0.5], [float(v) for v in (1 - ac[t]) ** 0.5]
+
+
 class _SchedulerBase:
     order = 1
     _defaults: dict = {}
@@ -80,6 +88,29 @@ class _SchedulerBase:
 
     def set_begin_index(self, begin_index: int = 0):
         self._begin_index = begin_index
+        if self._step_dev is not None and self._step_index is None:
+            # the captured step reads the DEVICE counter: the first step of an img2img loop is row `begin_index` of the table
+            self._step_dev.fill_(int(begin_index))
+
+    def _add_noise_coeffs(self, timesteps, dtype):
+        """(a, b) per sample of ``add_noise`` = a x + b n, each rounded to ``dtype`` as the reference's tensors are."""
+        raise NotImplementedError(f"{type(self).__name__}.add_noise is not implemented")
+
+    def add_noise(self, original_samples: torch.Tensor, noise: torch.Tensor, timesteps) -> torch.Tensor:
+        """The reference's ``add_noise`` on bf16 latents, every torch op's bf16 rounding kept (ops.add_noise: one kernel per
+        distinct coefficient pair).  The coefficients are computed on the host in the latents' dtype, as the reference does."""
+        if original_samples.dtype != torch.bfloat16:
+            raise ValueError(f"{type(self).__name__}.add_noise: bf16 latents expected, got {original_samples.dtype}")
+        a, b = self._add_noise_coeffs(timesteps, original_samples.dtype)
+        B = original_samples.shape[0]
+        if len(a) == 1:
+            a, b = a * B, b * B
+        if len(a) != B:
+            raise ValueError(f"add_noise: {len(a)} timesteps for a batch of {B}")
+        if len(set(zip(a, b))) == 1:
+            return ops.add_noise(original_samples, noise, a[0], b[0])
+        return torch.cat([ops.add_noise(original_samples[i:i + 1], noise[i:i + 1], a[i], b[i]) for i in range(B)], 0)
+
 
     def index_for_timestep(self, timestep, schedule_timesteps=None):
         ts = self._timesteps_host if schedule_timesteps is None else np.asarray(schedule_timesteps.cpu())
@@ -274,6 +305,19 @@ class EulerDiscreteScheduler(_SchedulerBase):
             rows[i, 7] = float(ts[i])
         self._upload(rows, device)
 
+    def _add_noise_coeffs(self, timesteps, dtype):
+        """scheduling_euler_discrete.py add_noise: x + n sigma, sigma of the step at ``begin_index`` (img2img: before the first
+        step), at ``step_index`` (after it), or of each timestep's index when no begin index is set; sigmas cast to ``dtype``."""
+        sig = self.sigmas.to(dtype=dtype)
+        ts = torch.as_tensor(timesteps).reshape(-1).cpu()
+        if self.begin_index is None:
+            idx = [self.index_for_timestep(t) for t in ts]
+        elif self.step_index is not None:
+            idx = [self.step_index] * ts.shape[0]
+        else:
+            idx = [self.begin_index] * ts.shape[0]
+        return [1.0] * len(idx), [float(sig[i]) for i in idx]
+
     def scale_model_input(self, sample, timestep=None, rep: int = 1):
         if self._step_index is None:
             self._init_step_index(timestep)
@@ -334,6 +378,9 @@ class DDIMScheduler(_SchedulerBase):
         self._timesteps_host = self.timesteps.numpy()
         self._eta = None
 
+    def _add_noise_coeffs(self, timesteps, dtype):
+        return _alpha_noise_coeffs(self.alphas_cumprod, timesteps, dtype)
+
     def _get_variance(self, timestep, prev_timestep):
         a_t = self.alphas_cumprod[timestep]
         a_prev = self.alphas_cumprod[prev_timestep] if prev_timestep >= 0 else self.final_alpha_cumprod
@@ -365,6 +412,7 @@ class DDIMScheduler(_SchedulerBase):
         self.timesteps = torch.from_numpy(ts).to(device)
         self._timesteps_host = ts
         self._step_index = None
+        self._begin_index = None
         self._device_req = device
         self._eta = None   # table rows are rebuilt lazily for the eta of the first step(); buffers are reused in place
 
@@ -392,13 +440,18 @@ class DDIMScheduler(_SchedulerBase):
         self._upload(rows, self._device_req)
         self._eta = eta
 
+    def _rebuild(self, eta):
+        """_build, keeping the step index: refreshing the table in place zeroes the device counter, which a loop that starts past
+        step 0 (img2img, scheduler.set_begin_index) must not lose."""
+        keep = self._step_index
+        self._build(eta)
+        self._step_index = keep
+        if keep is not None:
+            self._sync_device_step()
+
     def _ensure(self, eta, timestep):
         if self._table is None or self._eta != eta:
-            keep = self._step_index
-            self._build(eta)
-            self._step_index = keep
-            if keep is not None:
-                self._sync_device_step()
+            self._rebuild(eta)
         if self._step_index is None:
             self._init_step_index(timestep)
 
@@ -449,13 +502,13 @@ class DDIMScheduler(_SchedulerBase):
     @property
     def device_table(self):
         if self._table is None or self._eta is None:
-            self._build(0.0)
+            self._rebuild(0.0)
         return self._table
 
     @property
     def device_step(self):
         if self._table is None or self._eta is None:
-            self._build(0.0)
+            self._rebuild(0.0)
         return self._step_dev
 
 
@@ -487,6 +540,9 @@ class DDPMScheduler(_SchedulerBase):
         self._timesteps_host = self.timesteps.numpy()
         self.variance_type = c.variance_type
 
+    def _add_noise_coeffs(self, timesteps, dtype):
+        return _alpha_noise_coeffs(self.alphas_cumprod, timesteps, dtype)
+
     def set_timesteps(self, num_inference_steps: int = None, device=None, timesteps=None):
         c = self.config
         if timesteps is not None:
@@ -511,6 +567,7 @@ class DDPMScheduler(_SchedulerBase):
         self.timesteps = torch.from_numpy(ts).to(device)
         self._timesteps_host = ts
         self._step_index = None
+        self._begin_index = None
         rows = np.zeros((len(ts), 8), dtype=np.float32)
         for i, t in enumerate(ts):
             t = int(t)

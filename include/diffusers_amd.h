@@ -501,6 +501,46 @@ int da_conv_thin_out_bf16(const void* x, const void* w, const void* bias, void* 
                           int Cout, int out_f32, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------------
+ * The two ends of the VAE encoder (AutoencoderKL.encode, autoencoder_kl.py:146-185; Encoder.forward, vae.py:140-184) and
+ * the img2img latent preparation (pipeline_stable_diffusion_xl_img2img.py prepare_latents).
+ *
+ *   da_vae_conv_in_image   the caller's image -> encoder conv_in (3 -> Cout, 3x3, pad 1), output NHWC bf16 [B][H][W][Cout].
+ *                          src: DA_IMAGE_F32_NCHW / DA_IMAGE_F32_NHWC / DA_IMAGE_U8_NHWC (3 channels).  Every input value is
+ *                          converted as VaeImageProcessor.preprocess (image_processor.py:581-715) + the pipeline's cast do it:
+ *                          uint8 -> x / 255 (correctly rounded fp32 division, pil_to_numpy :151-161), then 2 x - 1 in fp32
+ *                          when `normalize` (:213-220), then the bf16 round.  The convolution is the four-pixel kernel of
+ *                          da_conv_thin_in_bf16: the result equals that entry point run on the converted bf16 image.
+ *   da_vae_posterior_latents  the encoder's conv_out result -> latents, one pass (NCHW bf16 out, fp32 arithmetic, every
+ *                          bf16 round where the reference's bf16 torch op rounds):
+ *                            p[o]    = bf16(bq[o] + sum_k wq[o][k] * x[k])   quant_conv 1x1, k ascending (fp32 fma; products of
+ *                                                                           bf16 values are exact); wq == bq == NULL: p = x
+ *                            mean    = p[c], logvar = clamp(p[L + c], -30, 20)                        (vae.py:689-694)
+ *                            SAMPLE: std = bf16(expf(bf16(0.5 logvar)));  z = bf16(mean + bf16(std * eps1))
+ *                            MEAN:   z = mean
+ *                            flags & DA_LATENTS_SHIFT: z = bf16(z - shift);  flags & DA_LATENTS_SCALE: z = bf16(z * scale)
+ *                            eps2 != NULL (scheduler.add_noise): z = bf16(bf16(a * z) + bf16(b * eps2))
+ *                          MOMENTS writes p itself ([B][2L][HW], the DiagonalGaussianDistribution's `parameters`).
+ *                          NOISE (add_noise alone): z = x[c] (the input is latents, L channels), then the add_noise step.
+ *                          Input element (b, channel c, pixel p) at in[b * sB + c * sC + p * sP]: NCHW (sC = HW, sP = 1) or the
+ *                          NHWC channel-padded output of the implicit-GEMM conv_out (sC = 1, sP = 16).  eps1 / eps2: NCHW bf16
+ *                          [B][L][HW].  L = 4 (the SD / SDXL VAE).
+ * ------------------------------------------------------------------------------------------------------------------ */
+#define DA_IMAGE_F32_NCHW 0
+#define DA_IMAGE_F32_NHWC 1
+#define DA_IMAGE_U8_NHWC 2
+#define DA_POSTERIOR_MOMENTS 0
+#define DA_POSTERIOR_MEAN 1
+#define DA_POSTERIOR_SAMPLE 2
+#define DA_POSTERIOR_NOISE 3
+#define DA_LATENTS_SHIFT 1
+#define DA_LATENTS_SCALE 2
+int da_vae_conv_in_image(const void* x, int src, const void* w, const void* bias, void* y, int B, int H, int W, int Cout,
+                         int normalize, void* stream);
+int da_vae_posterior_latents(const void* in, long long sB, long long sC, long long sP, const void* wq, const void* bq,
+                             const void* eps1, const void* eps2, void* out, int B, long long HW, int L, int mode, int flags,
+                             float shift, float scale, float a, float b, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------------
  * Launch plans: a recorded sequence of the launch entry points above, owned by the library and replayed by ONE call --
  * the C-ABI form of the denoising step the Python pipelines capture into a HIP graph (the reference's per-step work,
  * pipeline_stable_diffusion_xl.py:1186-1250: scale_model_input, the U-Net forward, the CFG combine, scheduler.step; and the
