@@ -11,7 +11,9 @@ data path; rank 0 broadcasts the text embeddings once before the timed region). 
 launcher re-executes itself under ``torch.distributed.run`` with N ranks (the reference's own recipe spawns its ranks the
 same way, docs/source/en/training/distributed_inference.md:62-108).  Rank 0 prints ONE JSON line.
 
-Besides the contract keys the line carries, all measured OUTSIDE the timed region on rank 0 at N = 1:
+A plain run does only what the headline needs: set-up, warm-up, the timed steps, --dump-outputs and the line.  With --full the
+line also carries `config.box_*` (the box normalisers, measured before the warm-up) and, all measured OUTSIDE the timed region on
+rank 0 at N = 1 (each --no-* flag drops one of them):
   roofline            dominant kernel family (igemm_bf16_kernel + igemm2_bf16_kernel + gemm3_bf16_kernel) over the launches of one eager denoising step,
                       timed with HIP events ATTACHED to every launch (da_set_launch_events: the dispatch's own begin / end, the
                       duration rocprofv3 reports; `timing` says which method ran, `host_event_pairs` carries the host-recorded
@@ -61,13 +63,17 @@ def parse(argv=None):
     ap.add_argument("--denoise-steps", type=int, default=None, help="sampler steps per unit (default: the config's own: 50, flux 4)")
     ap.add_argument("--tiny", action="store_true", help="tiny config (plumbing check only; not a valid bench number)")
     ap.add_argument("--no-graph", action="store_true")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every side leg: box normalisers, roofline, parity / torch_rocm_baseline / dropin, cpu_baseline, "
+                         "serving_two_in_flight and other_configs (--config runs: per-family kernels, cpu_baseline, Wan's decode split)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the cpu_baseline leg")
+    ap.add_argument("--no-roofline", action="store_true", help="--full without the roofline leg")
     ap.add_argument("--no-live-traffic", action="store_true",
                     help="roofline.traffic: do not run the two rocprofv3 --pmc passes (FETCH_SIZE, WRITE_SIZE) in subprocesses; replay "
                          "profiles/sdxl_traffic.json instead (what a multi-rank run and a box without rocprofv3 do anyway)")
-    ap.add_argument("--no-reference", action="store_true", help="skip the parity / torch_rocm_baseline / dropin legs")
-    ap.add_argument("--no-other-configs", action="store_true", help="skip the other_configs leg (sd15, flux, ddpm, wan) of the default run")
+    ap.add_argument("--no-reference", action="store_true", help="--full without the parity / torch_rocm_baseline / dropin legs")
+    ap.add_argument("--no-other-configs", action="store_true",
+                    help="--full without the serving_two_in_flight and other_configs (sd15, flux, ddpm, wan) legs")
     ap.add_argument("--save-tuning", default=None, help="write the GEMM variant table measured during warm-up here")
     ap.add_argument("--dump-outputs", default=None, metavar="DIR",
                     help="after the timed region, write rank 0's output of the last timed step as DIR/<name>.npy (float32, at most 64 MB "
@@ -821,8 +827,9 @@ def _other_cpu_baseline(config, unit_tflop, n_steps):
 def measure_other_config(config, dev, rank, world, args, units, warmup, n_steps=None, extrapolate_from=None, legs=True, dump=None):
     """One BASELINE config other than the headline under the driver contract's timing rule: `warmup` untimed units, `units` timed
     units between synchronisations (+ barriers when world > 1), max over ranks.  ``extrapolate_from`` = k: a unit is timed with k
-    sampler steps and scaled to the config's step count (flagged) -- the 50-step Wan video inside the default run.
-    ``legs``: per-family `roofline.kernels` and the `cpu_baseline` (rank 0, world == 1).  ``dump``: --dump-outputs directory."""
+    sampler steps and scaled to the config's step count (flagged) -- the 50-step Wan video inside a --full run.
+    ``legs``: per-family `roofline.kernels` and the `cpu_baseline` (rank 0, world == 1) and Wan's decode split.  ``dump``:
+    --dump-outputs directory."""
     from diffusers_amd import distributed as D
     metric, unit_name, what, default_steps, tflop_of = OTHER_CONFIGS[config]
     n = n_steps or default_steps
@@ -848,7 +855,7 @@ def measure_other_config(config, dev, rank, world, args, units, warmup, n_steps=
     dumped = dump_outputs(dump, {"images": out}) if dump and rank == 0 else None
     scale = n / run_steps if extrapolate_from else 1.0
     side = {}
-    if config == "wan":
+    if config == "wan" and (legs or extrapolate_from):
         # the unit holds a decode that does not scale with the step count: time the latents-only unit next to it (outside the
         # contract's timed region) -- decode = full - latents-only; an extrapolated unit scales only the sampler part
         lat_fn = unit(run_steps, output_type="latent")
@@ -896,7 +903,7 @@ def measure_other_config(config, dev, rank, world, args, units, warmup, n_steps=
                                        "sample": f"not measured: {type(e).__name__}: {e}"}
     if "cpu_baseline" not in res:
         res["cpu_baseline"] = {"value": None, "unit": unit_name, "cores": None, "kind": "reference",
-                               "sample": "not measured in this run (rank 0 at N = 1 without --no-cpu-baseline measures it)"}
+                               "sample": "not measured in this run (rank 0 at N = 1 with --full measures it)"}
     del pipe
     torch.cuda.empty_cache()
     return res
@@ -905,14 +912,14 @@ def measure_other_config(config, dev, rank, world, args, units, warmup, n_steps=
 def run_other_config(args, argv):
     """`--config sd15 | flux | wan | ddpm`: the same contract (W untimed units, K timed units between barriers, max over ranks, ONE
     JSON line from rank 0) on the other BASELINE configs; one prompt per rank, no collective in the data path.  `roofline` is the
-    whole unit against the MFMA peak (algorithmic TFLOP of SURVEY.md 8d / wall time) with per-family `kernels` from one eager
-    step; `cpu_baseline` is the reference classes on a bounded sample of the same workload."""
+    whole unit against the MFMA peak (algorithmic TFLOP of SURVEY.md 8d / wall time); with --full it also carries per-family
+    `kernels` from one eager step and `cpu_baseline` = the reference classes on a bounded sample of the same workload."""
     from diffusers_amd import distributed as D
     rank, world, local = D.init_from_env()
     dev = _device(local)
     log(f"rank {rank}/{world}: {args.config} on {dev}")
     result = measure_other_config(args.config, dev, rank, world, args, args.steps, args.warmup, n_steps=args.denoise_steps,
-                                  dump=args.dump_outputs)
+                                  legs=args.full, dump=args.dump_outputs)
     if rank == 0:
         print(json.dumps(result), flush=True)
     if _pg():
@@ -922,7 +929,7 @@ def run_other_config(args, argv):
 
 
 def other_configs_leg(dev, args):
-    """The other four BASELINE configs inside the default run (rank 0, N = 1, outside the timed region): three timed units each
+    """The other four BASELINE configs inside a --full run (rank 0, N = 1, outside the timed region): three timed units each
     (Wan: two units of 3 sampler steps, scaled to 50 and flagged), each with its per-family kernels and its CPU baseline."""
     out = []
     for cfg, units, extra in (("sd15", 3, {}), ("flux", 3, {}), ("ddpm", 3, {}), ("wan", 2, {"extrapolate_from": 3})):
@@ -1088,7 +1095,7 @@ def main(argv=None):
                     height=hw, width=hw, output_type=output_type, use_graph=state["graph"]).images
 
     box = None
-    if not args.tiny and dev.type == "cuda":
+    if args.full and not args.tiny and dev.type == "cuda":
         try:
             box = box_mfma_probe()
             log(f"box normaliser: {box['tflops']:.0f} TFLOP/s on the register-only MFMA loop ({box['ms']:.1f} ms)")
@@ -1182,7 +1189,7 @@ def main(argv=None):
     if dumped:
         result["dumped_outputs"] = dumped
 
-    if rank == 0 and not args.tiny:
+    if args.full and rank == 0 and not args.tiny:
         if not args.no_roofline:
             log("roofline leg: one eager denoising step with HIP events around every igemm launch")
             try:

@@ -33,7 +33,7 @@ PYEOF
   export DIFFUSERS_AMD_TUNE_DB=$O/tuned_merged_r2.json
 fi
 if [[ $WHAT == *bench* ]]; then
-  timeout 900 python bench.py --steps 3 --warmup 1 > $O/bench.json 2> $O/bench.err; echo "bench rc=$?"
+  timeout 900 python bench.py --full --steps 3 --warmup 1 > $O/bench.json 2> $O/bench.err; echo "bench rc=$?"
   cat $O/bench.json; grep "^\[bench" $O/bench.err | tail -20
 fi
 if [[ $WHAT == *prof* ]]; then

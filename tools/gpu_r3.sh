@@ -27,7 +27,7 @@ fi
 if [[ $WHAT == *bench* ]]; then
   EXTRA=""
   [[ $WHAT == *benchfast* ]] && EXTRA="--no-reference --no-cpu-baseline"
-  timeout 1200 python bench.py --steps 3 --warmup 1 $EXTRA > $O/bench.json 2> $O/bench.err; echo "bench rc=$?"
+  timeout 1200 python bench.py --full --steps 3 --warmup 1 $EXTRA > $O/bench.json 2> $O/bench.err; echo "bench rc=$?"
   cut -c1-1500 $O/bench.json; grep "^\[bench" $O/bench.err | tail -20
 fi
 if [[ $WHAT == *test* ]]; then
@@ -60,7 +60,7 @@ if [[ $WHAT == *others* ]]; then
   # the other BASELINE configs under the driver contract; unseen GEMM / conv shapes are tuned live (both kernel families) and saved
   for cfg in sd15 flux ddpm wan; do
     ST=2; [[ $cfg == wan ]] && ST=1
-    DIFFUSERS_AMD_TUNE_SAVE=$O/tuned_$cfg.json timeout 1200 python bench.py --config $cfg --steps $ST --warmup 1 > $O/bench_$cfg.json 2> $O/bench_$cfg.err; echo "$cfg rc=$?"
+    DIFFUSERS_AMD_TUNE_SAVE=$O/tuned_$cfg.json timeout 1200 python bench.py --full --config $cfg --steps $ST --warmup 1 > $O/bench_$cfg.json 2> $O/bench_$cfg.err; echo "$cfg rc=$?"
     cut -c1-700 $O/bench_$cfg.json; tail -2 $O/bench_$cfg.err
   done
 fi
@@ -96,7 +96,7 @@ shutil.copy("$R/diffusers_amd/tuned/gfx950.json", "$O/tuned_all.json")
 PYEOF
   for cfg in sd15 flux ddpm wan; do
     rm -f $O/tuned_$cfg.json
-    DIFFUSERS_AMD_TUNE_DB=$O/none.json DIFFUSERS_AMD_TUNE_SAVE=$O/tuned_$cfg.json timeout 1500 python bench.py --config $cfg --steps 1 --warmup 1 > $O/retune_$cfg.json 2> $O/retune_$cfg.err; echo "retune $cfg rc=$?"
+    DIFFUSERS_AMD_TUNE_DB=$O/none.json DIFFUSERS_AMD_TUNE_SAVE=$O/tuned_$cfg.json timeout 1500 python bench.py --full --config $cfg --steps 1 --warmup 1 > $O/retune_$cfg.json 2> $O/retune_$cfg.err; echo "retune $cfg rc=$?"
     python - <<PYEOF
 import json
 a = json.load(open("$O/tuned_all.json"))
@@ -108,7 +108,7 @@ PYEOF
   done
   for cfg in sd15 flux ddpm wan; do
     ST=2; [[ $cfg == wan ]] && ST=1
-    DIFFUSERS_AMD_TUNE_DB=$O/tuned_all.json timeout 1200 python bench.py --config $cfg --steps $ST --warmup 1 > $O/bench_$cfg.json 2> $O/bench_$cfg.err; echo "$cfg rc=$?"
+    DIFFUSERS_AMD_TUNE_DB=$O/tuned_all.json timeout 1200 python bench.py --full --config $cfg --steps $ST --warmup 1 > $O/bench_$cfg.json 2> $O/bench_$cfg.err; echo "$cfg rc=$?"
     cut -c1-330 $O/bench_$cfg.json
   done
 fi

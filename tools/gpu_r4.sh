@@ -16,13 +16,13 @@ if [[ $WHAT == *attnbench* ]]; then
   tail -3 $O/attn_r4.log | cut -c1-300
 fi
 if [[ $WHAT == *benchfast* ]]; then
-  timeout 900 python bench.py --steps 3 --warmup 1 --no-reference --no-cpu-baseline > $O/bench.json 2> $O/bench.err; echo "bench rc=$?"
+  timeout 900 python bench.py --full --steps 3 --warmup 1 --no-reference --no-cpu-baseline > $O/bench.json 2> $O/bench.err; echo "bench rc=$?"
   cut -c1-1200 $O/bench.json; grep "^\[bench" $O/bench.err | tail -20
 fi
 if [[ $WHAT == *others* ]]; then
   for cfg in flux wan sd15; do
     ST=2; [[ $cfg == wan ]] && ST=1
-    timeout 900 python bench.py --config $cfg --steps $ST --warmup 1 > $O/bench_$cfg.json 2> $O/bench_$cfg.err; echo "$cfg rc=$?"
+    timeout 900 python bench.py --full --config $cfg --steps $ST --warmup 1 > $O/bench_$cfg.json 2> $O/bench_$cfg.err; echo "$cfg rc=$?"
     cut -c1-400 $O/bench_$cfg.json; tail -2 $O/bench_$cfg.err | cut -c1-300
   done
 fi
@@ -66,7 +66,7 @@ if [[ $WHAT == *traffic* ]]; then
   tail -4 $O/pmc_traffic/fetch.log | cut -c1-200
 fi
 if [[ $WHAT == *benchfull* ]]; then
-  timeout 1500 python bench.py --steps 3 --warmup 1 > $O/bench_full.json 2> $O/bench_full.err; echo "bench full rc=$?"
+  timeout 1500 python bench.py --full --steps 3 --warmup 1 > $O/bench_full.json 2> $O/bench_full.err; echo "bench full rc=$?"
   cut -c1-300 $O/bench_full.json; grep "^\[bench" $O/bench_full.err | tail -40
 fi
 if [[ $WHAT == *plantest* ]]; then
@@ -95,7 +95,7 @@ if [[ $WHAT == *tunemissing* ]]; then
   rm -f $O/tuned_new_r4.json
   DIFFUSERS_AMD_GEMM_FAMILY=all DIFFUSERS_AMD_TUNE_SAVE=$O/tuned_new_r4.json timeout 700 python bench.py --steps 1 --warmup 1 --no-cpu-baseline --no-roofline --no-reference --no-other-configs > $O/tunemissing.json 2> $O/tunemissing.err; echo "tunemissing rc=$?"
   for cfg in sd15 flux; do
-    DIFFUSERS_AMD_GEMM_FAMILY=all DIFFUSERS_AMD_TUNE_DB=$O/tuned_new_r4.json DIFFUSERS_AMD_TUNE_SAVE=$O/tuned_new_r4.json timeout 700 python bench.py --config $cfg --steps 1 --warmup 1 --no-cpu-baseline > $O/tunemissing_$cfg.json 2>> $O/tunemissing.err; echo "tunemissing $cfg rc=$?"
+    DIFFUSERS_AMD_GEMM_FAMILY=all DIFFUSERS_AMD_TUNE_DB=$O/tuned_new_r4.json DIFFUSERS_AMD_TUNE_SAVE=$O/tuned_new_r4.json timeout 700 python bench.py --full --config $cfg --steps 1 --warmup 1 --no-cpu-baseline > $O/tunemissing_$cfg.json 2>> $O/tunemissing.err; echo "tunemissing $cfg rc=$?"
   done
   python - <<PYEOF
 import json
@@ -190,7 +190,7 @@ if [[ $WHAT == *tuneothers* ]]; then
   # shapes of the other BASELINE configs that the shipped table does not hold (bench.py reports them as config.tuned_live)
   rm -f $O/tuned_others_r4.json
   for cfg in sd15 flux ddpm; do
-    DIFFUSERS_AMD_GEMM_FAMILY=all DIFFUSERS_AMD_TUNE_SAVE=$O/tuned_others_r4.json timeout 600 python bench.py --config $cfg --steps 1 --warmup 1 --no-cpu-baseline > $O/tuneothers_$cfg.json 2>> $O/tuneothers.err; echo "tuneothers $cfg rc=$? $(grep -o '"tuned_live": [0-9]*' $O/tuneothers_$cfg.json)"
+    DIFFUSERS_AMD_GEMM_FAMILY=all DIFFUSERS_AMD_TUNE_SAVE=$O/tuned_others_r4.json timeout 600 python bench.py --full --config $cfg --steps 1 --warmup 1 --no-cpu-baseline > $O/tuneothers_$cfg.json 2>> $O/tuneothers.err; echo "tuneothers $cfg rc=$? $(grep -o '"tuned_live": [0-9]*' $O/tuneothers_$cfg.json)"
     python - <<PYEOF
 import json
 a = json.load(open("$R/diffusers_amd/tuned/gfx950.json"))
@@ -210,7 +210,7 @@ if [[ $WHAT == *profothers* ]]; then
   cd /tmp && export TMPDIR=/tmp
   for cfg in sd15 ddpm; do
     rm -rf $O/prof_$cfg
-    timeout 600 rocprofv3 --kernel-trace --stats -f csv -d $O/prof_$cfg -o $cfg -- python $R/bench.py --config $cfg --steps 1 --warmup 1 --no-cpu-baseline > $O/prof_$cfg.log 2>&1; echo "prof $cfg rc=$?"
+    timeout 600 rocprofv3 --kernel-trace --stats -f csv -d $O/prof_$cfg -o $cfg -- python $R/bench.py --full --config $cfg --steps 1 --warmup 1 --no-cpu-baseline > $O/prof_$cfg.log 2>&1; echo "prof $cfg rc=$?"
     find $O/prof_$cfg -name '*kernel_trace*' -size +30M -delete
     python $R/tools/prof_summary.py $(find $O/prof_$cfg -name '*kernel_stats.csv' | head -1) "r04 $cfg bench (--steps 1 --warmup 1)" > $O/prof_summary_$cfg.md 2>> $O/prof_$cfg.log; head -34 $O/prof_summary_$cfg.md | cut -c1-190
   done
@@ -251,7 +251,7 @@ print("entries to tune again:", len(drop))
 PYEOF
   cp $O/table_pruned.json $O/table_retuned.json
   for cfg in sd15 ddpm; do
-    DIFFUSERS_AMD_SPLITK=1 DIFFUSERS_AMD_GEMM_FAMILY=all DIFFUSERS_AMD_TUNE_DB=$O/table_retuned.json DIFFUSERS_AMD_TUNE_SAVE=$O/table_retuned.json timeout 900 python bench.py --config $cfg --steps 1 --warmup 1 --no-cpu-baseline > $O/retune_$cfg.json 2> $O/retune_$cfg.err; echo "retune $cfg rc=$? $(grep -o '"value": [0-9.]*' $O/retune_$cfg.json | head -1) $(grep -o '"tuned_live": [0-9]*' $O/retune_$cfg.json)"
+    DIFFUSERS_AMD_SPLITK=1 DIFFUSERS_AMD_GEMM_FAMILY=all DIFFUSERS_AMD_TUNE_DB=$O/table_retuned.json DIFFUSERS_AMD_TUNE_SAVE=$O/table_retuned.json timeout 900 python bench.py --full --config $cfg --steps 1 --warmup 1 --no-cpu-baseline > $O/retune_$cfg.json 2> $O/retune_$cfg.err; echo "retune $cfg rc=$? $(grep -o '"value": [0-9.]*' $O/retune_$cfg.json | head -1) $(grep -o '"tuned_live": [0-9]*' $O/retune_$cfg.json)"
   done
   python - <<PYEOF
 import json

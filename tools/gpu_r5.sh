@@ -21,11 +21,11 @@ if [[ $WHAT == *dropin* ]]; then
   grep -E "passed|failed|FAILED|Error|\[parity\]" $O/pytest_wanvae.log | tail -30
 fi
 if [[ $WHAT == *benchfast* ]]; then
-  timeout 900 python bench.py --steps 3 --warmup 1 --no-reference --no-cpu-baseline --no-other-configs > $O/bench.json 2> $O/bench.err; echo "bench rc=$?"
+  timeout 900 python bench.py --full --steps 3 --warmup 1 --no-reference --no-cpu-baseline --no-other-configs > $O/bench.json 2> $O/bench.err; echo "bench rc=$?"
   cut -c1-1400 $O/bench.json; grep "^\[bench" $O/bench.err | tail -20
 fi
 if [[ $WHAT == *wanbench* ]]; then
-  timeout 900 python bench.py --config wan --steps 1 --warmup 1 --denoise-steps ${WAN_STEPS:-6} --no-cpu-baseline > $O/bench_wan.json 2> $O/bench_wan.err; echo "wan rc=$?"
+  timeout 900 python bench.py --full --config wan --steps 1 --warmup 1 --denoise-steps ${WAN_STEPS:-6} --no-cpu-baseline > $O/bench_wan.json 2> $O/bench_wan.err; echo "wan rc=$?"
   cut -c1-1600 $O/bench_wan.json; tail -3 $O/bench_wan.err | cut -c1-300
 fi
 if [[ $WHAT == *fulltest* ]]; then
@@ -34,7 +34,7 @@ if [[ $WHAT == *fulltest* ]]; then
   grep -E "\[parity\] (SDXL|FLUX|Wan|SD1.5|full|Auto)|\[drop-in\]|\[B3\]|\[B4\]|\[rccl\]" $O/pytest_gpu.log | tail -60
 fi
 if [[ $WHAT == *benchfull* && $WHAT != *trafficfirst* ]]; then
-  timeout 1500 python bench.py --steps 3 --warmup 1 > $O/bench_full.json 2> $O/bench_full.err; echo "bench full rc=$?"
+  timeout 1500 python bench.py --full --steps 3 --warmup 1 > $O/bench_full.json 2> $O/bench_full.err; echo "bench full rc=$?"
   cut -c1-300 $O/bench_full.json; grep "^\[bench" $O/bench_full.err | tail -40
 fi
 if [[ $WHAT == *traffic* ]]; then
@@ -77,7 +77,7 @@ fi
 if [[ $WHAT == *gnab* ]]; then
   for m in 1 0 1 0; do
     DA_GN_FUSED=$m timeout 600 python bench.py --steps 3 --warmup 1 --no-reference --no-cpu-baseline --no-roofline --no-other-configs > $O/bench_gn$m.json 2> $O/bench_gn$m.err; echo "gn fused $m rc=$? $(cut -c1-140 $O/bench_gn$m.json | grep -o '"value": [0-9.]*')"
-    DA_GN_FUSED=$m timeout 600 python bench.py --config sd15 --steps 3 --warmup 1 --no-cpu-baseline > $O/bench_sd15_gn$m.json 2> $O/bench_sd15_gn$m.err; echo "sd15 gn fused $m rc=$? $(cut -c1-160 $O/bench_sd15_gn$m.json | grep -o '"value": [0-9.]*')"
+    DA_GN_FUSED=$m timeout 600 python bench.py --full --config sd15 --steps 3 --warmup 1 --no-cpu-baseline > $O/bench_sd15_gn$m.json 2> $O/bench_sd15_gn$m.err; echo "sd15 gn fused $m rc=$? $(cut -c1-160 $O/bench_sd15_gn$m.json | grep -o '"value": [0-9.]*')"
   done
 fi
 if [[ $WHAT == *splitk* ]]; then
@@ -137,8 +137,8 @@ if [[ $WHAT == *gemmtests* ]]; then
   grep -E "passed|failed|FAILED|Error|assert|differ" $O/pytest_gemm.log | tail -20
 fi
 if [[ $WHAT == *otherbench* ]]; then
-  timeout 600 python bench.py --config flux --steps 3 --warmup 1 --no-cpu-baseline > $O/bench_flux.json 2> $O/bench_flux.err; echo "flux rc=$? $(grep -o '"value": [0-9.]*' $O/bench_flux.json | head -1)"
-  timeout 600 python bench.py --config wan --steps 1 --warmup 1 --denoise-steps 6 --no-cpu-baseline > $O/bench_wan6.json 2> $O/bench_wan6.err; echo "wan rc=$? $(grep -o '"ms_per_step": [0-9.]*' $O/bench_wan6.json | head -1)"
+  timeout 600 python bench.py --full --config flux --steps 3 --warmup 1 --no-cpu-baseline > $O/bench_flux.json 2> $O/bench_flux.err; echo "flux rc=$? $(grep -o '"value": [0-9.]*' $O/bench_flux.json | head -1)"
+  timeout 600 python bench.py --full --config wan --steps 1 --warmup 1 --denoise-steps 6 --no-cpu-baseline > $O/bench_wan6.json 2> $O/bench_wan6.err; echo "wan rc=$? $(grep -o '"ms_per_step": [0-9.]*' $O/bench_wan6.json | head -1)"
 fi
 if [[ $WHAT == *k3prio* ]]; then
   rm -f $O/k3_prio.jsonl
@@ -161,11 +161,11 @@ if [[ $WHAT == *gegluab* ]]; then
   unset DIFFUSERS_AMD_TUNE_DB
 fi
 if [[ $WHAT == *trafficfirst* ]]; then   # (the stages above run in file order: this one runs the full bench AFTER the traffic stage)
-  timeout 1500 python bench.py --steps 3 --warmup 1 > $O/bench_full.json 2> $O/bench_full.err; echo "bench full rc=$?"
+  timeout 1500 python bench.py --full --steps 3 --warmup 1 > $O/bench_full.json 2> $O/bench_full.err; echo "bench full rc=$?"
   cut -c1-300 $O/bench_full.json; grep "^\[bench" $O/bench_full.err | tail -40
 fi
 if [[ $WHAT == *wanfull* ]]; then
-  timeout 900 python bench.py --config wan --steps 1 --warmup 1 --no-cpu-baseline > $O/bench_wan_full.json 2> $O/bench_wan_full.err; echo "wan full rc=$? $(grep -o '"value": [0-9.]*' $O/bench_wan_full.json | head -1) $(grep -o '"ms_per_step": [0-9.]*' $O/bench_wan_full.json | head -1)"
+  timeout 900 python bench.py --full --config wan --steps 1 --warmup 1 --no-cpu-baseline > $O/bench_wan_full.json 2> $O/bench_wan_full.err; echo "wan full rc=$? $(grep -o '"value": [0-9.]*' $O/bench_wan_full.json | head -1) $(grep -o '"ms_per_step": [0-9.]*' $O/bench_wan_full.json | head -1)"
 fi
 if [[ $WHAT == *forcedk3ab* ]]; then
   for tb in new old new old; do

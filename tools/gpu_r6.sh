@@ -144,7 +144,7 @@ if [[ $WHAT == *splitab* ]]; then
   done
 fi
 if [[ $WHAT == *benchfast* ]]; then
-  timeout 900 python bench.py --steps 3 --warmup 1 --no-reference --no-cpu-baseline --no-other-configs > $O/bench.json 2> $O/bench.err; echo "bench rc=$?"
+  timeout 900 python bench.py --full --steps 3 --warmup 1 --no-reference --no-cpu-baseline --no-other-configs > $O/bench.json 2> $O/bench.err; echo "bench rc=$?"
   cut -c1-1400 $O/bench.json; grep "^\[bench" $O/bench.err | tail -20
 fi
 if [[ $WHAT == *fulltest* ]]; then
@@ -153,7 +153,7 @@ if [[ $WHAT == *fulltest* ]]; then
   grep -E "\[parity\] (SDXL|FLUX|Wan|SD1.5|full|Auto|ddpm)|\[drop-in\]|\[B3\]|\[B4\]|\[rccl\]|\[split\]" $O/pytest_gpu.log | tail -70
 fi
 if [[ $WHAT == *benchfull* && $WHAT != *trafficfirst* ]]; then
-  timeout 1500 python bench.py --steps 3 --warmup 1 > $O/bench_full.json 2> $O/bench_full.err; echo "bench full rc=$?"
+  timeout 1500 python bench.py --full --steps 3 --warmup 1 > $O/bench_full.json 2> $O/bench_full.err; echo "bench full rc=$?"
   cut -c1-300 $O/bench_full.json; grep "^\[bench" $O/bench_full.err | tail -40
 fi
 if [[ $WHAT == *traffic* ]]; then
@@ -179,12 +179,12 @@ if [[ $WHAT == *prof* ]]; then
   python tools/prof_summary.py $(find $O/prof -name '*kernel_stats.csv' | head -1) "r06 sdxl bench (--steps 1 --warmup 1)" > $O/prof_summary.md 2>> $O/prof.log; head -60 $O/prof_summary.md
 fi
 if [[ $WHAT == *trafficfirst* && $WHAT == *benchfull* ]]; then
-  timeout 1500 python bench.py --steps 3 --warmup 1 > $O/bench_full.json 2> $O/bench_full.err; echo "bench full rc=$?"
+  timeout 1500 python bench.py --full --steps 3 --warmup 1 > $O/bench_full.json 2> $O/bench_full.err; echo "bench full rc=$?"
   cut -c1-300 $O/bench_full.json; grep "^\[bench" $O/bench_full.err | tail -40
 fi
 if [[ $WHAT == *otherbench* ]]; then
   for c in sd15 flux ddpm; do
-    timeout 900 python bench.py --config $c --steps 3 --warmup 1 --no-cpu-baseline > $O/bench_$c.json 2> $O/bench_$c.err; echo "$c rc=$? $(cut -c1-200 $O/bench_$c.json)"
+    timeout 900 python bench.py --full --config $c --steps 3 --warmup 1 --no-cpu-baseline > $O/bench_$c.json 2> $O/bench_$c.err; echo "$c rc=$? $(cut -c1-200 $O/bench_$c.json)"
   done
 fi
 if [[ $WHAT == *insitu* ]]; then
@@ -281,12 +281,12 @@ if [[ $WHAT == *r05ab* ]]; then
   # the round-5 library (git edaa4bd, built in the worktree _r05_ab/) against this round's, alternating, one box
   for m in r05 r06 r05 r06; do
     if [[ $m == r05 ]]; then D=$R/_r05_ab; else D=$R; fi
-    (cd $D && timeout 600 python bench.py --steps 3 --warmup 1 --no-reference --no-cpu-baseline --no-other-configs > $O/bench_ab_$m.json 2> $O/bench_ab_$m.err); echo "library $m rc=$? $(cut -c1-140 $O/bench_ab_$m.json | grep -o '"value": [0-9.]*') $(python -c "import json;d=json.load(open('$O/bench_ab_$m.json'));r=d['roofline'];print('igemm',round(r['frac'],3),'attention',round([k for k in r['kernels'] if k['name']=='attention'][0]['frac'],3), 'attn_ms', round([k for k in r['kernels'] if k['name']=='attention'][0]['ms'],3))" 2>/dev/null)"
+    (cd $D && timeout 600 python bench.py --full --steps 3 --warmup 1 --no-reference --no-cpu-baseline --no-other-configs > $O/bench_ab_$m.json 2> $O/bench_ab_$m.err); echo "library $m rc=$? $(cut -c1-140 $O/bench_ab_$m.json | grep -o '"value": [0-9.]*') $(python -c "import json;d=json.load(open('$O/bench_ab_$m.json'));r=d['roofline'];print('igemm',round(r['frac'],3),'attention',round([k for k in r['kernels'] if k['name']=='attention'][0]['frac'],3), 'attn_ms', round([k for k in r['kernels'] if k['name']=='attention'][0]['ms'],3))" 2>/dev/null)"
   done
   for c in sd15 flux; do
     for m in r05 r06; do
       if [[ $m == r05 ]]; then D=$R/_r05_ab; else D=$R; fi
-      (cd $D && timeout 600 python bench.py --config $c --steps 3 --warmup 1 --no-cpu-baseline > $O/bench_ab_${c}_$m.json 2> $O/bench_ab_${c}_$m.err); echo "$c library $m rc=$? $(cut -c1-160 $O/bench_ab_${c}_$m.json | grep -o '"value": [0-9.]*')"
+      (cd $D && timeout 600 python bench.py --full --config $c --steps 3 --warmup 1 --no-cpu-baseline > $O/bench_ab_${c}_$m.json 2> $O/bench_ab_${c}_$m.err); echo "$c library $m rc=$? $(cut -c1-160 $O/bench_ab_${c}_$m.json | grep -o '"value": [0-9.]*')"
     done
   done
 fi
@@ -339,10 +339,10 @@ if [[ $WHAT == *lnf3ab* ]]; then
   done
   done
   DIFFUSERS_AMD_LN_FOLD=1 DIFFUSERS_AMD_LN_FOLD_K3=0 timeout 600 python bench.py --steps 3 --warmup 1 --no-reference --no-cpu-baseline --no-roofline --no-other-configs > $O/bench_lnf1k1.json 2> $O/bench_lnf1k1.err; echo "LN_FOLD=1 on k1:128x320 rc=$? $(cut -c1-140 $O/bench_lnf1k1.json | grep -o '"value": [0-9.]*')"
-  DIFFUSERS_AMD_LN_FOLD=1 timeout 900 python bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-other-configs --no-live-traffic > $O/bench_lnf1_parity.json 2> $O/bench_lnf1_parity.err; echo "LN_FOLD=1 with parity rc=$?"; grep -E "parity:|dropin:|timed region done" $O/bench_lnf1_parity.err | cut -c1-200
+  DIFFUSERS_AMD_LN_FOLD=1 timeout 900 python bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-other-configs --no-live-traffic > $O/bench_lnf1_parity.json 2> $O/bench_lnf1_parity.err; echo "LN_FOLD=1 with parity rc=$?"; grep -E "parity:|dropin:|timed region done" $O/bench_lnf1_parity.err | cut -c1-200
   for c in sd15; do
     for m in 2 1; do
-      DIFFUSERS_AMD_LN_FOLD=$m timeout 900 python bench.py --config $c --steps 3 --warmup 1 --no-cpu-baseline > $O/bench_${c}_lnf$m.json 2> $O/bench_${c}_lnf$m.err; echo "$c LN_FOLD=$m rc=$? $(cut -c1-200 $O/bench_${c}_lnf$m.json | grep -o '"value": [0-9.]*')"
+      DIFFUSERS_AMD_LN_FOLD=$m timeout 900 python bench.py --full --config $c --steps 3 --warmup 1 --no-cpu-baseline > $O/bench_${c}_lnf$m.json 2> $O/bench_${c}_lnf$m.err; echo "$c LN_FOLD=$m rc=$? $(cut -c1-200 $O/bench_${c}_lnf$m.json | grep -o '"value": [0-9.]*')"
     done
   done
 fi

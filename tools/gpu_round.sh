@@ -55,7 +55,7 @@ a["entries"].update(b["entries"])
 json.dump(a, open("$O/tuned_merged.json", "w"), indent=0)
 print("retuned", len(b["entries"]), "shapes;", ch, "changed variant; table now", len(a["entries"]))
 PYEOF
-  DIFFUSERS_AMD_TUNE_DB=$O/tuned_merged.json timeout 400 python bench.py --steps 3 --warmup 1 > $O/bench.json 2> $O/bench.err; echo "bench rc=$?"
+  DIFFUSERS_AMD_TUNE_DB=$O/tuned_merged.json timeout 400 python bench.py --full --steps 3 --warmup 1 > $O/bench.json 2> $O/bench.err; echo "bench rc=$?"
   cat $O/bench.json
   cd /tmp && export TMPDIR=/tmp
   rm -rf $O/prof
@@ -85,7 +85,7 @@ if [[ $WHAT == *sd15* ]]; then
   tail -3 $O/sd15.log | cut -c1-300
 fi
 if [[ $WHAT == *bench* ]]; then
-  timeout 600 python bench.py --steps 3 --warmup 1 --save-tuning $O/tuned_gfx950.json > $O/bench.json 2> $O/bench.err; echo "bench rc=$?"
+  timeout 600 python bench.py --full --steps 3 --warmup 1 --save-tuning $O/tuned_gfx950.json > $O/bench.json 2> $O/bench.err; echo "bench rc=$?"
   cat $O/bench.json; grep "^\[bench" $O/bench.err | tail -12
 fi
 if [[ $WHAT == *prof* ]]; then
