@@ -26,6 +26,7 @@ _EXPORTS = {
     "DDPMScheduler": "schedulers",
     "FlowMatchEulerDiscreteScheduler": "schedulers",
     "UniPCMultistepScheduler": "schedulers",
+    "DPMSolverMultistepScheduler": "schedulers",
     "StableDiffusionPipeline": "pipelines",
     "StableDiffusionXLPipeline": "pipelines",
     "StableDiffusionImg2ImgPipeline": "pipelines",

@@ -248,6 +248,102 @@ __global__ void unipc_flow_step_kernel(const TV* __restrict__ v, TX* __restrict_
   }
 }
 
+// DPM-Solver++ (2M) step, orders 1 / 2 -- data-prediction multistep solver of Lu et al., "DPM-Solver++", Alg. 2; the
+// scheduler (schedulers.py DPMSolverMultistepScheduler) evaluates every scalar on the host in fp64 and stores fp32 rows:
+//   row = [alpha_s0, sigma_s0, cx, c0, cd, -, second_order_allowed, timestep]
+//   x0  = (x - sigma_s0 e) / alpha_s0 (epsilon) | alpha_s0 x - sigma_s0 e (v_prediction) | e (sample)
+//   x'  = cx x + c0 x0 [+ cd (x0 - m1)]        cx = sigma_t / sigma_s0, c0 = -alpha_t (exp(-h) - 1), cd = D1 coefficient / r0
+// The second-order term is added only when the row allows it AND this is not the first step of the loop (step != begin: img2img
+// and the refiner hand-off start past row 0 and replay the same graph), so stale history is never read.  fp32 arithmetic with
+// one rounding at the store of x; the history m1 <- x0 stays fp32 (D1 is a difference of two nearby tensors).  TX = dtype of the
+// sample, TV = dtype of the model output.
+struct DpmCoef {
+  float a0, b0, cx, c0, cd;
+  bool second;
+};
+
+template <int PRED>
+__device__ __forceinline__ float dpm_x0(const DpmCoef& k, float e, float xs) {
+  if (PRED == 0) return __fdiv_rn(__fsub_rn(xs, __fmul_rn(k.b0, e)), k.a0);
+  if (PRED == 1) return __fsub_rn(__fmul_rn(k.a0, xs), __fmul_rn(k.b0, e));
+  return e;
+}
+
+__device__ __forceinline__ float dpm_update(const DpmCoef& k, float xs, float x0, float m1o) {
+  float xn = __fadd_rn(__fmul_rn(k.cx, xs), __fmul_rn(k.c0, x0));
+  if (k.second) xn = __fadd_rn(xn, __fmul_rn(k.cd, __fsub_rn(x0, m1o)));
+  return xn;
+}
+
+template <typename T>
+struct Vec4;
+template <>
+struct Vec4<uint16_t> {
+  static __device__ __forceinline__ void ld(const uint16_t* p, size_t i, float (&v)[4]) {
+    const uint2 r = *reinterpret_cast<const uint2*>(p + i);
+    v[0] = __uint_as_float(r.x << 16), v[1] = __uint_as_float(r.x & 0xffff0000u);
+    v[2] = __uint_as_float(r.y << 16), v[3] = __uint_as_float(r.y & 0xffff0000u);
+  }
+  static __device__ __forceinline__ void st(uint16_t* p, size_t i, const float (&v)[4]) {
+    uint2 r;
+    r.x = (uint32_t)f2bf(v[0]) | ((uint32_t)f2bf(v[1]) << 16);
+    r.y = (uint32_t)f2bf(v[2]) | ((uint32_t)f2bf(v[3]) << 16);
+    *reinterpret_cast<uint2*>(p + i) = r;
+  }
+};
+template <>
+struct Vec4<float> {
+  static __device__ __forceinline__ void ld(const float* p, size_t i, float (&v)[4]) {
+    const float4 r = *reinterpret_cast<const float4*>(p + i);
+    v[0] = r.x, v[1] = r.y, v[2] = r.z, v[3] = r.w;
+  }
+  static __device__ __forceinline__ void st(float* p, size_t i, const float (&v)[4]) {
+    *reinterpret_cast<float4*>(p + i) = make_float4(v[0], v[1], v[2], v[3]);
+  }
+};
+
+// n_vec (a multiple of 4, 0 when a pointer is not 16-byte aligned or, with CFG, the cond half is not) elements go through
+// 4-wide loads / stores, the rest through the scalar tail; both run the same per-element arithmetic.
+template <typename TX, typename TV, bool CFG, int PRED>
+__global__ void dpmpp_2m_step_kernel(const TV* __restrict__ eps, TX* __restrict__ x, float* __restrict__ m1,
+                                     const float* __restrict__ table, const int* __restrict__ step_idx,
+                                     const int* __restrict__ begin_idx, float g, size_t n, size_t n_vec) {
+  const int step = *step_idx;
+  const float* row = table + (size_t)step * 8;
+  DpmCoef k;
+  k.a0 = row[0], k.b0 = row[1], k.cx = row[2], k.c0 = row[3], k.cd = row[4];
+  k.second = row[6] != 0.f && step != *begin_idx;
+  const size_t tid = (size_t)blockIdx.x * blockDim.x + threadIdx.x, nth = (size_t)gridDim.x * blockDim.x;
+  for (size_t i = tid * 4; i < n_vec; i += nth * 4) {
+    float e[4], xs[4], mo[4], x0[4], xn[4];
+    if (CFG) {
+      float u[4], c[4];
+      Vec4<TV>::ld(eps, i, u), Vec4<TV>::ld(eps, n + i, c);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) e[j] = cfg_combine<TV>(u[j], c[j], g);
+    } else {
+      Vec4<TV>::ld(eps, i, e);
+    }
+    Vec4<TX>::ld(x, i, xs);
+    if (k.second) Vec4<float>::ld(m1, i, mo);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      x0[j] = dpm_x0<PRED>(k, e[j], xs[j]);
+      xn[j] = dpm_update(k, xs[j], x0[j], k.second ? mo[j] : 0.f);
+    }
+    Vec4<float>::st(m1, i, x0);
+    Vec4<TX>::st(x, i, xn);
+  }
+  for (size_t i = n_vec + tid; i < n; i += nth) {
+    const float e = load_eps<TV, CFG>(eps, i, n, g);
+    const float xs = IO<TX>::ld(x, i);
+    const float x0 = dpm_x0<PRED>(k, e, xs);
+    const float xn = dpm_update(k, xs, x0, k.second ? m1[i] : 0.f);
+    m1[i] = x0;
+    IO<TX>::st(x, i, xn);
+  }
+}
+
 __global__ void advance_step_kernel(int* step_idx) { *step_idx += 1; }
 
 // out = x * s in the tensor dtype (latents * init_noise_sigma, pipeline_stable_diffusion.py:713)
@@ -413,6 +509,38 @@ extern "C" int da_unipc_flow_step(const void* v, void* x, void* last, void* m1, 
   else if (x_dtype == DA_DTYPE_BF16 && v_dtype == DA_DTYPE_BF16) { if (cfg) DA_UP(uint16_t, uint16_t, true); else DA_UP(uint16_t, uint16_t, false); }
   else return DA_ERR_UNSUPPORTED;
 #undef DA_UP
+  DA_CHECK_LAUNCH();
+  return DA_OK;
+}
+
+extern "C" int da_dpmpp_2m_step(const void* eps, void* x, float* m1, const float* table, const int* step_idx,
+                                const int* begin_idx, int cfg, float guidance, long long n_, int x_dtype, int e_dtype,
+                                int pred_type, void* stream) {
+  if (!eps || !x || !m1 || !table || !step_idx || !begin_idx || n_ <= 0) return DA_ERR_INVALID;
+  if (pred_type < 0 || pred_type > 2) return DA_ERR_INVALID;
+  if ((x_dtype != DA_DTYPE_BF16 && x_dtype != DA_DTYPE_F32) || (e_dtype != DA_DTYPE_BF16 && e_dtype != DA_DTYPE_F32))
+    return DA_ERR_UNSUPPORTED;
+  const size_t n = (size_t)n_;
+  hipStream_t s = (hipStream_t)stream;
+  // 4-wide accesses: 16-byte aligned bases; with CFG the cond half starts n elements in, so n must be a multiple of 4 too
+  const bool aligned = ((uintptr_t)eps | (uintptr_t)x | (uintptr_t)m1) % 16 == 0 && (!cfg || n % 4 == 0);
+  const size_t n_vec = aligned ? n - n % 4 : 0;
+  const size_t work = n_vec / 4 > n - n_vec ? n_vec / 4 : n - n_vec;
+#define DA_DP(TX, TV, C, P)                                                                                          \
+  DA_LAUNCH((dpmpp_2m_step_kernel<TX, TV, C, P>), ew_grid(work), dim3(256), 0, s, (const TV*)eps, (TX*)x, m1, table, \
+            step_idx, begin_idx, guidance, n, n_vec)
+#define DA_DP_P(TX, TV, C) \
+  do { if (pred_type == 0) DA_DP(TX, TV, C, 0); else if (pred_type == 1) DA_DP(TX, TV, C, 1); else DA_DP(TX, TV, C, 2); } while (0)
+#define DA_DP_C(TX, TV) \
+  do { if (cfg) DA_DP_P(TX, TV, true); else DA_DP_P(TX, TV, false); } while (0)
+  if (x_dtype == DA_DTYPE_BF16) {
+    if (e_dtype == DA_DTYPE_BF16) DA_DP_C(uint16_t, uint16_t); else DA_DP_C(uint16_t, float);
+  } else {
+    if (e_dtype == DA_DTYPE_BF16) DA_DP_C(float, uint16_t); else DA_DP_C(float, float);
+  }
+#undef DA_DP_C
+#undef DA_DP_P
+#undef DA_DP
   DA_CHECK_LAUNCH();
   return DA_OK;
 }

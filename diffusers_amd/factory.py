@@ -19,6 +19,11 @@ SDXL_SCHEDULER = dict(beta_start=0.00085, beta_end=0.012, beta_schedule="scaled_
                       timestep_spacing="leading")
 SD15_SCHEDULER = dict(beta_start=0.00085, beta_end=0.012, beta_schedule="scaled_linear", clip_sample=False,
                       set_alpha_to_one=False, steps_offset=1)
+# DPM-Solver++ 2M with Karras sigmas ("DPM++ 2M Karras") on the same betas: DPMSolverMultistepScheduler(**SDXL_DPM_SCHEDULER)
+SDXL_DPM_SCHEDULER = dict(beta_start=0.00085, beta_end=0.012, beta_schedule="scaled_linear", steps_offset=1,
+                          timestep_spacing="leading", use_karras_sigmas=True)
+SD15_DPM_SCHEDULER = dict(beta_start=0.00085, beta_end=0.012, beta_schedule="scaled_linear", steps_offset=1,
+                          timestep_spacing="leading", use_karras_sigmas=True)
 
 
 def build_unet(cfg: dict, seed: int = 0, device="cuda", init_device: Optional[str] = None, state_dict=None):

@@ -23,8 +23,8 @@ import torch
 from . import ops
 from .autoencoder_kl import AutoencoderKL
 from .pipeline_loading import PipelineLoadingMixin
-from .schedulers import (DDIMScheduler, DDPMScheduler, EulerDiscreteScheduler, FlowMatchEulerDiscreteScheduler,
-                         UniPCMultistepScheduler)
+from .schedulers import (DDIMScheduler, DDPMScheduler, DPMSolverMultistepScheduler, EulerDiscreteScheduler,
+                         FlowMatchEulerDiscreteScheduler, UniPCMultistepScheduler)
 from .transformer_flux import FluxTransformer2DModel
 from .transformer_wan import WanTransformer3DModel
 from .unet_2d import UNet2DModel
@@ -138,6 +138,13 @@ def denoising_end_steps(scheduler, denoising_end) -> int:
     n_train = scheduler.config.num_train_timesteps
     cutoff = int(round(n_train - denoising_end * n_train))
     return len([t for t in scheduler.timesteps.tolist() if t >= cutoff])
+
+
+def _refuse_custom_schedule(scheduler, timesteps, sigmas):
+    """retrieve_timesteps (pipeline_stable_diffusion_xl.py:144-167) for a scheduler whose set_timesteps takes a step count only."""
+    if (timesteps is not None or sigmas is not None) and isinstance(scheduler, DPMSolverMultistepScheduler):
+        raise ValueError(f"The current scheduler class {type(scheduler)}'s `set_timesteps` does not support custom "
+                         "timestep or sigma schedules. Please check whether you are using the correct scheduler.")
 
 
 def _capture_step(pipe, step, mode):
@@ -272,7 +279,7 @@ class _LatentDiffusionBase(_StepCallbacks, PipelineLoadingMixin):
         if isinstance(sch, EulerDiscreteScheduler):
             x_in = sch.scale_model_input(latents, sch.timesteps[0], rep=rep)
         else:
-            x_in = ops.mul_scalar(latents, 1.0, rep=rep) if rep > 1 else latents  # DDIM: scale_model_input = identity
+            x_in = ops.mul_scalar(latents, 1.0, rep=rep) if rep > 1 else latents  # DDIM, DPM-Solver++: scale_model_input = identity
         eps = self.unet(x_in, None, None, conditioning=cond, sampler_table=sch.device_table,
                         step_idx=sch.device_step, return_dict=False)[0]
         # in place (same buffer every replay); without CFG (guidance_scale <= 1, pipeline_stable_diffusion_xl.py:1202,
@@ -298,7 +305,8 @@ class _LatentDiffusionBase(_StepCallbacks, PipelineLoadingMixin):
         return (tuple(latents.shape), float(guidance_scale), bool(do_cfg), cond["kvs"][0][0].skv if cond["kvs"] else 0,
                 sch.device_table.data_ptr(), sch.device_step.data_ptr(),
                 self._noise_table.data_ptr() if self._noise_table is not None else 0, float(self._eta),
-                float(self._guidance_rescale), id(self.unet))       # (a captured step points into THIS model's packed weights)
+                float(self._guidance_rescale), id(self.unet),       # (a captured step points into THIS model's packed weights)
+                sch.graph_buffers(latents))                         # (DPM-Solver++: the loop's begin word, the x0 history)
 
     def _denoise(self, latents, cond, num_steps, guidance_scale, do_cfg, use_graph, begin: int = 0):
         """``num_steps`` steps from schedule entry ``begin`` (img2img / the refiner hand-off start past 0).  The captured step reads
@@ -436,6 +444,7 @@ class StableDiffusionXLPipeline(_LatentDiffusionBase):
         B = prompt_embeds.shape[0]
         # retrieve_timesteps (:144-167): a custom timestep / sigma schedule replaces the step count; denoising_end (:1164-1183) then
         # keeps the leading steps down to its cut-off (the loop below simply runs fewer replays of the same captured step)
+        _refuse_custom_schedule(self.scheduler, timesteps, sigmas)
         if timesteps is not None:
             self.scheduler.set_timesteps(timesteps=timesteps, device=dev)
         elif sigmas is not None:
@@ -784,6 +793,7 @@ class StableDiffusionXLImg2ImgPipeline(_Img2ImgMixin, StableDiffusionXLPipeline)
                              "`negative_pooled_prompt_embeds`")
         dev = self.device
         B = prompt_embeds.shape[0]
+        _refuse_custom_schedule(self.scheduler, timesteps, sigmas)
         if timesteps is not None:
             self.scheduler.set_timesteps(timesteps=timesteps, device=dev)
         elif sigmas is not None:

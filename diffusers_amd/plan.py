@@ -19,6 +19,7 @@ from __future__ import annotations
 
 import contextlib
 import ctypes as C
+import gc
 import struct
 from pathlib import Path
 from typing import Callable, List, Optional, Sequence
@@ -380,12 +381,21 @@ def recording(strict: bool = True, private_pool: bool = True):
     rec.proxy = _Proxy(L._lib if L._lib is not None else L.load(), rec)
     rec.pool = torch.cuda.MemPool() if private_pool and torch.cuda.is_available() else None
     pool_ctx = torch.cuda.use_mem_pool(rec.pool) if rec.pool is not None else contextlib.nullcontext()
+    # While the private pool is in use the caching allocator must not release another pool: a HIP graph or a Plan dropped earlier
+    # and still waiting for the cyclic collector would do just that from its finalizer, at whatever allocation triggers a collection
+    # (the allocator then aborts the process).  Collect before the pool is taken, as torch.cuda.graph does before a capture, and keep
+    # the collector off until the pool is handed back.
+    gc.collect()
+    gc_was_on = gc.isenabled()
+    gc.disable()
     L._tls.recorder = rec
     try:
         with pool_ctx, _ForeignOps(rec):
             yield rec
     finally:
         L._tls.recorder = None
+        if gc_was_on:
+            gc.enable()
     if strict and rec.foreign:
         raise RuntimeError(f"recorded code ran torch operators a plan cannot replay: {sorted(set(rec.foreign))}")
     if len(rec.streams) > 1:

@@ -6,6 +6,7 @@ Host side (schedule construction) is numpy / torch-CPU scalar math written to fo
   DDIMScheduler                   schedulers/scheduling_ddim.py:212-236, :334-382, :384-514
   DDPMScheduler                   schedulers/scheduling_ddpm.py:348-416, :461-567
   FlowMatchEulerDiscreteScheduler schedulers/scheduling_flow_match_euler_discrete.py:283-382, :423-523
+  DPMSolverMultistepScheduler     schedulers/scheduling_dpmsolver_multistep.py (dpmsolver++, order <= 2; float64 host scalars)
 Per-step scalars are evaluated once with fp32 torch scalar ops (same ops, same order as the reference evaluates them
 every step) and stored in a device table of 8 floats per step; a device-resident step counter selects the row, so a
 denoising step is HIP-graph replayable.  ``step_cfg`` additionally fuses the classifier-free-guidance combine.
@@ -163,6 +164,10 @@ class _SchedulerBase:
             raise ValueError("set_model_timesteps: call set_timesteps() first; one value per step")
         self._table[:, 7].copy_(v.to(self._table.device))
 
+    def graph_buffers(self, sample):
+        """Engine extension: addresses of device state a captured step reads besides the table and the step counter."""
+        return ()
+
     def reset(self, index: int = 0):
         """Rewind to step ``index`` (host mirror + device counter)."""
         self._step_index = index
@@ -183,6 +188,16 @@ def _sigma_to_t(sigma, log_sigmas):
     low, high = log_sigmas[low_idx], log_sigmas[high_idx]
     w = np.clip((low - log_sigma) / (low - high), 0, 1)
     return ((1 - w) * low_idx + w * high_idx).reshape(np.shape(sigma))
+
+
+def _respaced_sigmas(smin: float, smax: float, n: int, karras: bool):
+    """``n`` sigmas from ``smax`` down to ``smin``: Karras et al. (rho = 7) or uniform in log sigma
+    (scheduling_euler_discrete.py:520-585, the same two functions in scheduling_dpmsolver_multistep.py)."""
+    if karras:
+        rho = 7.0
+        ramp = np.linspace(0, 1, n)
+        return (smax ** (1 / rho) + ramp * (smin ** (1 / rho) - smax ** (1 / rho))) ** rho
+    return np.exp(np.linspace(math.log(smax), math.log(smin), n))
 
 
 class EulerDiscreteScheduler(_SchedulerBase):
@@ -271,12 +286,7 @@ class EulerDiscreteScheduler(_SchedulerBase):
             # the step kernel reads sigma / dt / timestep from the same table as before.
             smin = c.sigma_min if c.sigma_min is not None else sig[-1].item()
             smax = c.sigma_max if c.sigma_max is not None else sig[0].item()
-            if c.use_karras_sigmas:
-                rho = 7.0
-                ramp = np.linspace(0, 1, num_inference_steps)
-                sig = (smax ** (1 / rho) + ramp * (smin ** (1 / rho) - smax ** (1 / rho))) ** rho
-            else:
-                sig = np.exp(np.linspace(math.log(smax), math.log(smin), num_inference_steps))
+            sig = _respaced_sigmas(smin, smax, num_inference_steps, karras=c.use_karras_sigmas)
             ts = np.array([_sigma_to_t(s_, np.log(base)) for s_ in sig])
         if c.final_sigmas_type == "sigma_min":
             last = float(((1 - self.alphas_cumprod[0]) / self.alphas_cumprod[0]) ** 0.5)
@@ -885,3 +895,244 @@ class UniPCMultistepScheduler(_SchedulerBase):
         ops.unipc_flow_step_(model_output, sample, last, m1, m2, self._coef, self._step_dev)
         self._advance()
         return sample
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+def _vp_alpha_sigma(s):
+    """(alpha, sigma) of the variance-preserving form of a k-diffusion sigma ``s`` (float64):
+    alpha = 1 / sqrt(s^2 + 1), sigma = s alpha (scheduling_dpmsolver_multistep.py _sigma_to_alpha_sigma_t)."""
+    s = np.float64(s)
+    a = 1.0 / np.sqrt(s * s + 1.0)
+    return a, s * a
+
+
+def _vp_lambda(s):
+    """Half log-SNR log(alpha) - log(sigma) of a sigma > 0 (float64)."""
+    a, b = _vp_alpha_sigma(s)
+    return np.log(a) - np.log(b)
+
+
+class DPMSolverMultistepScheduler(_SchedulerBase):
+    """schedulers/scheduling_dpmsolver_multistep.py with ``algorithm_type="dpmsolver++"``, ``solver_order`` <= 2 -- "DPM++ 2M",
+    usually run with Karras sigmas.  Every scalar of a step (alpha / sigma of the current row, the first-order pair and, where
+    the row may run second order, the D1 coefficient with ``1 / r0`` and the midpoint / heun factor folded in) is evaluated on
+    the host in float64 and stored as one fp32 row of the device table; ONE kernel per step (da_dpmpp_2m_step) converts the model
+    output to x0, applies the row and rolls the fp32 x0 history in place, so the step is HIP-graph replayable.  The first step of
+    a loop runs first order wherever it starts: the kernel compares the device step counter with a second device word, the loop's
+    begin row, which ``reset`` / ``set_begin_index`` / the first ``step`` write."""
+
+    _defaults = dict(num_train_timesteps=1000, beta_start=0.0001, beta_end=0.02, beta_schedule="linear", trained_betas=None,
+                     solver_order=2, prediction_type="epsilon", thresholding=False, dynamic_thresholding_ratio=0.995,
+                     sample_max_value=1.0, algorithm_type="dpmsolver++", solver_type="midpoint", lower_order_final=True,
+                     euler_at_final=False, use_karras_sigmas=False, use_exponential_sigmas=False, use_beta_sigmas=False,
+                     use_lu_lambdas=False, use_flow_sigmas=False, flow_shift=1.0, final_sigmas_type="zero",
+                     lambda_min_clipped=-float("inf"), variance_type=None, timestep_spacing="linspace", steps_offset=0,
+                     rescale_betas_zero_snr=False, use_dynamic_shifting=False, time_shift_type="exponential")
+
+    def __init__(self, **kwargs):
+        super().__init__(**kwargs)
+        c = self.config
+        name = type(self).__name__
+        if c.algorithm_type != "dpmsolver++":
+            raise NotImplementedError(f"{name}: algorithm_type={c.algorithm_type!r} is not implemented (only 'dpmsolver++')")
+        if c.solver_order not in (1, 2):
+            raise NotImplementedError(f"{name}: solver_order={c.solver_order} is not implemented (1 or 2)")
+        if c.solver_type not in ("midpoint", "heun"):
+            raise NotImplementedError(f"{name}: solver_type={c.solver_type!r} is not implemented ('midpoint' or 'heun')")
+        if c.prediction_type not in L.PRED_TYPES:
+            raise NotImplementedError(f"{name}: prediction_type={c.prediction_type!r} is not implemented "
+                                      "('epsilon', 'v_prediction' or 'sample')")
+        for flag in ("thresholding", "use_beta_sigmas", "use_lu_lambdas", "use_flow_sigmas", "rescale_betas_zero_snr",
+                     "use_dynamic_shifting"):
+            if c[flag]:
+                raise NotImplementedError(f"{name}: {flag}=True is not implemented")
+        if not math.isinf(c.lambda_min_clipped) or c.lambda_min_clipped > 0:
+            raise NotImplementedError(f"{name}: lambda_min_clipped={c.lambda_min_clipped} is not implemented (-inf only)")
+        if c.variance_type is not None:
+            raise NotImplementedError(f"{name}: variance_type={c.variance_type!r} is not implemented (None only)")
+        if c.use_karras_sigmas and c.use_exponential_sigmas:
+            raise ValueError("Only one of `config.use_beta_sigmas`, `config.use_exponential_sigmas`, "
+                             "`config.use_karras_sigmas` can be used.")
+        if c.final_sigmas_type not in ("zero", "sigma_min"):
+            raise ValueError(f"`final_sigmas_type` must be one of 'zero', or 'sigma_min', but got {c.final_sigmas_type}")
+        self._pred = L.PRED_TYPES[c.prediction_type]
+        # the training ladder in float64 like every other scalar of this class: in fp32, 1 - alphas_cumprod[0] cancels down to
+        # four digits and sigma_min of the SD betas comes out 1.3e-5 high (0.0291675 for 0.0291672)
+        if c.trained_betas is not None:
+            betas = np.asarray(c.trained_betas, dtype=np.float64)
+        elif c.beta_schedule == "linear":
+            betas = np.linspace(c.beta_start, c.beta_end, c.num_train_timesteps, dtype=np.float64)
+        elif c.beta_schedule == "scaled_linear":
+            betas = np.linspace(c.beta_start ** 0.5, c.beta_end ** 0.5, c.num_train_timesteps, dtype=np.float64) ** 2
+        else:
+            raise NotImplementedError(f"{c.beta_schedule} is not implemented")
+        ac = np.cumprod(1.0 - betas)
+        self._sig_all = np.sqrt((1.0 - ac) / ac)
+        self.betas = torch.from_numpy(betas).float()
+        self.alphas = 1.0 - self.betas
+        # (the float64 product rounded once: not bit-equal to the fp32 cumprod the other schedulers hold for the same betas)
+        self.alphas_cumprod = torch.from_numpy(ac).float()
+        self.init_noise_sigma = 1.0
+        ts = np.arange(0, c.num_train_timesteps)[::-1].copy().astype(np.int64)
+        self.timesteps = torch.from_numpy(ts)
+        self._timesteps_host = ts
+        self.sigmas = torch.from_numpy(np.concatenate([self._sig_all[::-1], [0.0]]).astype(np.float32))
+        self._begin_dev = None      # device int32: the row the running loop started at
+        self._hist = None           # fp32 x0 prediction of the previous step
+        self.second_order_rows = None
+
+    def set_timesteps(self, num_inference_steps: int = None, device=None, mu=None, timesteps=None):
+        c = self.config
+        if timesteps is not None:
+            raise NotImplementedError("custom timesteps are not supported by the HIP DPMSolverMultistepScheduler")
+        if num_inference_steps is None:
+            raise ValueError("Must pass exactly one of `num_inference_steps` or `timesteps`.")
+        n, N = int(num_inference_steps), c.num_train_timesteps
+        if c.timestep_spacing == "linspace":
+            ts = np.linspace(0, N - 1, n + 1).round()[::-1][:-1].copy().astype(np.int64)
+        elif c.timestep_spacing == "leading":
+            ts = (np.arange(0, n + 1) * (N // (n + 1))).round()[::-1][:-1].copy().astype(np.int64)
+            ts += c.steps_offset
+        elif c.timestep_spacing == "trailing":
+            ts = np.arange(N, 0, -N / n).round().copy().astype(np.int64)
+            ts -= 1
+        else:
+            raise ValueError(f"{c.timestep_spacing} is not supported. Please make sure to choose one of 'linspace', "
+                             "'leading' or 'trailing'.")
+        sig_all = self._sig_all
+        if c.use_karras_sigmas or c.use_exponential_sigmas:
+            sig = _respaced_sigmas(float(sig_all[0]), float(sig_all[-1]), n, karras=c.use_karras_sigmas)
+            log_sigmas = np.log(sig_all)
+            ts = np.array([_sigma_to_t(s_, log_sigmas) for s_ in sig]).round().astype(np.int64)
+        else:
+            sig = np.interp(ts, np.arange(0, N), sig_all)
+        last = 0.0 if c.final_sigmas_type == "zero" else float(sig_all[0])
+        sig = np.concatenate([sig, [last]]).astype(np.float32)
+        self.sigmas = torch.from_numpy(sig)                      # kept on the CPU like the reference
+        self.timesteps = torch.from_numpy(ts).to(device=device, dtype=torch.int64)
+        self._timesteps_host = ts
+        self.num_inference_steps = n
+        self._step_index = None
+        self._begin_index = None
+        rows = self._rows(sig, ts)
+        self.second_order_rows = [bool(r[6]) for r in rows]
+        self._upload(rows, device)
+
+    def _rows(self, sig: np.ndarray, ts: np.ndarray) -> np.ndarray:
+        """[alpha_s0, sigma_s0, cx, c0, cd, 0, second_order_allowed, timestep] per step, float64 host math on the fp32 sigmas.
+        Row i steps from s0 = sig[i] to t = sig[i+1], h = lambda_t - lambda_s0:
+          first order   x' = (sigma_t / sigma_s0) x - alpha_t (exp(-h) - 1) x0                     -> cx x + c0 x0
+          second order  + cd (x0 - m1),  cd = -0.5 alpha_t (exp(-h) - 1) / r0 (midpoint) | alpha_t ((exp(-h) - 1) / h + 1) / r0 (heun),
+                        r0 = (lambda_s0 - lambda_s1) / h, s1 = sig[i-1]
+        A final sigma of 0 has h = inf: exp(-h) - 1 = -1 and sigma_t = 0 are set here, the row is x' = x0, nothing non-finite is
+        stored.  A step of no length (t = s0) is the identity row.  A row may run second order unless solver_order == 1, it is
+        row 0, or it is the last row and (euler_at_final or the final sigma is 0 or (lower_order_final and fewer than 15 steps));
+        the kernel also runs the loop's first step first order."""
+        c = self.config
+        n = len(ts)
+        rows = np.zeros((n, 8), dtype=np.float64)
+        for i in range(n):
+            s0, t = sig[i], sig[i + 1]
+            a0, b0 = _vp_alpha_sigma(s0)
+            at, bt = _vp_alpha_sigma(t)
+            if t == 0:
+                h, em1 = np.inf, -1.0
+            else:
+                h = _vp_lambda(t) - _vp_lambda(s0)
+                em1 = np.exp(-h) - 1.0
+            rows[i, :4] = a0, b0, bt / b0, -at * em1
+            rows[i, 7] = float(ts[i])
+            if h == 0:      # a step of no length (a ladder that ends at sigma_min, then final_sigmas_type="sigma_min"): x' = x
+                continue
+            last_first = i == n - 1 and (c.euler_at_final or c.final_sigmas_type == "zero" or (c.lower_order_final and n < 15))
+            if c.solver_order == 2 and i > 0 and not last_first:
+                r0 = (_vp_lambda(s0) - _vp_lambda(sig[i - 1])) / h
+                d1 = -0.5 * at * em1 if c.solver_type == "midpoint" else at * (em1 / h + 1.0)
+                rows[i, 4], rows[i, 6] = d1 / r0, 1.0
+        rows = rows.astype(np.float32)
+        if not np.isfinite(rows).all():
+            raise ValueError("DPMSolverMultistepScheduler: non-finite step coefficients (repeated sigmas in the schedule?)")
+        return rows
+
+    def _upload(self, rows, device):
+        super()._upload(rows, device)
+        if self._begin_dev is None or self._begin_dev.device != self._table.device:
+            self._begin_dev = torch.zeros((), dtype=torch.int32, device=self._table.device)
+        else:
+            self._begin_dev.zero_()         # in place: captured graphs keep the address
+
+    def _sync_device_step(self):
+        """reset() and the first step() of a loop come through here: the loop starts at this row."""
+        super()._sync_device_step()
+        if self._begin_dev is not None:
+            self._begin_dev.fill_(int(self._step_index))
+
+    def set_begin_index(self, begin_index: int = 0):
+        super().set_begin_index(begin_index)
+        if self._begin_dev is not None and self._step_index is None:
+            self._begin_dev.fill_(int(begin_index))
+
+    @property
+    def device_begin(self):
+        return self._begin_dev
+
+    def history(self, sample):
+        """The fp32 x0 history buffer for samples of this size (allocated once: captured graphs hold its address).  Its content
+        is never read by the first step of a loop, so it is not cleared between loops."""
+        if self._hist is None or self._hist.shape != sample.shape or self._hist.device != sample.device:
+            self._hist = torch.zeros(sample.shape, dtype=torch.float32, device=sample.device)
+        return self._hist
+
+    def graph_buffers(self, sample):
+        return (self._begin_dev.data_ptr(), self.history(sample).data_ptr())
+
+    def _add_noise_coeffs(self, timesteps, dtype):
+        """scheduling_dpmsolver_multistep.py add_noise: alpha_t x + sigma_t n of the sigma at ``begin_index`` (img2img: before the
+        first step), at ``step_index`` (after it), or of each timestep's index when no begin index is set; ops in ``dtype``."""
+        sig = self.sigmas.to(dtype=dtype)
+        ts = torch.as_tensor(timesteps).reshape(-1).cpu()
+        if self.begin_index is None:
+            idx = [self.index_for_timestep(t) for t in ts]
+        elif self.step_index is not None:
+            idx = [self.step_index] * ts.shape[0]
+        else:
+            idx = [self.begin_index] * ts.shape[0]
+        s = sig[idx]
+        a = 1 / ((s ** 2 + 1) ** 0.5)
+        b = s * a
+        return [float(v) for v in a], [float(v) for v in b]
+
+    def _before_step(self, timestep):
+        if self.num_inference_steps is None:
+            raise ValueError("Number of inference steps is 'None', you need to run 'set_timesteps' after creating the "
+                             "scheduler")
+        if self._step_index is None:
+            self._init_step_index(timestep)
+        if not 0 <= self._step_index < self.num_inference_steps:
+            raise IndexError(f"DPMSolverMultistepScheduler: step {self._step_index} of a {self.num_inference_steps}-step "
+                             "schedule (call set_timesteps() or reset() before another loop)")
+
+    def _run(self, model_output, sample, cfg, guidance_scale):
+        ops.dpmpp_2m_step_(model_output, sample, self.history(sample), self._table, self._step_dev, self._begin_dev, cfg=cfg,
+                           guidance=float(guidance_scale), pred_type=self._pred)
+        self._advance()
+        return sample
+
+    def step(self, model_output, timestep, sample, generator=None, variance_noise=None, return_dict: bool = True):
+        """``generator`` / ``variance_noise`` belong to the SDE variants and are unused by dpmsolver++."""
+        self._before_step(timestep)
+        prev = self._run(model_output.contiguous(), sample.contiguous().clone(), False, 0.0)
+        if not return_dict:
+            return (prev,)
+        return SchedulerOutput(prev_sample=prev)
+
+    def step_cfg(self, model_output_2b, sample, guidance_scale: float, out=None, cfg: bool = True):
+        """Engine extension: CFG combine (``cfg=False``: a plain model output) + the step, written over ``sample`` (graph replay)."""
+        if out is not None and out.data_ptr() != sample.data_ptr():
+            raise ValueError("DPMSolverMultistepScheduler.step_cfg updates `sample` in place")
+        self._before_step(self.timesteps[0])
+        return self._run(model_output_2b, sample, cfg, guidance_scale)
+
+    def step_inplace(self, model_output, sample):
+        self._before_step(self.timesteps[0])
+        return self._run(model_output, sample, False, 0.0)

@@ -15,10 +15,11 @@ name ends in ``_``).  Registration happens on import of this module (``import di
     y = torch.ops.mi355x.groupnorm(x, gamma, beta, 32, 1e-5, True)
     y = torch.ops.mi355x.layernorm(x, gamma, beta, 1e-5)
     x_next = torch.ops.mi355x.euler_step(eps, x, table, step_idx, True, 5.0, 0)
+    x_next, m1 = torch.ops.mi355x.dpmpp_2m_step(eps, x, m1, table, step_idx, begin_idx, True, 5.0, 0)
 """
 from __future__ import annotations
 
-from typing import Optional
+from typing import Optional, Tuple
 
 import torch
 
@@ -106,4 +107,20 @@ def _(model_output, sample, table, step_idx, cfg, guidance_scale, pred_type):
     return torch.empty_like(sample)
 
 
-OPS = ("gemm", "conv2d_nhwc", "flash_attn", "groupnorm", "layernorm", "euler_step")
+@torch.library.custom_op(f"{NAMESPACE}::dpmpp_2m_step", mutates_args=(), device_types="cuda")
+def dpmpp_2m_step(model_output: torch.Tensor, sample: torch.Tensor, history: torch.Tensor, table: torch.Tensor,
+                  step_idx: torch.Tensor, begin_idx: torch.Tensor, cfg: bool, guidance_scale: float,
+                  pred_type: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """DPMSolverMultistepScheduler.step (DPM-Solver++ 2M; + the CFG combine when ``cfg``) from the scheduler's device table:
+    returns (new sample, new fp32 history = this step's x0 prediction).  Functional form of the in-place kernel."""
+    x, m1 = sample.contiguous().clone(), history.contiguous().clone()
+    ops.dpmpp_2m_step_(model_output, x, m1, table, step_idx, begin_idx, cfg=cfg, guidance=guidance_scale, pred_type=pred_type)
+    return x, m1
+
+
+@dpmpp_2m_step.register_fake
+def _(model_output, sample, history, table, step_idx, begin_idx, cfg, guidance_scale, pred_type):
+    return torch.empty_like(sample), torch.empty_like(history)
+
+
+OPS = ("gemm", "conv2d_nhwc", "flash_attn", "groupnorm", "layernorm", "euler_step", "dpmpp_2m_step")

@@ -98,8 +98,9 @@ extern "C" {
  * structs by hand (ctypes, JNI, cgo), `da_sizeof_*()` against their own sizeof -- because the structs carry no size field: a host
  * built against an older header would pass shorter structs and the library would read garbage for the new members
  * (da_gemm_params.vt is a STORE address).  History: 1 = rounds 1-3; 4 = round 4 (da_gemm_params.vt / vt_col0 / ld_vt,
- * da_attention_params.algo); 5 = round 5; 6 = round 6 (this header: da_attention_params.split_ws / split_ws_bytes / kv_split; da_groupnorm_nhwc_bf16 takes `sync`). */
-#define DA_ABI_VERSION 6
+ * da_attention_params.algo); 5 = round 5; 6 = round 6 (da_attention_params.split_ws / split_ws_bytes / kv_split; da_groupnorm_nhwc_bf16 takes `sync`);
+ * 7 = this header (da_dpmpp_2m_step, DA_FN_DPMPP_2M_STEP). */
+#define DA_ABI_VERSION 7
 int da_version(void);
 size_t da_sizeof_gemm_params(void);
 size_t da_sizeof_attention_params(void);
@@ -432,6 +433,14 @@ int da_flowmatch_step(const void* v, const void* x, void* out, const float* tabl
  * rk_p, -, -]; x_dtype (sample + history) / v_dtype (model output): f32/f32, f32/bf16 (Wan pipeline) or bf16/bf16. */
 int da_unipc_flow_step(const void* v, void* x, void* last, void* m1, void* m2, const float* coef, const int* step_idx,
                        int cfg, float guidance, long long n, int x_dtype, int v_dtype, void* stream);
+/* da_dpmpp_2m_step: DPM-Solver++ multistep (2M) update, orders 1 / 2 (DPMSolverMultistepScheduler, algorithm_type
+ * "dpmsolver++", midpoint / heun folded into the row): x0 conversion + update + history roll (m1 <- x0) in ONE pass, in place on
+ * x; m1 is an fp32 tensor of n elements whatever the sample's dtype.  row = [alpha_s0, sigma_s0, cx, c0, cd, -, second_order_allowed,
+ * timestep]: x' = cx x + c0 x0 [+ cd (x0 - m1)], the bracket only when the row allows it and *step_idx != *begin_idx (the first
+ * step of a loop is first order wherever it starts).  fp32 arithmetic, one rounding at the store of x.  x_dtype (sample) and
+ * e_dtype (model output) are independent: bf16 or f32 each. */
+int da_dpmpp_2m_step(const void* eps, void* x, float* m1, const float* table, const int* step_idx, const int* begin_idx,
+                     int cfg, float guidance, long long n, int x_dtype, int e_dtype, int pred_type, void* stream);
 int da_advance_step(int* step_idx, void* stream);
 /* rescale_noise_cfg (pipelines/stable_diffusion/pipeline_stable_diffusion.py:69-92; SDXL :1227-1229, SD :1057-1059): eps
  * [2][B][n_per] = (uncond, cond) -> out [B][n_per] = guidance_rescale * (cfg * std(text) / std(cfg)) + (1 - guidance_rescale) * cfg
@@ -589,7 +598,8 @@ int da_vae_posterior_latents(const void* in, long long sB, long long sC, long lo
 #define DA_FN_LINEAR_SMALL_M 29           /* da_linear_small_m_bf16 */
 #define DA_FN_CONV_THIN_IN 30             /* da_conv_thin_in_bf16 */
 #define DA_FN_CONV_THIN_OUT 31            /* da_conv_thin_out_bf16 */
-#define DA_FN_COUNT 32
+#define DA_FN_DPMPP_2M_STEP 32            /* da_dpmpp_2m_step */
+#define DA_FN_COUNT 33
 #define DA_PLAN_MAX_ARGS 16
 
 typedef struct da_plan_op {
