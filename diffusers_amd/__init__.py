@@ -31,6 +31,8 @@ _EXPORTS = {
     "StableDiffusionXLPipeline": "pipelines",
     "StableDiffusionImg2ImgPipeline": "pipelines",
     "StableDiffusionXLImg2ImgPipeline": "pipelines",
+    "StableDiffusionInpaintPipeline": "pipelines",
+    "StableDiffusionXLInpaintPipeline": "pipelines",
     "from_reference_config": "config_utils",
     "CLIPTextModel": "text_encoders",
     "CLIPTextModelWithProjection": "text_encoders",

@@ -86,7 +86,7 @@ FN_IDS = {name: i + 1 for i, name in enumerate((
     "da_mul_scalar", "da_bcast_add_f32", "da_patchify3d_bf16", "da_unpatchify3d_bf16", "da_transpose_bf16",
     "da_nhwc_take_nchw_bf16", "da_nhwc_take_postprocess", "da_permute_0213_bf16", "da_image_postprocess",
     "da_frames_to_ncthw_bf16", "da_timestep_embedding", "da_linear_small_m_bf16", "da_conv_thin_in_bf16",
-    "da_conv_thin_out_bf16", "da_dpmpp_2m_step"))}
+    "da_conv_thin_out_bf16", "da_inpaint_blend", "da_conv_in_inpaint", "da_dpmpp_2m_step"))}
 FN_COUNT = len(FN_IDS) + 1
 
 
@@ -128,6 +128,7 @@ SIGNATURES = {
     "da_unipc_flow_step": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _f, _ll, _i, _i, _vp]),
     "da_dpmpp_2m_step": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _f, _ll, _i, _i, _i, _vp]),
     "da_advance_step": (_i, [_vp, _vp]),
+    "da_inpaint_blend": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _ll, _i, _vp]),
     "da_cfg_rescale": (_i, [_vp, _vp, _vp, _i, _ll, _f, _f, _i, _vp]),
     "da_cast_f32_bf16": (_i, [_vp, _vp, _i, _ll, _vp]),
     "da_mul_scalar": (_i, [_vp, _vp, _f, _i, _ll, _i, _vp]),
@@ -145,6 +146,7 @@ SIGNATURES = {
     "da_linear_small_m_bf16": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "da_conv_thin_in_bf16": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _f, _f, _vp]),
     "da_conv_thin_out_bf16": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
+    "da_conv_in_inpaint": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     "da_vae_conv_in_image": (_i, [_vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "da_vae_posterior_latents": (_i, [_vp, _ll, _ll, _ll, _vp, _vp, _vp, _vp, _vp, _i, _ll, _i, _i, _i, _f, _f, _f, _f, _vp]),
     "da_plan_create": (_i, [C.POINTER(PlanOp), _i, C.POINTER(C.c_void_p)]),
@@ -162,7 +164,7 @@ IMAGE_F32_NCHW, IMAGE_F32_NHWC, IMAGE_U8_NHWC = 0, 1, 2
 POSTERIOR_MOMENTS, POSTERIOR_MEAN, POSTERIOR_SAMPLE, POSTERIOR_NOISE = 0, 1, 2, 3
 LATENTS_SHIFT, LATENTS_SCALE = 1, 2
 
-ABI_VERSION = 7              # include/diffusers_amd.h DA_ABI_VERSION
+ABI_VERSION = 8              # include/diffusers_amd.h DA_ABI_VERSION
 _lib = None
 _tls = threading.local()     # .recorder: the plan recorder of this thread (diffusers_amd/plan.py), if one is active
 

@@ -298,6 +298,113 @@ __global__ __launch_bounds__(256) void conv_thin_in4_kernel(const void* __restri
   }
 }
 
+// conv_in of a 9-channel inpainting U-Net (runwayml/stable-diffusion-inpainting, the SDXL inpainting checkpoint) read from its three
+// sources: the reference builds torch.cat([scale_model_input(latents)] * rep, [mask] * rep, [masked_image_latents] * rep, dim=1) every
+// step (pipeline_stable_diffusion_inpaint.py: the `num_channels_unet == 9` branch) and hands it to conv_in.  Here nothing is
+// concatenated: channels 0-3 come from x [B][4][H][W], channel 4 from mask [Bm][1][H][W], channels 5-8 from masked [Bm][4][H][W]
+// (Bm in {1, B}), the Euler scale s(x) = bf16(x / table[*step_idx][3]) (euler_scale_input_kernel's arithmetic; `table` NULL: identity) is
+// applied at the load, and the two CFG halves, whose inputs are identical, are computed once and stored `rep` times.
+// The structure is conv_thin_in4_kernel's: weights in LDS k-major, four output pixels of a row per thread, a kernel row's six input columns
+// loaded once -- unconditionally, from clamped addresses, zeroed by a select -- for the four pixels that share them; per output element
+// bias, then the taps in (kh, kw, c) order, padded taps skipped: bit-identical to da_conv_thin_in_bf16 on the concatenated tensor.
+__global__ __launch_bounds__(256) void conv_in_inpaint_kernel(const uint16_t* __restrict__ x, const uint16_t* __restrict__ mask,
+                                                              const uint16_t* __restrict__ masked, const uint16_t* __restrict__ w,
+                                                              const uint16_t* __restrict__ bias, uint16_t* __restrict__ y,
+                                                              const float* __restrict__ table, const int* __restrict__ step_idx, int B,
+                                                              int H, int W, int Cout, int rep, int cond_per_sample, int coc) {
+  extern __shared__ __attribute__((aligned(16))) float wsm[];  // [81][coc]
+  constexpr int CIN = 9, kk = 9 * CIN;
+  const int co0 = blockIdx.y * coc;
+  const int ncoc = min(coc, Cout - co0);
+  for (int i = threadIdx.x; i < ncoc * kk; i += blockDim.x) {
+    const int k = i / ncoc, co = i - k * ncoc;
+    wsm[k * coc + co] = bf2f(w[(size_t)(co0 + co) * kk + k]);
+  }
+  const bool scale = table != nullptr;
+  const float den = scale ? table[(size_t)(*step_idx) * 8 + 3] : 1.0f;
+  __syncthreads();
+  const int cgroups = ncoc >> 3;
+  const size_t plane = (size_t)H * W;
+  const int wq = (W + 3) >> 2;
+  const size_t total = (size_t)B * H * wq * cgroups;
+  for (size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (size_t)gridDim.x * blockDim.x) {
+    const int cg = (int)(idx % cgroups);
+    const size_t quad = idx / cgroups;
+    const int x0 = (int)(quad % wq) * 4;
+    const int yh = (int)((quad / wq) % H);
+    const int b = (int)(quad / ((size_t)wq * H));
+    const int bm = cond_per_sample ? b : 0;
+    float acc[4][8];
+    {
+      float bvs[8];
+      if (bias) {                                            // (16-byte aligned: checked by the entry point)
+        unpack8(*(const uint4*)(bias + co0 + cg * 8), bvs);
+      } else {
+#pragma unroll
+        for (int e = 0; e < 8; ++e) bvs[e] = 0.f;
+      }
+#pragma unroll
+      for (int e = 0; e < 8; ++e)
+#pragma unroll
+        for (int px = 0; px < 4; ++px) acc[px][e] = bvs[e];
+    }
+#pragma unroll
+    for (int kh = 0; kh < 3; ++kh) {
+      const int iy = yh + kh - 1;
+      const bool row_ok = (unsigned)iy < (unsigned)H;
+      const int iyc = min(max(iy, 0), H - 1);
+      const uint16_t* xrow = x + (size_t)b * 4 * plane + (size_t)iyc * W;
+      const uint16_t* mrow = mask + (size_t)bm * plane + (size_t)iyc * W;
+      const uint16_t* irow = masked + (size_t)bm * 4 * plane + (size_t)iyc * W;
+      uint16_t raw[6][CIN];
+#pragma unroll
+      for (int j = 0; j < 6; ++j) {
+        const int ixc = min(max(x0 + j - 1, 0), W - 1);
+#pragma unroll
+        for (int c = 0; c < 4; ++c) raw[j][c] = xrow[(size_t)c * plane + ixc];
+        raw[j][4] = mrow[ixc];
+#pragma unroll
+        for (int c = 0; c < 4; ++c) raw[j][5 + c] = irow[(size_t)c * plane + ixc];
+      }
+      float xin[6][CIN];
+#pragma unroll
+      for (int j = 0; j < 6; ++j) {
+        const bool ok = row_ok && (unsigned)(x0 + j - 1) < (unsigned)W;
+#pragma unroll
+        for (int c = 0; c < CIN; ++c) {
+          float xv = bf2f(raw[j][c]);
+          if (c < 4 && scale) xv = bf2f(f2bf(__fdiv_rn(xv, den)));
+          xin[j][c] = ok ? xv : 0.f;
+        }
+      }
+      if (!row_ok) continue;
+#pragma unroll
+      for (int kw = 0; kw < 3; ++kw)
+#pragma unroll
+        for (int c = 0; c < CIN; ++c) {
+          const float* wp = wsm + (size_t)((kh * 3 + kw) * CIN + c) * coc + cg * 8;
+          const float4 w0 = *(const float4*)wp, w1 = *(const float4*)(wp + 4);
+#pragma unroll
+          for (int px = 0; px < 4; ++px) {
+            const int ix = x0 + px + kw - 1;
+            if ((unsigned)ix >= (unsigned)W) continue;       // (skipped, not multiplied by zero: the sign of a zero sum)
+            const float xv = xin[px + kw][c];
+            acc[px][0] += xv * w0.x; acc[px][1] += xv * w0.y; acc[px][2] += xv * w0.z; acc[px][3] += xv * w0.w;
+            acc[px][4] += xv * w1.x; acc[px][5] += xv * w1.y; acc[px][6] += xv * w1.z; acc[px][7] += xv * w1.w;
+          }
+        }
+    }
+#pragma unroll
+    for (int px = 0; px < 4; ++px) {
+      if (x0 + px >= W) break;
+      const uint4 o = pack8(acc[px]);
+      const size_t pix = ((size_t)b * H + yh) * W + x0 + px;
+      *(uint4*)(y + pix * Cout + co0 + cg * 8) = o;
+      if (rep == 2) *(uint4*)(y + ((size_t)B * plane + pix) * Cout + co0 + cg * 8) = o;
+    }
+  }
+}
+
 // Thin-output conv 3x3 / pad 1: Cout <= 16, input NHWC [B][H][W][Cin] (Cin % 8 == 0), output NCHW (bf16 or fp32).
 // Thread = one output pixel, all Cout channels; weights [Cout][3][3][Cin] staged in LDS as bf16.
 template <int COUT>
@@ -639,6 +746,28 @@ extern "C" int da_conv_thin_in_bf16(const void* x, const void* w, const void* bi
   DA_LAUNCH(conv_thin_in_kernel, dim3((unsigned)blocks, (unsigned)nchunk), dim3(256), lds, (hipStream_t)stream,
             (const uint16_t*)x, (const uint16_t*)w, (const uint16_t*)bias, (uint16_t*)y, B, H, W, Cin, Cout, ksize,
             in_nchw, in_div, in_add, coc);
+  DA_CHECK_LAUNCH();
+  return DA_OK;
+}
+
+extern "C" int da_conv_in_inpaint(const void* x, const void* mask, const void* masked, const void* w, const void* bias, void* y,
+                                  const float* table, const int* step_idx, int B, int H, int W, int Cout, int rep, int Bm,
+                                  void* stream) {
+  if (!x || !mask || !masked || !w || !y || B <= 0 || H <= 0 || W <= 0 || (table && !step_idx)) return DA_ERR_INVALID;
+  if ((rep != 1 && rep != 2) || (Bm != 1 && Bm != B)) return DA_ERR_INVALID;
+  if (Cout <= 0 || (Cout & 7) || ((uintptr_t)bias & 15)) return DA_ERR_UNSUPPORTED;
+  // the launch geometry of the four-pixel branch of da_conv_thin_in_bf16 with Cin = 9: 81 x coc floats of weights per chunk
+  const int kk = 81;
+  int coc = ((64 * 1024) / (kk * (int)sizeof(float))) & ~7;
+  if (coc > Cout) coc = Cout;
+  const int nchunk = (Cout + coc - 1) / coc;
+  const size_t lds = (size_t)coc * kk * sizeof(float);
+  const size_t cap = 768 / nchunk > 0 ? 768 / nchunk : 1;
+  size_t qblocks = ((size_t)B * H * ((W + 3) / 4) * (coc / 8) + 255) / 256;
+  if (qblocks > cap) qblocks = cap;
+  DA_LAUNCH(conv_in_inpaint_kernel, dim3((unsigned)qblocks, (unsigned)nchunk), dim3(256), lds, (hipStream_t)stream, (const uint16_t*)x,
+            (const uint16_t*)mask, (const uint16_t*)masked, (const uint16_t*)w, (const uint16_t*)bias, (uint16_t*)y, table, step_idx, B, H,
+            W, Cout, rep, Bm == B && B > 1 ? 1 : 0, coc);
   DA_CHECK_LAUNCH();
   return DA_OK;
 }

@@ -51,6 +51,8 @@ const char* const kSig[DA_FN_COUNT] = {
     /* DA_FN_LINEAR_SMALL_M           */ "pppppiiiiiiii",
     /* DA_FN_CONV_THIN_IN             */ "ppppiiiiiiiff",
     /* DA_FN_CONV_THIN_OUT            */ "ppppiiiiii",
+    /* DA_FN_INPAINT_BLEND            */ "ppppppiiili",
+    /* DA_FN_CONV_IN_INPAINT          */ "ppppppppiiiiii",
     /* DA_FN_DPMPP_2M_STEP            */ "ppppppifliii",
 };
 
@@ -156,6 +158,10 @@ int run_op(const Op& op, void* s) {
     case DA_FN_CONV_THIN_OUT: return da_conv_thin_out_bf16(P(0), P(1), P(2), P(3), I(4), I(5), I(6), I(7), I(8), I(9), s);
     case DA_FN_DPMPP_2M_STEP:
       return da_dpmpp_2m_step(P(0), P(1), (float*)P(2), CF(3), CI(4), CI(5), I(6), F(7), LL(8), I(9), I(10), I(11), s);
+    case DA_FN_INPAINT_BLEND:
+      return da_inpaint_blend(P(0), P(1), P(2), P(3), CF(4), CI(5), I(6), I(7), I(8), LL(9), I(10), s);
+    case DA_FN_CONV_IN_INPAINT:
+      return da_conv_in_inpaint(P(0), P(1), P(2), P(3), P(4), P(5), CF(6), CI(7), I(8), I(9), I(10), I(11), I(12), I(13), s);
   }
 #undef P
 #undef CF

@@ -344,6 +344,55 @@ __global__ void dpmpp_2m_step_kernel(const TV* __restrict__ eps, TX* __restrict_
   }
 }
 
+// Inpainting with a 4-channel U-Net re-imposes the known region after every scheduler step
+// (pipelines/stable_diffusion/pipeline_stable_diffusion_inpaint.py, the `num_channels_unet == 4` branch of the loop):
+//   init_latents_proper = scheduler.add_noise(image_latents, noise, timesteps[i + 1])     (the clean latents after the last step)
+//   latents = (1 - mask) * init_latents_proper + mask * latents
+// One pass, in place over the latents, every bf16 rounding of the reference's op chain kept:
+//   p = bf16(bf16(a x0) + bf16(b n))      out = bf16(bf16(bf16(1 - m) p) + bf16(m l))
+// (a, b) = row *step_idx of `coef` ([rows][2] fp32, bf16-rounded values; last row (1, 0)).  The launch follows the scheduler step,
+// which has advanced the counter: during step i the row read is i + 1.  The row index is clamped to the table.
+// Layout: l / x0 / n [B][C][HW], mask [Bm][1][HW] with Bm in {1, B}.  VEC: eight elements per thread through 16-byte accesses
+// (HW % 8 == 0, 16-byte aligned bases: a group of eight never straddles a (b, c) plane); otherwise one element per thread.
+struct BlendCoef {
+  float a, b;
+};
+
+__device__ __forceinline__ float inpaint_blend_one(const BlendCoef& k, float l, float x0, float n, float m) {
+  const float p = bf2f(f2bf(__fadd_rn(bf2f(f2bf(__fmul_rn(k.a, x0))), bf2f(f2bf(__fmul_rn(k.b, n))))));
+  const float om = bf2f(f2bf(__fsub_rn(1.0f, m)));
+  return __fadd_rn(bf2f(f2bf(__fmul_rn(om, p))), bf2f(f2bf(__fmul_rn(m, l))));
+}
+
+template <bool VEC>
+__global__ __launch_bounds__(256) void inpaint_blend_kernel(uint16_t* __restrict__ lat, const uint16_t* __restrict__ x0,
+                                                            const uint16_t* __restrict__ noise, const uint16_t* __restrict__ mask,
+                                                            const float* __restrict__ coef, const int* __restrict__ step_idx,
+                                                            int n_rows, size_t chw, size_t hw, int mask_per_sample, size_t n) {
+  const int row = min(max(*step_idx, 0), n_rows - 1);
+  BlendCoef k;
+  k.a = coef[2 * row], k.b = coef[2 * row + 1];
+  const size_t tid = (size_t)blockIdx.x * blockDim.x + threadIdx.x, nth = (size_t)gridDim.x * blockDim.x;
+  if (VEC) {
+    for (size_t i = tid * 8; i < n; i += nth * 8) {
+      const size_t b = i / chw, p = i % hw;
+      const uint4 lq = *(const uint4*)(lat + i), xq = *(const uint4*)(x0 + i), nq = *(const uint4*)(noise + i);
+      const uint4 mq = *(const uint4*)(mask + (mask_per_sample ? b * hw : 0) + p);
+      float l[8], x[8], e[8], m[8], o[8];
+      unpack8(lq, l), unpack8(xq, x), unpack8(nq, e), unpack8(mq, m);
+#pragma unroll
+      for (int j = 0; j < 8; ++j) o[j] = inpaint_blend_one(k, l[j], x[j], e[j], m[j]);
+      *(uint4*)(lat + i) = pack8(o);
+    }
+  } else {
+    for (size_t i = tid; i < n; i += nth) {
+      const size_t b = i / chw, p = i % hw;
+      const float m = bf2f(mask[(mask_per_sample ? b * hw : 0) + p]);
+      lat[i] = f2bf(inpaint_blend_one(k, bf2f(lat[i]), bf2f(x0[i]), bf2f(noise[i]), m));
+    }
+  }
+}
+
 __global__ void advance_step_kernel(int* step_idx) { *step_idx += 1; }
 
 // out = x * s in the tensor dtype (latents * init_noise_sigma, pipeline_stable_diffusion.py:713)
@@ -549,6 +598,24 @@ extern "C" int da_cast_f32_bf16(const float* x, void* out, int rep, long long n_
   if (!x || !out || n_ <= 0 || rep <= 0) return DA_ERR_INVALID;
   const size_t n = (size_t)n_;
   DA_LAUNCH(cast_f32_bf16_kernel, ew_grid(n), dim3(256), 0, (hipStream_t)stream, x, (uint16_t*)out, rep, n);
+  DA_CHECK_LAUNCH();
+  return DA_OK;
+}
+
+extern "C" int da_inpaint_blend(void* latents, const void* image_latents, const void* noise, const void* mask, const float* coef,
+                                const int* step_idx, int n_rows, int B, int C, long long HW, int Bm, void* stream) {
+  if (!latents || !image_latents || !noise || !mask || !coef || !step_idx || n_rows <= 0 || B <= 0 || C <= 0 || HW <= 0)
+    return DA_ERR_INVALID;
+  if (Bm != 1 && Bm != B) return DA_ERR_INVALID;
+  const size_t hw = (size_t)HW, chw = (size_t)C * hw, n = (size_t)B * chw;
+  hipStream_t s = (hipStream_t)stream;
+  const bool vec = hw % 8 == 0 && ((uintptr_t)latents | (uintptr_t)image_latents | (uintptr_t)noise | (uintptr_t)mask) % 16 == 0;
+  if (vec)
+    DA_LAUNCH(inpaint_blend_kernel<true>, ew_grid(n / 8), dim3(256), 0, s, (uint16_t*)latents, (const uint16_t*)image_latents,
+              (const uint16_t*)noise, (const uint16_t*)mask, coef, step_idx, n_rows, chw, hw, Bm == B && B > 1 ? 1 : 0, n);
+  else
+    DA_LAUNCH(inpaint_blend_kernel<false>, ew_grid(n), dim3(256), 0, s, (uint16_t*)latents, (const uint16_t*)image_latents,
+              (const uint16_t*)noise, (const uint16_t*)mask, coef, step_idx, n_rows, chw, hw, Bm == B && B > 1 ? 1 : 0, n);
   DA_CHECK_LAUNCH();
   return DA_OK;
 }

@@ -6,8 +6,9 @@ from typing import Optional
 from . import init as dinit
 from .autoencoder_kl import AutoencoderKL
 from .autoencoder_kl_wan import AutoencoderKLWan
-from .pipelines import (DDPMPipeline, FluxPipeline, StableDiffusionImg2ImgPipeline, StableDiffusionPipeline,
-                        StableDiffusionXLImg2ImgPipeline, StableDiffusionXLPipeline, WanPipeline)
+from .pipelines import (DDPMPipeline, FluxPipeline, StableDiffusionImg2ImgPipeline, StableDiffusionInpaintPipeline,
+                        StableDiffusionPipeline, StableDiffusionXLImg2ImgPipeline, StableDiffusionXLInpaintPipeline,
+                        StableDiffusionXLPipeline, WanPipeline)
 from .schedulers import DDPMScheduler
 from .unet_2d import UNet2DModel
 from .transformer_wan import WanTransformer3DModel
@@ -58,29 +59,40 @@ def build_wan_vae(cfg: dict, seed: int = 21, device="cuda", init_device: Optiona
     return vae, state_dict
 
 
+def _inpaint_unet_config(ucfg: dict, unet_in_channels: int) -> dict:
+    if unet_in_channels not in (4, 9):
+        raise ValueError("unet_in_channels: 4 (any checkpoint, mask blend after every step) or 9 (an inpainting U-Net)")
+    return ucfg if unet_in_channels == ucfg.get("in_channels", 4) else dict(ucfg, in_channels=unet_in_channels)
+
+
 def build_sdxl_pipeline(device="cuda", tiny: bool = False, seed: int = 0, init_device: Optional[str] = None,
-                        with_encoder: bool = False, img2img: bool = False):
+                        with_encoder: bool = False, img2img: bool = False, inpaint: bool = False, unet_in_channels: int = 4):
     """SDXL-base (BASELINE config 3) or its tiny sibling.  Full size: weights are generated on ``init_device``
     (default: the HIP device, ~2.6 B parameters in seconds) and freed after packing.  ``with_encoder``: the VAE's encoder as
-    well; ``img2img``: the same components in a StableDiffusionXLImg2ImgPipeline (implies ``with_encoder``)."""
+    well; ``img2img``: the same components in a StableDiffusionXLImg2ImgPipeline, ``inpaint``: in a
+    StableDiffusionXLInpaintPipeline (both imply ``with_encoder``), whose U-Net takes ``unet_in_channels`` = 4 or 9 input channels."""
     ucfg = dinit.TINY_SDXL_UNET if tiny else dinit.SDXL_UNET
+    if inpaint:
+        ucfg = _inpaint_unet_config(ucfg, unet_in_channels)
     vcfg = dinit.TINY_VAE if tiny else dinit.SDXL_VAE
     idev = init_device or ("cpu" if tiny else str(device))
     unet, _ = build_unet(ucfg, seed=seed, device=device, init_device=idev)
-    vae, _ = build_vae(vcfg, seed=seed + 1, device=device, init_device=idev, with_encoder=with_encoder or img2img)
+    vae, _ = build_vae(vcfg, seed=seed + 1, device=device, init_device=idev, with_encoder=with_encoder or img2img or inpaint)
     sch = EulerDiscreteScheduler(**SDXL_SCHEDULER)
-    cls = StableDiffusionXLImg2ImgPipeline if img2img else StableDiffusionXLPipeline
+    cls = StableDiffusionXLInpaintPipeline if inpaint else StableDiffusionXLImg2ImgPipeline if img2img else StableDiffusionXLPipeline
     return cls(vae=vae, unet=unet, scheduler=sch)
 
 
 def build_sd15_pipeline(device="cuda", tiny: bool = False, seed: int = 0, init_device: Optional[str] = None,
-                        with_encoder: bool = False, img2img: bool = False):
+                        with_encoder: bool = False, img2img: bool = False, inpaint: bool = False, unet_in_channels: int = 4):
     ucfg = dinit.TINY_SD15_UNET if tiny else dinit.SD15_UNET
+    if inpaint:
+        ucfg = _inpaint_unet_config(ucfg, unet_in_channels)
     vcfg = dinit.TINY_VAE if tiny else dinit.SD_VAE
     idev = init_device or ("cpu" if tiny else str(device))
     unet, _ = build_unet(ucfg, seed=seed, device=device, init_device=idev)
-    vae, _ = build_vae(vcfg, seed=seed + 1, device=device, init_device=idev, with_encoder=with_encoder or img2img)
-    cls = StableDiffusionImg2ImgPipeline if img2img else StableDiffusionPipeline
+    vae, _ = build_vae(vcfg, seed=seed + 1, device=device, init_device=idev, with_encoder=with_encoder or img2img or inpaint)
+    cls = StableDiffusionInpaintPipeline if inpaint else StableDiffusionImg2ImgPipeline if img2img else StableDiffusionPipeline
     return cls(vae=vae, unet=unet, scheduler=DDIMScheduler(**SD15_SCHEDULER))
 
 

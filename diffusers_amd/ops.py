@@ -1030,6 +1030,29 @@ def advance_step(step_idx: torch.Tensor) -> None:
     L.check(L.load().da_advance_step(step_idx.data_ptr(), _stream()), "da_advance_step")
 
 
+def inpaint_blend_(latents: torch.Tensor, image_latents: torch.Tensor, noise: torch.Tensor, mask: torch.Tensor,
+                   coef: torch.Tensor, step_idx: torch.Tensor) -> torch.Tensor:
+    """IN PLACE mask blend of the inpainting loop (see da_inpaint_blend): latents <- (1 - mask) * add_noise(image_latents, noise)
+    + mask * latents with the add_noise coefficients of row ``*step_idx`` of ``coef`` ([rows][2] fp32, scheduler.add_noise_table).
+    latents / image_latents / noise: bf16 [B][C][...]; mask: bf16 [Bm][1][...], Bm in {1, B}."""
+    _req(latents, "latents"), _req(image_latents, "image_latents"), _req(noise, "noise"), _req(mask, "mask")
+    _req(coef, "coef", torch.float32), _req(step_idx, "step_idx", torch.int32)
+    if latents.dim() < 3 or image_latents.shape != latents.shape or noise.shape != latents.shape:
+        raise ValueError(f"inpaint_blend_: latents {tuple(latents.shape)}, image_latents {tuple(image_latents.shape)} and noise "
+                         f"{tuple(noise.shape)} must have one shape (B, C, ...)")
+    B, C = latents.shape[0], latents.shape[1]
+    hw = latents[0, 0].numel()
+    if mask.dim() != latents.dim() or mask.shape[0] not in (1, B) or mask.shape[1] != 1 or mask[0, 0].numel() != hw:
+        raise ValueError(f"inpaint_blend_: mask {tuple(mask.shape)} must be (1 or {B}, 1, ...) over the latents' {hw} positions")
+    if not all(t.is_contiguous() for t in (latents, image_latents, noise, mask)):
+        raise ValueError("inpaint_blend_: contiguous tensors required")
+    if coef.dim() != 2 or coef.shape[1] != 2 or not coef.is_contiguous():
+        raise ValueError("inpaint_blend_: coef must be a contiguous [rows][2] fp32 tensor")
+    L.check(L.load().da_inpaint_blend(latents.data_ptr(), image_latents.data_ptr(), noise.data_ptr(), mask.data_ptr(), coef.data_ptr(),
+                                      step_idx.data_ptr(), coef.shape[0], B, C, hw, mask.shape[0], _stream()), "da_inpaint_blend")
+    return latents
+
+
 # ----------------------------------------------------------------------------------------------------------------------
 # misc
 # ----------------------------------------------------------------------------------------------------------------------
@@ -1165,6 +1188,41 @@ def conv_thin_in(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor],
     y = torch.empty((B, H, W_, Cout), device=x.device, dtype=bf16)
     L.check(L.load().da_conv_thin_in_bf16(x.data_ptr(), w.data_ptr(), _ptr(bias), y.data_ptr(), B, H, W_, Cin, Cout,
                                           ksize, int(in_nchw), in_div, in_add, _stream()), "da_conv_thin_in_bf16")
+    return y
+
+
+def conv_in_inpaint(x: torch.Tensor, mask: torch.Tensor, masked: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor], *,
+                    table: Optional[torch.Tensor] = None, step_idx: Optional[torch.Tensor] = None, rep: int = 1) -> torch.Tensor:
+    """conv_in of a 9-channel inpainting U-Net from its three sources (see da_conv_in_inpaint): equals
+    ``conv_thin_in(cat([s(x)] * rep, [mask] * rep, [masked] * rep, dim=1), w, bias, ksize=3, in_nchw=True)`` bit for bit, with
+    s = euler_scale_model_input when ``table`` / ``step_idx`` are given.  x: [B][4][H][W]; mask [Bm][1][H][W], masked [Bm][4][H][W],
+    Bm in {1, B}; w: [Cout][81]; returns NHWC [rep * B][H][W][Cout]."""
+    _req(x, "x"), _req(mask, "mask"), _req(masked, "masked_image_latents"), _req(w, "w")
+    if x.dim() != 4 or x.shape[1] != 4:
+        raise ValueError(f"conv_in_inpaint: latents must be (B, 4, H, W), got {tuple(x.shape)}")
+    B, _, H, W_ = x.shape
+    Bm = mask.shape[0]
+    if Bm not in (1, B) or tuple(mask.shape) != (Bm, 1, H, W_) or tuple(masked.shape) != (Bm, 4, H, W_):
+        raise ValueError(f"conv_in_inpaint: mask {tuple(mask.shape)} / masked_image_latents {tuple(masked.shape)} must be "
+                         f"(Bm, 1, {H}, {W_}) / (Bm, 4, {H}, {W_}) with Bm = 1 or {B}")
+    if not (x.is_contiguous() and mask.is_contiguous() and masked.is_contiguous() and w.is_contiguous()):
+        raise ValueError("conv_in_inpaint: contiguous tensors required")
+    if w.dim() != 2 or w.shape[1] != 81:
+        raise ValueError(f"conv_in_inpaint: a 9 -> Cout 3x3 weight [Cout][81] is required, got {tuple(w.shape)}")
+    if rep not in (1, 2):
+        raise ValueError("conv_in_inpaint: rep must be 1 or 2")
+    if (table is None) != (step_idx is None):
+        raise ValueError("conv_in_inpaint: pass `table` and `step_idx` together")
+    if table is not None:
+        _req(table, "table", torch.float32), _req(step_idx, "step_idx", torch.int32)
+    if bias is not None:
+        _req(bias, "bias")
+        if bias.data_ptr() % 16 or bias.numel() != w.shape[0] or not bias.is_contiguous():
+            raise ValueError("conv_in_inpaint: bias must be a contiguous, 16-byte aligned [Cout] tensor")
+    Cout = w.shape[0]
+    y = torch.empty((rep * B, H, W_, Cout), device=x.device, dtype=bf16)
+    L.check(L.load().da_conv_in_inpaint(x.data_ptr(), mask.data_ptr(), masked.data_ptr(), w.data_ptr(), _ptr(bias), y.data_ptr(),
+                                        _ptr(table), _ptr(step_idx), B, H, W_, Cout, rep, Bm, _stream()), "da_conv_in_inpaint")
     return y
 
 

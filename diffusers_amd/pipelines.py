@@ -273,15 +273,20 @@ class _LatentDiffusionBase(_StepCallbacks, PipelineLoadingMixin):
         pass
 
     # ---- the captured step -------------------------------------------------------------------------------------
-    def _step(self, latents, cond, guidance_scale, do_cfg):
+    def _predict_noise(self, latents, cond, do_cfg):
+        """scale_model_input + CFG batch doubling + the U-Net forward of one step."""
         sch = self.scheduler
         rep = 2 if do_cfg else 1
         if isinstance(sch, EulerDiscreteScheduler):
             x_in = sch.scale_model_input(latents, sch.timesteps[0], rep=rep)
         else:
             x_in = ops.mul_scalar(latents, 1.0, rep=rep) if rep > 1 else latents  # DDIM, DPM-Solver++: scale_model_input = identity
-        eps = self.unet(x_in, None, None, conditioning=cond, sampler_table=sch.device_table,
-                        step_idx=sch.device_step, return_dict=False)[0]
+        return self.unet(x_in, None, None, conditioning=cond, sampler_table=sch.device_table,
+                         step_idx=sch.device_step, return_dict=False)[0]
+
+    def _step(self, latents, cond, guidance_scale, do_cfg):
+        sch = self.scheduler
+        eps = self._predict_noise(latents, cond, do_cfg)
         # in place (same buffer every replay); without CFG (guidance_scale <= 1, pipeline_stable_diffusion_xl.py:1202,
         # :1223) the U-Net ran on the un-doubled batch and the same kernel skips the combine
         kw = {"eta": self._eta, "noise_table": self._noise_table} if self._eta > 0 else {}
@@ -844,6 +849,24 @@ class StableDiffusionXLImg2ImgPipeline(_Img2ImgMixin, StableDiffusionXLPipeline)
 class StableDiffusionImg2ImgPipeline(_Img2ImgMixin, StableDiffusionPipeline):
     """pipeline_stable_diffusion_img2img.py (__call__ :860-1132): SD1.5 img2img on the engine (DDIM by default, eta included)."""
 
+    def _set_eta(self, eta, latents, generator, num_inference_steps, n_steps, begin):
+        """DDIM's eta for a loop of ``n_steps`` steps from schedule entry ``begin``: the per-step variance noise, pre-drawn."""
+        dev = self.device
+        self._eta, self._noise_table = float(eta), None
+        if eta > 0:
+            if not hasattr(self.scheduler, "_get_variance"):
+                raise ValueError("eta > 0 is a DDIMScheduler option")
+            # one draw per step that runs, in order (scheduling_ddim.py:500-507), in the rows the device step counter selects
+            gdev = generator.device if generator is not None else dev
+            table = torch.zeros((num_inference_steps,) + tuple(latents.shape), device=dev, dtype=bf16)
+            for i in range(n_steps):
+                table[begin + i] = torch.randn(latents.shape, generator=generator, device=gdev, dtype=bf16).to(dev)
+            if self._static.get("noise_table") is not None and self._static["noise_table"].shape == table.shape:
+                self._static["noise_table"].copy_(table)
+                table = self._static["noise_table"]
+            self._static["noise_table"] = table
+            self._noise_table = table
+
     @torch.no_grad()
     def __call__(self, prompt=None, image=None, strength: float = 0.8, num_inference_steps: int = 50, timesteps=None,
                  sigmas=None, guidance_scale: float = 7.5, negative_prompt=None, num_images_per_prompt: int = 1,
@@ -889,20 +912,379 @@ class StableDiffusionImg2ImgPipeline(_Img2ImgMixin, StableDiffusionPipeline):
         if do_cfg:
             pe = torch.cat([negative_prompt_embeds.to(device=dev, dtype=bf16), pe], dim=0)
         cond = self.unet.precompute_conditioning(pe.contiguous(), None)
-        self._eta, self._noise_table = float(eta), None
-        if eta > 0:
-            if not hasattr(self.scheduler, "_get_variance"):
-                raise ValueError("eta > 0 is a DDIMScheduler option")
-            # one draw per step that runs, in order (scheduling_ddim.py:500-507), in the rows the device step counter selects
-            gdev = generator.device if generator is not None else dev
-            table = torch.zeros((num_inference_steps,) + tuple(latents.shape), device=dev, dtype=bf16)
-            for i in range(n_steps):
-                table[begin + i] = torch.randn(latents.shape, generator=generator, device=gdev, dtype=bf16).to(dev)
-            if self._static.get("noise_table") is not None and self._static["noise_table"].shape == table.shape:
-                self._static["noise_table"].copy_(table)
-                table = self._static["noise_table"]
-            self._static["noise_table"] = table
-            self._noise_table = table
+        self._set_eta(eta, latents, generator, num_inference_steps, n_steps, begin)
+        latents = self._denoise(latents, cond, n_steps, guidance_scale, do_cfg, use_graph, begin=begin)
+        images = self._decode(latents, output_type)
+        if not return_dict:
+            return (images,)
+        return PipelineOutput(images=images)
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# inpainting (pipeline_stable_diffusion_inpaint.py, pipeline_stable_diffusion_xl_inpaint.py)
+# ----------------------------------------------------------------------------------------------------------------------
+def prepare_mask(mask_image, vae_scale_factor: int, device):
+    """``mask_image`` as the reference's mask processor leaves it (VaeImageProcessor(do_normalize=False, do_binarize=True,
+    do_convert_grayscale=True).preprocess): fp32 ``[n][1][H][W]`` of zeros and ones, 1 where ``v >= 0.5`` -- 1 repaints, 0 keeps.
+    Accepted: a torch tensor [H][W], [1][H][W] or [n][1][H][W] in [0, 1]; a numpy array HW, HW1 or nHW1, float in [0, 1] or uint8
+    (read as x / 255); a PIL image (converted to "L", x / 255); a list of one kind.  The engine does not resize: sizes that are not
+    a multiple of the VAE's scale factor are refused, as images are."""
+    if isinstance(mask_image, (list, tuple)):
+        if not mask_image:
+            raise ValueError("`mask_image` is an empty list")
+        return torch.cat([prepare_mask(m, vae_scale_factor, device) for m in mask_image], 0)
+    if torch.is_tensor(mask_image):
+        t = mask_image
+        if t.dim() == 2:
+            t = t[None, None]
+        elif t.dim() == 3:
+            t = t[:, None] if t.shape[0] != 1 else t[None]
+        if t.dim() != 4 or t.shape[1] != 1:
+            raise ValueError(f"`mask_image` tensor must be [H][W], [1][H][W] or [B][1][H][W], got shape {tuple(mask_image.shape)}")
+        v = t.to(torch.float32)
+    elif isinstance(mask_image, np.ndarray):
+        a = mask_image
+        if a.ndim == 2:
+            a = a[None, :, :, None]
+        elif a.ndim == 3:
+            a = a[None] if a.shape[-1] == 1 else a[..., None]
+        if a.ndim != 4 or a.shape[-1] != 1:
+            raise ValueError(f"`mask_image` array must be HW, HW1 or BHW1, got shape {tuple(mask_image.shape)}")
+        v = torch.from_numpy(np.ascontiguousarray(a)).permute(0, 3, 1, 2)
+        v = v.to(torch.float32) / 255.0 if a.dtype == np.uint8 else v.to(torch.float32)
+    elif hasattr(mask_image, "convert"):                    # PIL.Image
+        v = torch.from_numpy(np.array(mask_image.convert("L"))).to(torch.float32)[None, None] / 255.0
+    else:
+        raise ValueError(f"`mask_image` has to be of type `torch.Tensor`, `np.ndarray`, `PIL.Image.Image` or a list of them, "
+                         f"but is {type(mask_image)}")
+    H, W_ = v.shape[-2], v.shape[-1]
+    if H % vae_scale_factor or W_ % vae_scale_factor:
+        raise ValueError(f"`mask_image` is {H} x {W_}: height and width must be multiples of the VAE scale factor {vae_scale_factor} "
+                         "(the engine does not resize masks)")
+    return (v >= 0.5).to(device=device, dtype=torch.float32).contiguous()
+
+
+def _image_normalised(prep, device):
+    """The ("image", tensor, nchw, normalize) of prepare_image as VaeImageProcessor.preprocess returns it: fp32 NCHW in [-1, 1]."""
+    _, t, nchw, normalize = prep
+    x = t.to(device=device, dtype=torch.float32) / 255.0 if t.dtype == torch.uint8 else t.to(device=device, dtype=torch.float32)
+    if not nchw:
+        x = x.permute(0, 3, 1, 2)
+    if normalize:
+        x = 2.0 * x - 1.0
+    return x.contiguous()
+
+
+def _to_batch(t: torch.Tensor, batch: int, what: str) -> torch.Tensor:
+    n = t.shape[0]
+    if n == batch:
+        return t
+    if batch % n:
+        raise ValueError(f"The passed {what} and the required batch size don't match. {what} are supposed to be duplicated to a "
+                         f"total batch size of {batch}, but {n} were passed. Make sure the number of {what} that you pass is "
+                         "divisible by the total requested batch size.")
+    return t.repeat(batch // n, *([1] * (t.dim() - 1)))
+
+
+class _InpaintMixin:
+    """The inpainting pipelines on top of the img2img ones.  A 4-channel U-Net (any SD / SDXL checkpoint) runs the img2img step and
+    re-imposes the known region after it -- scheduler.add_noise of the image latents at the next timestep, blended through the mask,
+    ONE launch (ops.inpaint_blend_) that reads its coefficients with the device step counter, so the step stays graph-replayable.  A
+    9-channel inpainting U-Net gets mask and masked-image latents as extra input channels every step: its conv_in reads them in place
+    (ops.conv_in_inpaint, the Euler scale_model_input and the CFG doubling folded in) and nothing is blended.  Not done here, as in
+    the reference without ``padding_mask_crop``: the original pixels are not pasted over the result."""
+
+    _inpaint = None        # static inputs of the captured step: mask, image_latents, noise, masked (9-channel only), table
+
+    def _check_inpaint_unet(self, masked_channels: int = 4):
+        nu, lat = self.unet.config.in_channels, self.vae.config.latent_channels
+        if nu == 9:
+            total = lat + 1 + masked_channels
+            if total != nu:
+                raise ValueError(f"Incorrect configuration settings! The config of `pipeline.unet`: {self.unet.config} expects "
+                                 f"{nu} but received `num_channels_latents`: {lat} + `num_channels_mask`: 1 + "
+                                 f"`num_channels_masked_image`: {masked_channels} = {total}. Please verify the config of "
+                                 "`pipeline.unet` or your `mask_image` or `image` input.")
+        elif nu != 4:
+            raise ValueError(f"The unet {self.unet.__class__} should have either 4 or 9 input channels, not {nu}.")
+        if lat != 4:
+            raise NotImplementedError("the inpainting engine pipelines run 4-channel latents (the SD / SDXL VAE)")
+        return nu
+
+    def _encode_scaled(self, img, generator, noise_dtype):
+        """_encode_vae_image: retrieve_latents(vae.encode(image), generator) * scaling_factor, for an fp32 NCHW image in [-1, 1]."""
+        vc = self.vae.config
+        dist = self.vae.encode_image(img, nchw=True, normalize=False)
+        return dist.latents(dist.draw_noise(generator, dtype=noise_dtype), scale=float(vc.scaling_factor))
+
+    def _inpaint_prepare(self, image, mask_image, masked_image_latents, height, width, latents, timestep, batch: int, generator,
+                         strength: float, add_noise: bool, noise_dtype, padding_mask_crop=None):
+        """prepare_latents + prepare_mask_latents of the inpainting pipelines.  Draws on ``generator``, in the reference's order: the
+        posterior noise of ``image``, ``noise``, the posterior noise of the masked image (9-channel U-Net only: with 4 channels the
+        reference's masked-image latents are never used, and the engine does not encode them).  Returns the loop's start latents and
+        leaves the step's static inputs in ``self._inpaint``."""
+        if padding_mask_crop is not None:
+            raise NotImplementedError("`padding_mask_crop` (crop, resize and paste-back) is not implemented by the engine pipelines")
+        if mask_image is None:
+            raise ValueError("`mask_image` input cannot be undefined.")
+        vc = self.vae.config
+        if vc.get("latents_mean") is not None or vc.get("latents_std") is not None:
+            raise NotImplementedError("AutoencoderKL configs with latents_mean / latents_std are not supported by the engine "
+                                      "pipelines")
+        dev, f = self.device, self.vae_scale_factor
+        nu = self._check_inpaint_unet(4 if masked_image_latents is None else int(masked_image_latents.shape[1]))
+        prep = prepare_image(image, f, vc.latent_channels, dev)
+        if prep[0] == "latents":
+            img = None
+            image_latents = prep[1].clone()
+            H, W_ = image_latents.shape[-2] * f, image_latents.shape[-1] * f
+        else:
+            img = _image_normalised(prep, dev)
+            H, W_ = img.shape[-2], img.shape[-1]
+        if (height is not None and height != H) or (width is not None and width != W_):
+            raise ValueError(f"`height` x `width` = {height} x {width} but `image` is {H} x {W_} (the engine does not resize)")
+        mask = prepare_mask(mask_image, f, dev)
+        if tuple(mask.shape[-2:]) != (H, W_):
+            raise ValueError(f"`mask_image` is {mask.shape[-2]} x {mask.shape[-1]} but `image` is {H} x {W_} (the engine does not "
+                             "resize masks)")
+        is_strength_max = strength == 1.0
+        # (1) image latents
+        if img is not None:
+            if isinstance(generator, (list, tuple)) and img.shape[0] < batch and batch % img.shape[0] == 0:
+                img = torch.cat([img] * (batch // img.shape[0]), 0)
+            image_latents = self._encode_scaled(img, generator, noise_dtype)
+        image_latents = _to_batch(image_latents, batch, "images").contiguous()
+        shape = tuple(image_latents.shape)
+        # (2) noise and the start of the loop
+        if latents is None and add_noise:
+            noise = _randn(shape, generator, dev, bf16)
+            if is_strength_max:
+                start = ops.mul_scalar(noise, float(self.scheduler.init_noise_sigma))
+            else:
+                start = self.scheduler.add_noise(image_latents, noise, timestep)
+        elif add_noise:
+            # (the reference takes supplied latents as the noise and starts from noise * init_noise_sigma whatever the strength)
+            noise = latents.to(device=dev, dtype=bf16).contiguous().clone()      # (kept as a static input of the step: never the caller's tensor)
+            if tuple(noise.shape) != shape:
+                raise ValueError(f"`latents` has shape {tuple(noise.shape)}, expected {shape}")
+            start = ops.mul_scalar(noise, float(self.scheduler.init_noise_sigma))
+        else:
+            noise = _randn(shape, generator, dev, bf16)
+            start = image_latents.clone()
+        # mask at latent resolution: F.interpolate's default (nearest) picks m[f i][f j]
+        mask_lat = torch.nn.functional.interpolate(mask, size=(H // f, W_ // f)).to(bf16)
+        masked = None
+        if nu == 9:
+            # (3) masked-image latents
+            if masked_image_latents is not None:
+                masked = masked_image_latents.to(device=dev, dtype=bf16)
+            else:
+                if img is None:
+                    raise ValueError("a 9-channel inpainting U-Net needs `image` as pixels (or `masked_image_latents`): the masked "
+                                     "image cannot be formed from latents")
+                n = max(mask.shape[0], img.shape[0])
+                masked_image = _to_batch(img, n, "images") * (_to_batch(mask, n, "masks") < 0.5)
+                masked = self._encode_scaled(masked_image.contiguous(), generator, noise_dtype)
+            if tuple(masked.shape[-2:]) != shape[-2:]:
+                raise ValueError(f"`masked_image_latents` is {tuple(masked.shape)}, the latents are {shape}")
+        # batch: one mask (and one masked image) is broadcast by the kernels; anything else is repeated to the batch
+        if masked is not None and (mask_lat.shape[0] != 1 or masked.shape[0] != 1):
+            mask_lat, masked = _to_batch(mask_lat, batch, "masks"), _to_batch(masked, batch, "images")
+        elif mask_lat.shape[0] != 1:
+            mask_lat = _to_batch(mask_lat, batch, "masks")
+        new = {"mask": mask_lat.contiguous(), "image_latents": image_latents, "noise": noise.contiguous(),
+               "masked": masked.contiguous() if masked is not None else None}
+        old = self._inpaint
+        if old is not None and all((old[k] is None) == (v is None) and (v is None or (old[k].shape == v.shape and old[k].device == v.device))
+                                   for k, v in new.items()):
+            for k, v in new.items():           # same shapes: refresh the captured step's static inputs in place (no re-capture)
+                if v is not None:
+                    old[k].copy_(v)
+        else:
+            old = self._inpaint = new
+        old["table"] = self.scheduler.add_noise_table(bf16) if nu == 4 else None
+        return start.contiguous()
+
+    def _predict_noise(self, latents, cond, do_cfg):
+        st = self._inpaint
+        if st is None or st["masked"] is None:
+            return super()._predict_noise(latents, cond, do_cfg)
+        sch = self.scheduler
+        euler = isinstance(sch, EulerDiscreteScheduler)
+        if euler:
+            if sch._step_index is None:
+                sch._init_step_index(sch.timesteps[0])
+            sch.is_scale_input_called = True
+        return self.unet(latents, None, None, conditioning=cond, sampler_table=sch.device_table, step_idx=sch.device_step,
+                         inpaint_cond=(st["mask"], st["masked"]), scale_model_input=euler, return_dict=False)[0]
+
+    def _step(self, latents, cond, guidance_scale, do_cfg):
+        super()._step(latents, cond, guidance_scale, do_cfg)
+        st = self._inpaint
+        if st is not None and st["masked"] is None:
+            ops.inpaint_blend_(latents, st["image_latents"], st["noise"], st["mask"], st["table"], self.scheduler.device_step)
+        return latents
+
+    def _make_graph_key(self, latents, cond, guidance_scale, do_cfg):
+        st = self._inpaint or {}
+        return super()._make_graph_key(latents, cond, guidance_scale, do_cfg) + tuple(
+            (k, st[k].data_ptr(), tuple(st[k].shape)) if st.get(k) is not None else (k, 0, ())
+            for k in ("mask", "image_latents", "noise", "masked", "table"))
+
+
+class StableDiffusionInpaintPipeline(_InpaintMixin, StableDiffusionImg2ImgPipeline):
+    """pipeline_stable_diffusion_inpaint.py: SD1.5 inpainting on the engine, 4-channel and 9-channel U-Nets (see _InpaintMixin)."""
+
+    @torch.no_grad()
+    def __call__(self, prompt=None, image=None, mask_image=None, masked_image_latents=None, height: Optional[int] = None,
+                 width: Optional[int] = None, padding_mask_crop=None, strength: float = 1.0, num_inference_steps: int = 50,
+                 timesteps=None, sigmas=None, guidance_scale: float = 7.5, negative_prompt=None, num_images_per_prompt: int = 1,
+                 eta: float = 0.0, generator=None, latents: Optional[torch.Tensor] = None, prompt_embeds=None,
+                 negative_prompt_embeds=None, ip_adapter_image=None, ip_adapter_image_embeds=None, output_type: str = "pt",
+                 return_dict: bool = True, clip_skip=None, guidance_rescale: float = 0.0, callback_on_step_end=None,
+                 callback_on_step_end_tensor_inputs=None, use_graph: bool = True):
+        _check_strength(strength)
+        if image is None:
+            raise ValueError("`image` input cannot be undefined.")
+        if ip_adapter_image is not None or ip_adapter_image_embeds is not None:
+            raise NotImplementedError("`ip_adapter_image` / `ip_adapter_image_embeds`: IP-Adapter is outside this engine")
+        if eta < 0.0 or eta > 1.0:
+            raise ValueError("eta (DDIM) must be in [0, 1]")
+        self._guidance_rescale = float(guidance_rescale)
+        self._arm_callback(callback_on_step_end, callback_on_step_end_tensor_inputs)
+        do_cfg = guidance_scale > 1.0
+        if prompt is not None:
+            if prompt_embeds is not None:
+                raise ValueError("Cannot forward both `prompt` and `prompt_embeds`. Please make sure to only forward one "
+                                 "of the two.")
+            prompt_embeds, negative_prompt_embeds = self.encode_prompt(prompt, self.device, num_images_per_prompt, do_cfg,
+                                                                        negative_prompt, clip_skip)
+        else:
+            prompt_embeds, negative_prompt_embeds = (_per_prompt(t, num_images_per_prompt) for t in (prompt_embeds, negative_prompt_embeds))
+        if prompt_embeds is None:
+            raise ValueError("Provide either `prompt` (with the text encoder given to the pipeline) or `prompt_embeds`.")
+        if do_cfg and negative_prompt_embeds is None:
+            raise ValueError("classifier-free guidance needs `negative_prompt_embeds`")
+        dev = self.device
+        B = prompt_embeds.shape[0]
+        if timesteps is not None or sigmas is not None:
+            if not isinstance(self.scheduler, EulerDiscreteScheduler):
+                raise ValueError(f"The current scheduler class {type(self.scheduler)}'s `set_timesteps` does not support custom "
+                                 "timestep or sigma schedules. Please check whether you are using the correct scheduler.")
+            self.scheduler.set_timesteps(timesteps=timesteps, sigmas=sigmas, device=dev)
+        else:
+            self.scheduler.set_timesteps(num_inference_steps, device=dev)
+        num_inference_steps = len(self.scheduler.timesteps)
+        ts, n_steps, begin = get_timesteps(self.scheduler, num_inference_steps, strength)
+        _no_steps(strength, n_steps)
+        latent_timestep = ts[:1].repeat(B)
+        # (no upcast in this pipeline: the posterior noise is drawn in the VAE's dtype)
+        latents = self._inpaint_prepare(image, mask_image, masked_image_latents, height, width, latents, latent_timestep, B,
+                                        generator, strength, True, bf16, padding_mask_crop)
+        pe = prompt_embeds.to(device=dev, dtype=bf16)
+        if do_cfg:
+            pe = torch.cat([negative_prompt_embeds.to(device=dev, dtype=bf16), pe], dim=0)
+        cond = self.unet.precompute_conditioning(pe.contiguous(), None)
+        self._set_eta(eta, latents, generator, num_inference_steps, n_steps, begin)
+        latents = self._denoise(latents, cond, n_steps, guidance_scale, do_cfg, use_graph, begin=begin)
+        images = self._decode(latents, output_type)
+        if not return_dict:
+            return (images,)
+        return PipelineOutput(images=images)
+
+
+class StableDiffusionXLInpaintPipeline(_InpaintMixin, StableDiffusionXLImg2ImgPipeline):
+    """pipeline_stable_diffusion_xl_inpaint.py: SDXL inpainting on the engine, 4-channel and 9-channel U-Nets (see _InpaintMixin);
+    ``denoising_start`` / ``denoising_end`` as in the img2img pipeline."""
+
+    @torch.no_grad()
+    def __call__(self, prompt=None, prompt_2=None, image=None, mask_image=None, masked_image_latents=None,
+                 height: Optional[int] = None, width: Optional[int] = None, padding_mask_crop=None, strength: float = 0.9999,
+                 num_inference_steps: int = 50, timesteps=None, sigmas=None, denoising_start: Optional[float] = None,
+                 denoising_end: Optional[float] = None, guidance_scale: float = 7.5, negative_prompt=None, negative_prompt_2=None,
+                 num_images_per_prompt: int = 1, eta: float = 0.0, generator=None, latents: Optional[torch.Tensor] = None,
+                 prompt_embeds=None, negative_prompt_embeds=None, pooled_prompt_embeds=None, negative_pooled_prompt_embeds=None,
+                 ip_adapter_image=None, ip_adapter_image_embeds=None, output_type: str = "pt", return_dict: bool = True,
+                 guidance_rescale: float = 0.0, original_size: Optional[Tuple[int, int]] = None,
+                 crops_coords_top_left: Tuple[int, int] = (0, 0), target_size: Optional[Tuple[int, int]] = None,
+                 negative_original_size: Optional[Tuple[int, int]] = None, negative_crops_coords_top_left: Tuple[int, int] = (0, 0),
+                 negative_target_size: Optional[Tuple[int, int]] = None, aesthetic_score: float = 6.0,
+                 negative_aesthetic_score: float = 2.5, clip_skip=None, callback_on_step_end=None,
+                 callback_on_step_end_tensor_inputs=None, use_graph: bool = True):
+        _check_strength(strength)
+        if image is None:
+            raise ValueError("`image` input cannot be undefined.")
+        if ip_adapter_image is not None or ip_adapter_image_embeds is not None:
+            raise NotImplementedError("`ip_adapter_image` / `ip_adapter_image_embeds`: IP-Adapter is outside this engine")
+        if eta != 0.0:
+            raise NotImplementedError("eta applies to DDIM; the SDXL inpainting engine pipeline runs the Euler scheduler")
+        if (denoising_end is not None and denoising_start is not None and _denoising_value_valid(denoising_end)
+                and _denoising_value_valid(denoising_start) and denoising_start >= denoising_end):
+            raise ValueError(f"`denoising_start`: {denoising_start} cannot be larger than or equal to `denoising_end`: "
+                             f"{denoising_end} when using type float.")
+        if timesteps is not None and sigmas is not None:
+            raise ValueError("Only one of `timesteps` or `sigmas` can be passed. Please choose one to set custom values")
+        do_cfg = guidance_scale > 1.0
+        self._guidance_rescale = float(guidance_rescale)
+        self._arm_callback(callback_on_step_end, callback_on_step_end_tensor_inputs)
+        if prompt is not None:
+            if prompt_embeds is not None:
+                raise ValueError("Cannot forward both `prompt` and `prompt_embeds`. Please make sure to only forward one "
+                                 "of the two.")
+            prompt_embeds, negative_prompt_embeds, pooled_prompt_embeds, negative_pooled_prompt_embeds = \
+                self.encode_prompt(prompt, prompt_2, self.device, num_images_per_prompt, do_cfg, negative_prompt,
+                                   negative_prompt_2, clip_skip)
+        else:
+            prompt_embeds, negative_prompt_embeds, pooled_prompt_embeds, negative_pooled_prompt_embeds = (
+                _per_prompt(t, num_images_per_prompt) for t in (prompt_embeds, negative_prompt_embeds, pooled_prompt_embeds,
+                                                                negative_pooled_prompt_embeds))
+        if prompt_embeds is None or pooled_prompt_embeds is None:
+            raise ValueError("Provide either `prompt` (with the text encoders given to the pipeline) or `prompt_embeds` "
+                             "and `pooled_prompt_embeds`.")
+        if do_cfg and (negative_prompt_embeds is None or negative_pooled_prompt_embeds is None):
+            raise ValueError("classifier-free guidance needs `negative_prompt_embeds` and "
+                             "`negative_pooled_prompt_embeds`")
+        dev = self.device
+        B = prompt_embeds.shape[0]
+        _refuse_custom_schedule(self.scheduler, timesteps, sigmas)
+        if timesteps is not None:
+            self.scheduler.set_timesteps(timesteps=timesteps, device=dev)
+        elif sigmas is not None:
+            self.scheduler.set_timesteps(sigmas=sigmas, device=dev)
+        else:
+            self.scheduler.set_timesteps(num_inference_steps, device=dev)
+        num_inference_steps = len(self.scheduler.timesteps)
+        ts, n_steps, begin = get_timesteps(self.scheduler, num_inference_steps, strength,
+                                           denoising_start if _denoising_value_valid(denoising_start) else None)
+        _no_steps(strength, n_steps)
+        latent_timestep = ts[:1].repeat(B)
+        add_noise = not _denoising_value_valid(denoising_start)
+        # the reference's upcast path (force_upcast): the posterior noise is drawn in fp32
+        latents = self._inpaint_prepare(image, mask_image, masked_image_latents, height, width, latents, latent_timestep, B,
+                                        generator, strength, add_noise, torch.float32 if self.vae.config.force_upcast else bf16,
+                                        padding_mask_crop)
+        if latents.shape[0] != B:
+            raise ValueError(f"`latents` holds {latents.shape[0]} samples, the prompt embeddings (x num_images_per_prompt) {B}")
+        if _denoising_value_valid(denoising_end):
+            cutoff = int(round(self.scheduler.config.num_train_timesteps - denoising_end * self.scheduler.config.num_train_timesteps))
+            n_steps = len([t for t in ts.tolist() if t >= cutoff])
+        height, width = latents.shape[-2] * self.vae_scale_factor, latents.shape[-1] * self.vae_scale_factor
+        original_size = original_size or (height, width)
+        target_size = target_size or (height, width)
+        negative_original_size = negative_original_size or original_size
+        negative_target_size = negative_target_size or target_size
+        pe = prompt_embeds.to(device=dev, dtype=bf16)
+        te = pooled_prompt_embeds.to(device=dev, dtype=bf16)
+        ids, neg_ids = self._get_add_time_ids(original_size, tuple(crops_coords_top_left), target_size, aesthetic_score,
+                                              negative_aesthetic_score, negative_original_size,
+                                              tuple(negative_crops_coords_top_left), negative_target_size,
+                                              text_encoder_projection_dim=int(te.shape[-1]))
+        ids = ids.to(dev).repeat(B, 1)
+        if do_cfg:
+            pe = torch.cat([negative_prompt_embeds.to(device=dev, dtype=bf16), pe], dim=0)
+            te = torch.cat([negative_pooled_prompt_embeds.to(device=dev, dtype=bf16), te], dim=0)
+            ids = torch.cat([neg_ids.to(dev).repeat(B, 1), ids], dim=0)
+        cond = self.unet.precompute_conditioning(pe.contiguous(), {"text_embeds": te, "time_ids": ids})
         latents = self._denoise(latents, cond, n_steps, guidance_scale, do_cfg, use_graph, begin=begin)
         images = self._decode(latents, output_type)
         if not return_dict:

@@ -112,6 +112,33 @@ class _SchedulerBase:
             return ops.add_noise(original_samples, noise, a[0], b[0])
         return torch.cat([ops.add_noise(original_samples[i:i + 1], noise[i:i + 1], a[i], b[i]) for i in range(B)], 0)
 
+    def add_noise_table(self, dtype=torch.bfloat16) -> torch.Tensor:
+        """Engine extension: the ``add_noise`` coefficients of every step of the current schedule as a device table, fp32
+        [n_steps + 1][2].  Row ``j`` = the (a, b) of ``_add_noise_coeffs(timesteps[j], dtype)`` with the scheduler standing at step
+        ``j`` of a loop with a begin index -- what the inpainting loop's ``add_noise(image_latents, noise, timesteps[i + 1])`` uses
+        after step ``i`` -- and the last row is (1, 0): the clean latents after the final step.  ops.inpaint_blend_ picks its row with
+        the device step counter.  Refreshed IN PLACE while the schedule length is unchanged (like the step table), so captured
+        graphs keep the address."""
+        n = len(self.timesteps)
+        rows = np.zeros((n + 1, 2), dtype=np.float32)
+        keep = (self._begin_index, self._step_index)
+        try:
+            self._begin_index = 0
+            for j in range(n):
+                self._step_index = j
+                a, b = self._add_noise_coeffs(self.timesteps[j:j + 1], dtype)
+                rows[j] = a[0], b[0]
+        finally:
+            self._begin_index, self._step_index = keep
+        rows[n] = 1.0, 0.0
+        host = torch.from_numpy(rows)
+        dev = self.timesteps.device
+        old = getattr(self, "_noise_coef", None)
+        if old is not None and old.device == dev and tuple(old.shape) == tuple(host.shape):
+            old.copy_(host)
+        else:
+            self._noise_coef = host.to(dev)
+        return self._noise_coef
 
     def index_for_timestep(self, timestep, schedule_timesteps=None):
         ts = self._timesteps_host if schedule_timesteps is None else np.asarray(schedule_timesteps.cpu())

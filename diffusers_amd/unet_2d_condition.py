@@ -274,10 +274,16 @@ class UNet2DConditionModel(PretrainedMixin):
                 timestep_cond=None, attention_mask=None, cross_attention_kwargs=None, added_cond_kwargs=None,
                 down_block_additional_residuals=None, mid_block_additional_residual=None,
                 down_intrablock_additional_residuals=None, encoder_attention_mask=None, return_dict: bool = True,
-                conditioning: Optional[Dict[str, Any]] = None, sampler_table=None, step_idx=None):
-        """Same signature as the reference forward (unet_2d_condition.py:979-994) plus two engine extensions:
-        ``conditioning`` (result of :meth:`precompute_conditioning`) and ``sampler_table``/``step_idx`` (read the
-        timestep from the device-resident sampler table so the call is HIP-graph replayable).
+                conditioning: Optional[Dict[str, Any]] = None, sampler_table=None, step_idx=None, inpaint_cond=None,
+                scale_model_input: bool = False):
+        """Same signature as the reference forward (unet_2d_condition.py:979-994) plus engine extensions:
+        ``conditioning`` (result of :meth:`precompute_conditioning`), ``sampler_table``/``step_idx`` (read the
+        timestep from the device-resident sampler table so the call is HIP-graph replayable) and, for a 9-channel inpainting
+        U-Net, ``inpaint_cond=(mask, masked_image_latents)``: ``sample`` is then the 4-channel, un-doubled latents, and conv_in reads
+        its nine input channels from the three tensors (ops.conv_in_inpaint; the CFG halves are stored from one computation, their
+        count taken from the conditioning batch).  ``scale_model_input`` (with ``inpaint_cond`` and ``sampler_table``) applies the
+        Euler scheduler's ``scale_model_input`` to the latents inside that conv.  Without ``inpaint_cond`` a 9-channel ``sample``
+        goes through the ordinary conv_in.
 
         Handled like the reference: ``encoder_attention_mask`` (key-padding mask of the text tokens, :1071-1073, through the
         masked flash kernel), ``down_block_additional_residuals`` / ``mid_block_additional_residual`` (ControlNet, :1178-1222:
@@ -310,6 +316,18 @@ class UNet2DConditionModel(PretrainedMixin):
             conditioning = self._cached_conditioning(encoder_hidden_states, added_cond_kwargs, encoder_attention_mask)
         elif encoder_attention_mask is not None:
             raise ValueError("pass encoder_attention_mask to precompute_conditioning() when `conditioning` is given")
+        if inpaint_cond is not None:
+            if c.in_channels != 9 or Cin != 4:
+                raise ValueError(f"`inpaint_cond` is for a U-Net with 9 input channels fed 4-channel latents (this one has "
+                                 f"{c.in_channels}, `sample` has {Cin})")
+            if scale_model_input and sampler_table is None:
+                raise ValueError("`scale_model_input` reads the sampler table: pass `sampler_table` / `step_idx`")
+            rep = conditioning["batch"] // B
+            if rep not in (1, 2) or rep * B != conditioning["batch"]:
+                raise ValueError("conditioning batch must be the latents' batch, or twice it (classifier-free guidance)")
+            B = rep * B
+        elif scale_model_input:
+            raise ValueError("`scale_model_input` is an option of `inpaint_cond`")
         if conditioning["batch"] != B:
             raise ValueError("conditioning batch does not match sample batch")
         kvs = conditioning["kvs"]
@@ -330,7 +348,12 @@ class UNet2DConditionModel(PretrainedMixin):
         emb = self.time_proj(emb)                    # the resnets below take their columns of this
 
         # 2. conv_in: NCHW -> channels-last
-        x = ops.conv_thin_in(sample.contiguous(), self.conv_in_w, self.conv_in_b, ksize=3, in_nchw=True)
+        if inpaint_cond is not None:
+            x = ops.conv_in_inpaint(sample.contiguous(), inpaint_cond[0], inpaint_cond[1], self.conv_in_w, self.conv_in_b,
+                                    table=sampler_table if scale_model_input else None,
+                                    step_idx=step_idx if scale_model_input else None, rep=rep)
+        else:
+            x = ops.conv_thin_in(sample.contiguous(), self.conv_in_w, self.conv_in_b, ksize=3, in_nchw=True)
 
         # 3. down
         ki = 0

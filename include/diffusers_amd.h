@@ -99,8 +99,9 @@ extern "C" {
  * built against an older header would pass shorter structs and the library would read garbage for the new members
  * (da_gemm_params.vt is a STORE address).  History: 1 = rounds 1-3; 4 = round 4 (da_gemm_params.vt / vt_col0 / ld_vt,
  * da_attention_params.algo); 5 = round 5; 6 = round 6 (da_attention_params.split_ws / split_ws_bytes / kv_split; da_groupnorm_nhwc_bf16 takes `sync`);
- * 7 = this header (da_dpmpp_2m_step, DA_FN_DPMPP_2M_STEP). */
-#define DA_ABI_VERSION 7
+ * 7 = da_dpmpp_2m_step, DA_FN_DPMPP_2M_STEP; 8 = this header (da_inpaint_blend, da_conv_in_inpaint; their DA_FN_* numbers are 32 and 33 and
+ * DA_FN_DPMPP_2M_STEP moved from 32 to 34: plan files written under version 7 are not valid under version 8). */
+#define DA_ABI_VERSION 8
 int da_version(void);
 size_t da_sizeof_gemm_params(void);
 size_t da_sizeof_attention_params(void);
@@ -442,6 +443,16 @@ int da_unipc_flow_step(const void* v, void* x, void* last, void* m1, void* m2, c
 int da_dpmpp_2m_step(const void* eps, void* x, float* m1, const float* table, const int* step_idx, const int* begin_idx,
                      int cfg, float guidance, long long n, int x_dtype, int e_dtype, int pred_type, void* stream);
 int da_advance_step(int* step_idx, void* stream);
+/* da_inpaint_blend: the per-step mask blend of the inpainting pipelines with a 4-channel U-Net
+ * (pipeline_stable_diffusion_inpaint.py, pipeline_stable_diffusion_xl_inpaint.py: `num_channels_unet == 4`), in place over latents:
+ *   p = bf16(bf16(a x0) + bf16(b noise))          scheduler.add_noise(image_latents, noise, timesteps[i + 1])
+ *   latents = bf16(bf16(bf16(1 - m) p) + bf16(m latents))
+ * latents / image_latents (x0) / noise: bf16 [B][C][HW]; mask: bf16 [Bm][1][HW], Bm in {1, B}, broadcast over the channels (and the
+ * batch when Bm == 1).  (a, b) = row *step_idx of coef, fp32 [n_rows][2] holding bf16-rounded values, last row (1, 0): launched after
+ * the scheduler step has advanced the counter, step i reads row i + 1 -- the noise level of the next timestep, the clean image latents
+ * after the last step.  The row index is clamped to [0, n_rows).  16-byte accesses where HW % 8 == 0 and the bases are aligned. */
+int da_inpaint_blend(void* latents, const void* image_latents, const void* noise, const void* mask, const float* coef,
+                     const int* step_idx, int n_rows, int B, int C, long long HW, int Bm, void* stream);
 /* rescale_noise_cfg (pipelines/stable_diffusion/pipeline_stable_diffusion.py:69-92; SDXL :1227-1229, SD :1057-1059): eps
  * [2][B][n_per] = (uncond, cond) -> out [B][n_per] = guidance_rescale * (cfg * std(text) / std(cfg)) + (1 - guidance_rescale) * cfg
  * with cfg = uncond + guidance * (cond - uncond), every torch op rounded in the tensor dtype; ratio_ws: B floats of scratch.
@@ -508,6 +519,13 @@ int da_conv_thin_in_bf16(const void* x, const void* w, const void* bias, void* y
                          int ksize, int in_nchw, float in_div, float in_add, void* stream);
 int da_conv_thin_out_bf16(const void* x, const void* w, const void* bias, void* y, int B, int H, int W, int Cin,
                           int Cout, int out_f32, void* stream);
+/* conv_in of a 9-channel inpainting U-Net from its three sources, nothing concatenated: da_conv_thin_in_bf16 (3x3, pad 1, Cin = 9, NCHW
+ * in, NHWC out, w [Cout][81]) on cat([s(x)] * rep, [mask] * rep, [masked] * rep, dim=1), bit for bit.  x: bf16 [B][4][H][W] (the un-doubled
+ * latents), mask [Bm][1][H][W], masked [Bm][4][H][W], Bm in {1, B}; s(x) = bf16(x / table[*step_idx][3]) (da_euler_scale_model_input)
+ * when table != NULL, else x; rep in {1, 2}: y [rep * B][H][W][Cout], the CFG halves computed once and stored twice.  bias NULL or
+ * 16-byte aligned, Cout % 8 == 0. */
+int da_conv_in_inpaint(const void* x, const void* mask, const void* masked, const void* w, const void* bias, void* y,
+                       const float* table, const int* step_idx, int B, int H, int W, int Cout, int rep, int Bm, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------------
  * The two ends of the VAE encoder (AutoencoderKL.encode, autoencoder_kl.py:146-185; Encoder.forward, vae.py:140-184) and
@@ -598,8 +616,10 @@ int da_vae_posterior_latents(const void* in, long long sB, long long sC, long lo
 #define DA_FN_LINEAR_SMALL_M 29           /* da_linear_small_m_bf16 */
 #define DA_FN_CONV_THIN_IN 30             /* da_conv_thin_in_bf16 */
 #define DA_FN_CONV_THIN_OUT 31            /* da_conv_thin_out_bf16 */
-#define DA_FN_DPMPP_2M_STEP 32            /* da_dpmpp_2m_step */
-#define DA_FN_COUNT 33
+#define DA_FN_INPAINT_BLEND 32            /* da_inpaint_blend */
+#define DA_FN_CONV_IN_INPAINT 33          /* da_conv_in_inpaint */
+#define DA_FN_DPMPP_2M_STEP 34            /* da_dpmpp_2m_step */
+#define DA_FN_COUNT 35
 #define DA_PLAN_MAX_ARGS 16
 
 typedef struct da_plan_op {
