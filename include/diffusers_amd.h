@@ -282,6 +282,7 @@ int da_gemm_tune(const da_gemm_params* p, const da_gemm_params* pair, void* stre
  *   vt  element (b, s, h, d) at vt + (h*D + d)*vt_ld + b*vt_batch_stride + s        (V transposed: keys contiguous)
  *   out element (b, s, h, d) at out + b*o_batch_stride + s*o_row_stride + h*D + d
  *   Skv = number of keys attended; Skv_alloc (multiple of 8, >= Skv) = keys present in memory per batch.
+ *   Keys [Skv, Skv_alloc) of K and V^T may hold any finite value and do not influence the result.
  *   D in {64, 96, 128, 160} (SD1.5's head dims 40 / 80 are zero-padded to 64 / 96 by the host-side weight packing).
  *   All strides in elements, multiples of 8 (o: 4).
  * ------------------------------------------------------------------------------------------------------------------ */
