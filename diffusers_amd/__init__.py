@@ -27,6 +27,7 @@ _EXPORTS = {
     "FlowMatchEulerDiscreteScheduler": "schedulers",
     "UniPCMultistepScheduler": "schedulers",
     "DPMSolverMultistepScheduler": "schedulers",
+    "EulerAncestralDiscreteScheduler": "schedulers",
     "StableDiffusionPipeline": "pipelines",
     "StableDiffusionXLPipeline": "pipelines",
     "StableDiffusionImg2ImgPipeline": "pipelines",

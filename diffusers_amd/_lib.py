@@ -86,7 +86,8 @@ FN_IDS = {name: i + 1 for i, name in enumerate((
     "da_mul_scalar", "da_bcast_add_f32", "da_patchify3d_bf16", "da_unpatchify3d_bf16", "da_transpose_bf16",
     "da_nhwc_take_nchw_bf16", "da_nhwc_take_postprocess", "da_permute_0213_bf16", "da_image_postprocess",
     "da_frames_to_ncthw_bf16", "da_timestep_embedding", "da_linear_small_m_bf16", "da_conv_thin_in_bf16",
-    "da_conv_thin_out_bf16", "da_inpaint_blend", "da_conv_in_inpaint", "da_dpmpp_2m_step"))}
+    "da_conv_thin_out_bf16", "da_inpaint_blend", "da_conv_in_inpaint", "da_euler_ancestral_step",
+    "da_dpmpp_2m_step"))}
 FN_COUNT = len(FN_IDS) + 1
 
 
@@ -124,6 +125,7 @@ SIGNATURES = {
     "da_euler_scale_model_input": (_i, [_vp, _vp, _vp, _vp, _i, _ll, _i, _vp]),
     "da_euler_step": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _f, _ll, _i, _i, _vp]),
     "da_x0_linear_step": (_i, [_vp, _vp, _vp, _ll, _vp, _vp, _vp, _i, _f, _ll, _i, _i, _vp]),
+    "da_euler_ancestral_step": (_i, [_vp, _vp, _vp, _ll, _vp, _vp, _vp, _i, _f, _ll, _i, _i, _vp]),
     "da_flowmatch_step": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _f, _ll, _i, _i, _vp]),
     "da_unipc_flow_step": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _f, _ll, _i, _i, _vp]),
     "da_dpmpp_2m_step": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _f, _ll, _i, _i, _i, _vp]),
@@ -164,7 +166,7 @@ IMAGE_F32_NCHW, IMAGE_F32_NHWC, IMAGE_U8_NHWC = 0, 1, 2
 POSTERIOR_MOMENTS, POSTERIOR_MEAN, POSTERIOR_SAMPLE, POSTERIOR_NOISE = 0, 1, 2, 3
 LATENTS_SHIFT, LATENTS_SCALE = 1, 2
 
-ABI_VERSION = 8              # include/diffusers_amd.h DA_ABI_VERSION
+ABI_VERSION = 9              # include/diffusers_amd.h DA_ABI_VERSION
 _lib = None
 _tls = threading.local()     # .recorder: the plan recorder of this thread (diffusers_amd/plan.py), if one is active
 

@@ -53,6 +53,7 @@ const char* const kSig[DA_FN_COUNT] = {
     /* DA_FN_CONV_THIN_OUT            */ "ppppiiiiii",
     /* DA_FN_INPAINT_BLEND            */ "ppppppiiili",
     /* DA_FN_CONV_IN_INPAINT          */ "ppppppppiiiiii",
+    /* DA_FN_EULER_ANCESTRAL_STEP     */ "ppplpppiflii",
     /* DA_FN_DPMPP_2M_STEP            */ "ppppppifliii",
 };
 
@@ -156,6 +157,8 @@ int run_op(const Op& op, void* s) {
     case DA_FN_CONV_THIN_IN:
       return da_conv_thin_in_bf16(P(0), P(1), P(2), P(3), I(4), I(5), I(6), I(7), I(8), I(9), I(10), F(11), F(12), s);
     case DA_FN_CONV_THIN_OUT: return da_conv_thin_out_bf16(P(0), P(1), P(2), P(3), I(4), I(5), I(6), I(7), I(8), I(9), s);
+    case DA_FN_EULER_ANCESTRAL_STEP:
+      return da_euler_ancestral_step(P(0), P(1), P(2), LL(3), P(4), CF(5), CI(6), I(7), F(8), LL(9), I(10), I(11), s);
     case DA_FN_DPMPP_2M_STEP:
       return da_dpmpp_2m_step(P(0), P(1), (float*)P(2), CF(3), CI(4), CI(5), I(6), F(7), LL(8), I(9), I(10), I(11), s);
     case DA_FN_INPAINT_BLEND:

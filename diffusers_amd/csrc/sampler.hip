@@ -4,6 +4,7 @@
 //   CFG combine        pipelines/stable_diffusion/pipeline_stable_diffusion.py:1054-1055,
 //                      pipelines/stable_diffusion_xl/pipeline_stable_diffusion_xl.py:1223-1225
 //   Euler              schedulers/scheduling_euler_discrete.py:326-348 (scale_model_input), :685-800 (step)
+//   Euler ancestral    schedulers/scheduling_euler_ancestral_discrete.py (step; per-step noise from a pre-drawn table)
 //   DDIM               schedulers/scheduling_ddim.py:384-514
 //   DDPM               schedulers/scheduling_ddpm.py:461-567
 //   FlowMatch Euler    schedulers/scheduling_flow_match_euler_discrete.py:423-523
@@ -344,6 +345,77 @@ __global__ void dpmpp_2m_step_kernel(const TV* __restrict__ eps, TX* __restrict_
   }
 }
 
+// Euler ancestral ("Euler a", schedulers/scheduling_euler_ancestral_discrete.py step):
+//   row = [sigma, sigma_to, dt = sigma_down - sigma, sqrt(sigma^2+1), c_out, sigma^2+1, sigma_up, timestep]
+// slots 0, 1, 3, 4, 5, 7 are the Euler row (euler_scale_input_kernel reads slot 3 of the same table); dt and sigma_up are evaluated
+// by the scheduler with fp32 torch scalar ops.  PRED: 0 epsilon, 1 v_prediction.  Rounding points of the reference's op chain:
+//   x0   = float(x) - T(sigma e)                      | T(e c_out) + float(x) / (sigma^2+1)        (products in the model dtype T)
+//   prev = float(x) + ((float(x) - x0) / sigma) dt                                                  (fp32, each op rounded)
+//   prev = prev + T(noise sigma_up)                                                                 (product in T, sum in fp32)
+//   out  = T(prev)
+// noise + *step_idx * noise_step_stride is this step's pre-drawn randn (stride 0: one buffer the host refills per step), so the
+// step stays graph-replayable.  A row with sigma_up == 0 (the last one) skips the noise read: x + T(n * 0) == x.
+struct EulerACoef {
+  float sigma, dt, c_out, s2p1, sigma_up;
+};
+
+template <typename T, int PRED>
+__device__ __forceinline__ float euler_a_one(const EulerACoef& k, float e, float s) {
+  float x0;
+  if (PRED == 0)
+    x0 = __fsub_rn(s, IO<T>::rnd(__fmul_rn(k.sigma, e)));
+  else
+    x0 = __fadd_rn(IO<T>::rnd(__fmul_rn(e, k.c_out)), __fdiv_rn(s, k.s2p1));
+  const float der = __fdiv_rn(__fsub_rn(s, x0), k.sigma);
+  return __fadd_rn(s, __fmul_rn(der, k.dt));
+}
+
+template <typename T>
+__device__ __forceinline__ float euler_a_noise(const EulerACoef& k, float prev, float nz) {
+  return __fadd_rn(prev, IO<T>::rnd(__fmul_rn(nz, k.sigma_up)));
+}
+
+// n_vec as in dpmpp_2m_step_kernel: the leading multiple of 4 elements when every base (the cond half and every noise row
+// included) is 16-byte aligned, else 0; the rest runs the scalar tail.  `out` may alias `x`: a thread reads its elements first.
+template <typename T, bool CFG, int PRED>
+__global__ void euler_ancestral_step_kernel(const T* __restrict__ eps, const T* x, const T* __restrict__ noise, T* out,
+                                            const float* __restrict__ table, const int* __restrict__ step_idx, float g,
+                                            size_t n, size_t n_vec, size_t noise_step_stride) {
+  const int step = *step_idx;
+  const float* row = table + (size_t)step * 8;
+  EulerACoef k;
+  k.sigma = row[0], k.dt = row[2], k.c_out = row[4], k.s2p1 = row[5], k.sigma_up = row[6];
+  noise += (size_t)step * noise_step_stride;
+  const bool add = k.sigma_up != 0.f;   // uniform over the launch
+  const size_t tid = (size_t)blockIdx.x * blockDim.x + threadIdx.x, nth = (size_t)gridDim.x * blockDim.x;
+  for (size_t i = tid * 4; i < n_vec; i += nth * 4) {
+    float e[4], xs[4], nz[4], o[4];
+    if (CFG) {
+      float u[4], c[4];
+      Vec4<T>::ld(eps, i, u), Vec4<T>::ld(eps, n + i, c);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) e[j] = cfg_combine<T>(u[j], c[j], g);
+    } else {
+      Vec4<T>::ld(eps, i, e);
+    }
+    Vec4<T>::ld(x, i, xs);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) o[j] = euler_a_one<T, PRED>(k, e[j], xs[j]);
+    if (add) {
+      Vec4<T>::ld(noise, i, nz);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) o[j] = euler_a_noise<T>(k, o[j], nz[j]);
+    }
+    Vec4<T>::st(out, i, o);
+  }
+  for (size_t i = n_vec + tid; i < n; i += nth) {
+    const float e = load_eps<T, CFG>(eps, i, n, g);
+    float o = euler_a_one<T, PRED>(k, e, IO<T>::ld(x, i));
+    if (add) o = euler_a_noise<T>(k, o, IO<T>::ld(noise, i));
+    IO<T>::st(out, i, o);
+  }
+}
+
 // Inpainting with a 4-channel U-Net re-imposes the known region after every scheduler step
 // (pipelines/stable_diffusion/pipeline_stable_diffusion_inpaint.py, the `num_channels_unet == 4` branch of the loop):
 //   init_latents_proper = scheduler.add_noise(image_latents, noise, timesteps[i + 1])     (the clean latents after the last step)
@@ -590,6 +662,35 @@ extern "C" int da_dpmpp_2m_step(const void* eps, void* x, float* m1, const float
 #undef DA_DP_C
 #undef DA_DP_P
 #undef DA_DP
+  DA_CHECK_LAUNCH();
+  return DA_OK;
+}
+
+extern "C" int da_euler_ancestral_step(const void* eps, const void* x, const void* noise, long long noise_step_stride,
+                                       void* out, const float* table, const int* step_idx, int cfg, float guidance,
+                                       long long n_, int dtype, int pred_type, void* stream) {
+  if (!eps || !x || !noise || !out || !table || !step_idx || n_ <= 0 || noise_step_stride < 0) return DA_ERR_INVALID;
+  if (pred_type < 0 || pred_type > 1) return DA_ERR_INVALID;
+  if (dtype != DA_DTYPE_BF16 && dtype != DA_DTYPE_F32) return DA_ERR_UNSUPPORTED;
+  const size_t n = (size_t)n_, esz = dtype == DA_DTYPE_BF16 ? 2 : 4;
+  hipStream_t s = (hipStream_t)stream;
+  // 4-wide accesses: every base 16-byte aligned -- with CFG the cond half n elements in, and the noise row of any step
+  const bool aligned = ((uintptr_t)eps | (uintptr_t)x | (uintptr_t)noise | (uintptr_t)out) % 16 == 0 &&
+                       ((size_t)noise_step_stride * esz) % 16 == 0 && (!cfg || (n * esz) % 16 == 0);
+  const size_t n_vec = aligned ? n - n % 4 : 0;
+  const size_t work = n_vec / 4 > n - n_vec ? n_vec / 4 : n - n_vec;
+#define DA_EA(T, C, P)                                                                                                    \
+  DA_LAUNCH((euler_ancestral_step_kernel<T, C, P>), ew_grid(work), dim3(256), 0, s, (const T*)eps, (const T*)x, (const T*)noise, \
+            (T*)out, table, step_idx, guidance, n, n_vec, (size_t)noise_step_stride)
+#define DA_EA_P(T, C) \
+  do { if (pred_type == 0) DA_EA(T, C, 0); else DA_EA(T, C, 1); } while (0)
+  if (dtype == DA_DTYPE_BF16) {
+    if (cfg) DA_EA_P(uint16_t, true); else DA_EA_P(uint16_t, false);
+  } else {
+    if (cfg) DA_EA_P(float, true); else DA_EA_P(float, false);
+  }
+#undef DA_EA_P
+#undef DA_EA
   DA_CHECK_LAUNCH();
   return DA_OK;
 }

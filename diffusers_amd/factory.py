@@ -25,6 +25,12 @@ SDXL_DPM_SCHEDULER = dict(beta_start=0.00085, beta_end=0.012, beta_schedule="sca
                           timestep_spacing="leading", use_karras_sigmas=True)
 SD15_DPM_SCHEDULER = dict(beta_start=0.00085, beta_end=0.012, beta_schedule="scaled_linear", steps_offset=1,
                           timestep_spacing="leading", use_karras_sigmas=True)
+# Euler ancestral ("Euler a") on the same betas: EulerAncestralDiscreteScheduler(**SDXL_EULER_A_SCHEDULER); few-step
+# Turbo-style checkpoints add timestep_spacing="trailing" and run 1-4 steps with guidance_scale=0
+SDXL_EULER_A_SCHEDULER = dict(beta_start=0.00085, beta_end=0.012, beta_schedule="scaled_linear", steps_offset=1,
+                              timestep_spacing="leading")
+SD15_EULER_A_SCHEDULER = dict(beta_start=0.00085, beta_end=0.012, beta_schedule="scaled_linear", steps_offset=1,
+                              timestep_spacing="leading")
 
 
 def build_unet(cfg: dict, seed: int = 0, device="cuda", init_device: Optional[str] = None, state_dict=None):

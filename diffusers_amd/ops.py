@@ -914,6 +914,46 @@ def euler_step(eps: torch.Tensor, x: torch.Tensor, table: torch.Tensor, step_idx
     return out
 
 
+def euler_ancestral_step(eps: torch.Tensor, x: torch.Tensor, noise: torch.Tensor, table: torch.Tensor, step_idx: torch.Tensor, *,
+                         cfg: bool, guidance: float, out: Optional[torch.Tensor] = None, pred_type: int = L.PRED_EPSILON,
+                         noise_step_stride: int = 0) -> torch.Tensor:
+    """EulerAncestralDiscreteScheduler.step (+ the CFG combine when ``cfg``), see da_euler_ancestral_step.  ``noise`` holds the
+    step's randn in the model output's dtype: one sample-sized block (``noise_step_stride=0``) or one row per table row,
+    ``noise_step_stride`` elements apart, picked by the device step counter.  ``out`` may be the sample (in place)."""
+    for t_, name in ((eps, "model_output"), (x, "sample"), (noise, "noise"), (table, "table"), (step_idx, "step_idx")):
+        if not torch.is_tensor(t_) or not t_.is_cuda:
+            raise ValueError(f"euler_ancestral_step: {name} must be a HIP device tensor (there is no CPU path)")
+    if out is not None and not out.is_cuda:
+        raise ValueError("euler_ancestral_step: out must be a HIP device tensor (there is no CPU path)")
+    if x.dtype not in (bf16, torch.float32):
+        raise ValueError(f"euler_ancestral_step: bf16 / fp32 samples, got {x.dtype}")
+    if eps.dtype != x.dtype:
+        raise ValueError(f"euler_ancestral_step: model_output ({eps.dtype}) and sample ({x.dtype}) must have the same dtype")
+    if pred_type not in (L.PRED_EPSILON, L.PRED_V):
+        raise ValueError("euler_ancestral_step: pred_type must be epsilon or v_prediction")
+    _check_sampler("euler_ancestral_step", x, eps, out, cfg)
+    if out is None:
+        out = torch.empty_like(x)
+    elif out.dtype != x.dtype:
+        raise ValueError("euler_ancestral_step: out must have the sample's dtype")
+    if table.dtype != torch.float32 or table.dim() != 2 or table.shape[1] != 8 or not table.is_contiguous():
+        raise ValueError("euler_ancestral_step: table must be a contiguous [steps][8] fp32 tensor")
+    if step_idx.dtype != torch.int32:
+        raise ValueError("euler_ancestral_step: step_idx must be an int32 device scalar")
+    if noise.dtype != eps.dtype:
+        raise ValueError(f"euler_ancestral_step: noise ({noise.dtype}) must have the model output's dtype ({eps.dtype})")
+    stride = int(noise_step_stride)
+    if stride < 0 or not noise.is_contiguous():
+        raise ValueError("euler_ancestral_step: noise must be contiguous, with a step stride >= 0")
+    if noise.numel() < (table.shape[0] - 1) * stride + x.numel():
+        raise ValueError(f"euler_ancestral_step: noise holds {noise.numel()} elements, {table.shape[0]} rows of stride {stride} "
+                         f"and a sample of {x.numel()} need {(table.shape[0] - 1) * stride + x.numel()}")
+    L.check(L.load().da_euler_ancestral_step(eps.data_ptr(), x.data_ptr(), noise.data_ptr(), stride, out.data_ptr(),
+                                             table.data_ptr(), step_idx.data_ptr(), int(cfg), float(guidance), x.numel(), _dt(x),
+                                             int(pred_type), _stream()), "da_euler_ancestral_step")
+    return out
+
+
 def x0_linear_step(eps: torch.Tensor, x: torch.Tensor, noise: Optional[torch.Tensor], table: torch.Tensor,
                    step_idx: torch.Tensor, *, cfg: bool, guidance: float,
                    out: Optional[torch.Tensor] = None, noise_step_stride: int = 0,

@@ -23,8 +23,8 @@ import torch
 from . import ops
 from .autoencoder_kl import AutoencoderKL
 from .pipeline_loading import PipelineLoadingMixin
-from .schedulers import (DDIMScheduler, DDPMScheduler, DPMSolverMultistepScheduler, EulerDiscreteScheduler,
-                         FlowMatchEulerDiscreteScheduler, UniPCMultistepScheduler)
+from .schedulers import (DDIMScheduler, DDPMScheduler, DPMSolverMultistepScheduler, EulerAncestralDiscreteScheduler,
+                         EulerDiscreteScheduler, FlowMatchEulerDiscreteScheduler, UniPCMultistepScheduler)
 from .transformer_flux import FluxTransformer2DModel
 from .transformer_wan import WanTransformer3DModel
 from .unet_2d import UNet2DModel
@@ -142,9 +142,15 @@ def denoising_end_steps(scheduler, denoising_end) -> int:
 
 def _refuse_custom_schedule(scheduler, timesteps, sigmas):
     """retrieve_timesteps (pipeline_stable_diffusion_xl.py:144-167) for a scheduler whose set_timesteps takes a step count only."""
-    if (timesteps is not None or sigmas is not None) and isinstance(scheduler, DPMSolverMultistepScheduler):
+    if (timesteps is not None or sigmas is not None) and isinstance(scheduler, (DPMSolverMultistepScheduler,
+                                                                                EulerAncestralDiscreteScheduler)):
         raise ValueError(f"The current scheduler class {type(scheduler)}'s `set_timesteps` does not support custom "
                          "timestep or sigma schedules. Please check whether you are using the correct scheduler.")
+
+
+def _scales_model_input(scheduler) -> bool:
+    """Schedulers whose ``scale_model_input`` divides by sqrt(sigma^2 + 1) (slot 3 of their table row); identity for the others."""
+    return isinstance(scheduler, (EulerDiscreteScheduler, EulerAncestralDiscreteScheduler))
 
 
 def _capture_step(pipe, step, mode):
@@ -262,7 +268,7 @@ class _LatentDiffusionBase(_StepCallbacks, PipelineLoadingMixin):
         self._graph_key = None
         self._static = {}
         self._eta = 0.0            # DDIM only: eta > 0 adds pre-drawn variance noise (one row per step) in the fused step
-        self._noise_table = None
+        self._noise_table = None   # [num_inference_steps, *latents.shape]: DDIM eta > 0, or a stochastic sampler (_draw_step_noise)
         self._guidance_rescale = 0.0   # > 0: rescale_noise_cfg after the CFG combine (pipeline_stable_diffusion.py:69-92)
 
     @property
@@ -277,7 +283,7 @@ class _LatentDiffusionBase(_StepCallbacks, PipelineLoadingMixin):
         """scale_model_input + CFG batch doubling + the U-Net forward of one step."""
         sch = self.scheduler
         rep = 2 if do_cfg else 1
-        if isinstance(sch, EulerDiscreteScheduler):
+        if _scales_model_input(sch):
             x_in = sch.scale_model_input(latents, sch.timesteps[0], rep=rep)
         else:
             x_in = ops.mul_scalar(latents, 1.0, rep=rep) if rep > 1 else latents  # DDIM, DPM-Solver++: scale_model_input = identity
@@ -290,6 +296,8 @@ class _LatentDiffusionBase(_StepCallbacks, PipelineLoadingMixin):
         # in place (same buffer every replay); without CFG (guidance_scale <= 1, pipeline_stable_diffusion_xl.py:1202,
         # :1223) the U-Net ran on the un-doubled batch and the same kernel skips the combine
         kw = {"eta": self._eta, "noise_table": self._noise_table} if self._eta > 0 else {}
+        if getattr(sch, "needs_step_noise", False):
+            kw = {"noise_table": self._noise_table}
         if do_cfg and self._guidance_rescale > 0.0:
             # pipeline_stable_diffusion_xl.py:1227-1229 / pipeline_stable_diffusion.py:1057-1059: combine, then rescale_noise_cfg
             # (per-sample std of the text and of the guided prediction: two small launches), then the step without its combine
@@ -298,6 +306,28 @@ class _LatentDiffusionBase(_StepCallbacks, PipelineLoadingMixin):
             return latents
         sch.step_cfg(eps, latents, guidance_scale, out=latents, cfg=do_cfg, **kw)
         return latents
+
+    def _draw_step_noise(self, latents, generator, num_inference_steps: int, n_steps: int, begin: int = 0):
+        """A stochastic sampler (``scheduler.needs_step_noise``) adds fresh noise in every step; the reference draws it inside
+        ``scheduler.step`` from the call's ``generator``.  The same draws are made here, up front and in step order -- callers
+        come here after every other draw of the call (initial latents, img2img / inpainting noise, the VAE posterior sample),
+        which is where the reference's loop would start consuming the generator -- into rows ``begin ... begin + n_steps - 1``
+        of a ``[num_inference_steps, *latents.shape]`` table in the latents' dtype (= the model output's); the fused step picks its
+        row with the device step counter, so it stays graph-replayable.  The table is refilled in place while its shape is
+        unchanged: captured graphs keep its address (``_make_graph_key`` carries it)."""
+        if not getattr(self.scheduler, "needs_step_noise", False):
+            if self._eta == 0.0:
+                self._noise_table = None
+            return
+        dev = latents.device
+        shape = (int(num_inference_steps),) + tuple(latents.shape)
+        table = self._static.get("noise_table")
+        if table is None or tuple(table.shape) != shape or table.dtype != latents.dtype or table.device != dev:
+            table = torch.zeros(shape, device=dev, dtype=latents.dtype)
+        for i in range(n_steps):
+            table[begin + i].copy_(_randn(latents.shape, generator, dev, latents.dtype))
+        self._static["noise_table"] = table
+        self._noise_table = table
 
     def _make_graph_key(self, latents, cond, guidance_scale, do_cfg):
         """Everything a captured step depends on besides the contents of its static buffers."""
@@ -479,6 +509,7 @@ class StableDiffusionXLPipeline(_LatentDiffusionBase):
             te = torch.cat([negative_pooled_prompt_embeds.to(device=dev, dtype=bf16), te], dim=0)
             ids = torch.cat([ids, ids], dim=0)
         cond = self.unet.precompute_conditioning(pe.contiguous(), {"text_embeds": te, "time_ids": ids})
+        self._draw_step_noise(latents, generator, len(self.scheduler.timesteps), num_inference_steps)
         latents = self._denoise(latents, cond, num_inference_steps, guidance_scale, do_cfg, use_graph)
         images = self._decode(latents, output_type)
         if not return_dict:
@@ -562,6 +593,7 @@ class StableDiffusionPipeline(_LatentDiffusionBase):
                 table = self._static["noise_table"]
             self._static["noise_table"] = table
             self._noise_table = table
+        self._draw_step_noise(latents, generator, num_inference_steps, num_inference_steps)
         latents = self._denoise(latents, cond, num_inference_steps, guidance_scale, do_cfg, use_graph)
         images = self._decode(latents, output_type)
         if not return_dict:
@@ -839,6 +871,7 @@ class StableDiffusionXLImg2ImgPipeline(_Img2ImgMixin, StableDiffusionXLPipeline)
             te = torch.cat([negative_pooled_prompt_embeds.to(device=dev, dtype=bf16), te], dim=0)
             ids = torch.cat([neg_ids.to(dev).repeat(B, 1), ids], dim=0)
         cond = self.unet.precompute_conditioning(pe.contiguous(), {"text_embeds": te, "time_ids": ids})
+        self._draw_step_noise(latents, generator, num_inference_steps, n_steps, begin)
         latents = self._denoise(latents, cond, n_steps, guidance_scale, do_cfg, use_graph, begin=begin)
         images = self._decode(latents, output_type)
         if not return_dict:
@@ -913,6 +946,7 @@ class StableDiffusionImg2ImgPipeline(_Img2ImgMixin, StableDiffusionPipeline):
             pe = torch.cat([negative_prompt_embeds.to(device=dev, dtype=bf16), pe], dim=0)
         cond = self.unet.precompute_conditioning(pe.contiguous(), None)
         self._set_eta(eta, latents, generator, num_inference_steps, n_steps, begin)
+        self._draw_step_noise(latents, generator, num_inference_steps, n_steps, begin)
         latents = self._denoise(latents, cond, n_steps, guidance_scale, do_cfg, use_graph, begin=begin)
         images = self._decode(latents, output_type)
         if not return_dict:
@@ -1110,7 +1144,7 @@ class _InpaintMixin:
         if st is None or st["masked"] is None:
             return super()._predict_noise(latents, cond, do_cfg)
         sch = self.scheduler
-        euler = isinstance(sch, EulerDiscreteScheduler)
+        euler = _scales_model_input(sch)
         if euler:
             if sch._step_index is None:
                 sch._init_step_index(sch.timesteps[0])
@@ -1186,6 +1220,7 @@ class StableDiffusionInpaintPipeline(_InpaintMixin, StableDiffusionImg2ImgPipeli
             pe = torch.cat([negative_prompt_embeds.to(device=dev, dtype=bf16), pe], dim=0)
         cond = self.unet.precompute_conditioning(pe.contiguous(), None)
         self._set_eta(eta, latents, generator, num_inference_steps, n_steps, begin)
+        self._draw_step_noise(latents, generator, num_inference_steps, n_steps, begin)
         latents = self._denoise(latents, cond, n_steps, guidance_scale, do_cfg, use_graph, begin=begin)
         images = self._decode(latents, output_type)
         if not return_dict:
@@ -1285,6 +1320,7 @@ class StableDiffusionXLInpaintPipeline(_InpaintMixin, StableDiffusionXLImg2ImgPi
             te = torch.cat([negative_pooled_prompt_embeds.to(device=dev, dtype=bf16), te], dim=0)
             ids = torch.cat([neg_ids.to(dev).repeat(B, 1), ids], dim=0)
         cond = self.unet.precompute_conditioning(pe.contiguous(), {"text_embeds": te, "time_ids": ids})
+        self._draw_step_noise(latents, generator, num_inference_steps, n_steps, begin)
         latents = self._denoise(latents, cond, n_steps, guidance_scale, do_cfg, use_graph, begin=begin)
         images = self._decode(latents, output_type)
         if not return_dict:

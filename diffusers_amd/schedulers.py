@@ -3,6 +3,7 @@ init_noise_sigma / order / config) whose per-step tensor update is ONE fused HIP
 
 Host side (schedule construction) is numpy / torch-CPU scalar math written to follow the reference formulas exactly:
   EulerDiscreteScheduler          schedulers/scheduling_euler_discrete.py:203-276, :350-481, :326-348, :685-800
+  EulerAncestralDiscreteScheduler schedulers/scheduling_euler_ancestral_discrete.py (stochastic: per-step noise, pre-drawn)
   DDIMScheduler                   schedulers/scheduling_ddim.py:212-236, :334-382, :384-514
   DDPMScheduler                   schedulers/scheduling_ddpm.py:348-416, :461-567
   FlowMatchEulerDiscreteScheduler schedulers/scheduling_flow_match_euler_discrete.py:283-382, :423-523
@@ -227,6 +228,60 @@ def _respaced_sigmas(smin: float, smax: float, n: int, karras: bool):
     return np.exp(np.linspace(math.log(smax), math.log(smin), n))
 
 
+def _euler_spaced_timesteps(spacing: str, n_train: int, n: int, steps_offset: int) -> np.ndarray:
+    """The float32 model timesteps of an ``n``-step schedule (scheduling_euler_discrete.py:409-431, the same three branches in
+    scheduling_euler_ancestral_discrete.py)."""
+    if spacing == "linspace":
+        return np.linspace(0, n_train - 1, n, dtype=np.float32)[::-1].copy()
+    if spacing == "leading":
+        ratio = n_train // n
+        ts = (np.arange(0, n) * ratio).round()[::-1].copy().astype(np.float32)
+        ts += steps_offset
+        return ts
+    if spacing == "trailing":
+        ratio = n_train / n
+        ts = (np.arange(n_train, 0, -ratio)).round().copy().astype(np.float32)
+        ts -= 1
+        return ts
+    raise ValueError(f"{spacing} is not supported. Please make sure to choose one of 'linspace', "
+                     "'leading' or 'trailing'.")
+
+
+def _euler_rows(sigmas: torch.Tensor, ts, n: int) -> np.ndarray:
+    """[sigma, sigma_next, dt, sqrt(sigma^2+1), c_out, sigma^2+1, 0, timestep] per step from the fp32 CPU sigma ladder (terminal
+    value included)."""
+    rows = np.zeros((n, 8), dtype=np.float32)
+    for i in range(n):
+        s, s_next = sigmas[i], sigmas[i + 1]
+        rows[i, 0] = float(s)
+        rows[i, 1] = float(s_next)
+        rows[i, 2] = float(s_next - s)                 # dt, fp32 torch scalar arithmetic as the reference
+        rows[i, 3] = float((s ** 2 + 1) ** 0.5)        # scale_model_input denominator
+        rows[i, 4] = float(-s / (s ** 2 + 1) ** 0.5)   # v_prediction: c_out (scheduling_euler_discrete.py:767)
+        rows[i, 5] = float(s ** 2 + 1)                 # v_prediction: sample / (sigma^2 + 1)
+        rows[i, 7] = float(ts[i])
+    return rows
+
+
+_INT_TIMESTEP_MSG = ("Passing integer indices (e.g. from `enumerate(timesteps)`) as timesteps to `{}.step()` is not supported. "
+                     "Make sure to pass one of the `scheduler.timesteps` as a timestep.")
+
+
+def _sigma_noise_coeffs(sch, timesteps, dtype):
+    """add_noise = x + n sigma of the k-diffusion style schedulers (scheduling_euler_discrete.py add_noise): sigma of the step at
+    ``begin_index`` (img2img: before the first step), at ``step_index`` (after it), or of each timestep's index when no begin
+    index is set; sigmas cast to ``dtype``."""
+    sig = sch.sigmas.to(dtype=dtype)
+    ts = torch.as_tensor(timesteps).reshape(-1).cpu()
+    if sch.begin_index is None:
+        idx = [sch.index_for_timestep(t) for t in ts]
+    elif sch.step_index is not None:
+        idx = [sch.step_index] * ts.shape[0]
+    else:
+        idx = [sch.begin_index] * ts.shape[0]
+    return [1.0] * len(idx), [float(sig[i]) for i in idx]
+
+
 class EulerDiscreteScheduler(_SchedulerBase):
     _defaults = dict(num_train_timesteps=1000, beta_start=0.0001, beta_end=0.02, beta_schedule="linear",
                      trained_betas=None, prediction_type="epsilon", interpolation_type="linear",
@@ -293,19 +348,8 @@ class EulerDiscreteScheduler(_SchedulerBase):
             return
         if timesteps is not None:
             ts = np.array(timesteps).astype(np.float32)
-        elif c.timestep_spacing == "linspace":
-            ts = np.linspace(0, n_train - 1, num_inference_steps, dtype=np.float32)[::-1].copy()
-        elif c.timestep_spacing == "leading":
-            ratio = n_train // num_inference_steps
-            ts = (np.arange(0, num_inference_steps) * ratio).round()[::-1].copy().astype(np.float32)
-            ts += c.steps_offset
-        elif c.timestep_spacing == "trailing":
-            ratio = n_train / num_inference_steps
-            ts = (np.arange(n_train, 0, -ratio)).round().copy().astype(np.float32)
-            ts -= 1
         else:
-            raise ValueError(f"{c.timestep_spacing} is not supported. Please make sure to choose one of 'linspace', "
-                             "'leading' or 'trailing'.")
+            ts = _euler_spaced_timesteps(c.timestep_spacing, n_train, num_inference_steps, c.steps_offset)
         sig = np.interp(ts, np.arange(0, len(base)), base)
         if c.use_karras_sigmas or c.use_exponential_sigmas:
             # a re-spaced sigma ladder between the interpolated extremes (scheduling_euler_discrete.py:446-452, :520-585);
@@ -330,30 +374,12 @@ class EulerDiscreteScheduler(_SchedulerBase):
         self._timesteps_host = ts.astype(np.float32)
         self._step_index = None
         self._begin_index = None
-        rows = np.zeros((num_inference_steps, 8), dtype=np.float32)
-        for i in range(num_inference_steps):
-            s, s_next = self.sigmas[i], self.sigmas[i + 1]
-            rows[i, 0] = float(s)
-            rows[i, 1] = float(s_next)
-            rows[i, 2] = float(s_next - s)                 # dt, fp32 torch scalar arithmetic as the reference
-            rows[i, 3] = float((s ** 2 + 1) ** 0.5)        # scale_model_input denominator
-            rows[i, 4] = float(-s / (s ** 2 + 1) ** 0.5)   # v_prediction: c_out (scheduling_euler_discrete.py:767)
-            rows[i, 5] = float(s ** 2 + 1)                 # v_prediction: sample / (sigma^2 + 1)
-            rows[i, 7] = float(ts[i])
-        self._upload(rows, device)
+        self._upload(_euler_rows(self.sigmas, ts, num_inference_steps), device)
 
     def _add_noise_coeffs(self, timesteps, dtype):
         """scheduling_euler_discrete.py add_noise: x + n sigma, sigma of the step at ``begin_index`` (img2img: before the first
         step), at ``step_index`` (after it), or of each timestep's index when no begin index is set; sigmas cast to ``dtype``."""
-        sig = self.sigmas.to(dtype=dtype)
-        ts = torch.as_tensor(timesteps).reshape(-1).cpu()
-        if self.begin_index is None:
-            idx = [self.index_for_timestep(t) for t in ts]
-        elif self.step_index is not None:
-            idx = [self.step_index] * ts.shape[0]
-        else:
-            idx = [self.begin_index] * ts.shape[0]
-        return [1.0] * len(idx), [float(sig[i]) for i in idx]
+        return _sigma_noise_coeffs(self, timesteps, dtype)
 
     def scale_model_input(self, sample, timestep=None, rep: int = 1):
         if self._step_index is None:
@@ -385,6 +411,124 @@ class EulerDiscreteScheduler(_SchedulerBase):
             self._init_step_index(self.timesteps[0])
         prev = ops.euler_step(model_output_2b, sample, self._table, self._step_dev, cfg=cfg,
                               guidance=float(guidance_scale), out=out, pred_type=self._pred)
+        self._advance()
+        return prev
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+class EulerAncestralDiscreteScheduler(_SchedulerBase):
+    """schedulers/scheduling_euler_ancestral_discrete.py ("Euler a"): the Euler step towards ``sigma_down`` plus fresh noise of
+    scale ``sigma_up`` per step, with sigma_down^2 + sigma_up^2 = sigma_to^2.  The table row is the Euler row with
+    dt = sigma_down - sigma in slot 2 and sigma_up in slot 6, both evaluated with fp32 torch scalar ops in the reference's order;
+    ONE kernel per step (da_euler_ancestral_step) does the CFG combine, the update and the noise add with the reference's rounding
+    points.  ``step()`` draws the noise as the reference does; ``step_cfg`` (the pipelines' captured step) reads row
+    ``device_step`` of a pre-drawn ``noise_table`` [steps][numel], so the step stays HIP-graph replayable."""
+
+    _defaults = dict(num_train_timesteps=1000, beta_start=0.0001, beta_end=0.02, beta_schedule="linear", trained_betas=None,
+                     prediction_type="epsilon", timestep_spacing="linspace", steps_offset=0, rescale_betas_zero_snr=False)
+    needs_step_noise = True          # the pipelines pre-draw one randn per step that runs, after every other draw of the call ...
+    step_noise_dtype = "model_output"  # ... in the model output's dtype (scheduling_euler_ancestral_discrete.py: randn_tensor(dtype=))
+
+    def __init__(self, **kwargs):
+        super().__init__(**kwargs)
+        c = self.config
+        if c.rescale_betas_zero_snr:
+            raise NotImplementedError("EulerAncestralDiscreteScheduler: zero-SNR rescaling is not on the hot path")
+        if c.prediction_type == "sample":
+            raise NotImplementedError("prediction_type not implemented yet: sample")
+        if c.prediction_type not in ("epsilon", "v_prediction"):
+            raise ValueError(f"prediction_type given as {c.prediction_type} must be one of `epsilon`, or `v_prediction`")
+        self._pred = L.PRED_TYPES[c.prediction_type]
+        self.betas = _betas(c.beta_schedule, c.beta_start, c.beta_end, c.num_train_timesteps, c.trained_betas)
+        self.alphas = 1.0 - self.betas
+        self.alphas_cumprod = torch.cumprod(self.alphas, dim=0)
+        sig = (((1 - self.alphas_cumprod) / self.alphas_cumprod) ** 0.5).flip(0)
+        ts = np.linspace(0, c.num_train_timesteps - 1, c.num_train_timesteps, dtype=float)[::-1].copy()
+        self.timesteps = torch.from_numpy(ts).to(dtype=torch.float32)
+        self._timesteps_host = self.timesteps.numpy()
+        self.sigmas = torch.cat([sig, torch.zeros(1)])
+        self.is_scale_input_called = False
+
+    @property
+    def init_noise_sigma(self):
+        max_sigma = self.sigmas.max()
+        if self.config.timestep_spacing in ("linspace", "trailing"):
+            return max_sigma
+        return (max_sigma ** 2 + 1) ** 0.5
+
+    def set_timesteps(self, num_inference_steps: int, device=None):
+        c = self.config
+        n = int(num_inference_steps)
+        self.num_inference_steps = n
+        ts = _euler_spaced_timesteps(c.timestep_spacing, c.num_train_timesteps, n, c.steps_offset)
+        base = (((1 - self.alphas_cumprod) / self.alphas_cumprod) ** 0.5).numpy()
+        sig = np.interp(ts, np.arange(0, len(base)), base)
+        sig = np.concatenate([sig, [0.0]]).astype(np.float32)
+        self.sigmas = torch.from_numpy(sig)                           # kept on the CPU like the reference
+        self.timesteps = torch.from_numpy(ts.astype(np.float32)).to(device=device)
+        self._timesteps_host = ts.astype(np.float32)
+        self._step_index = None
+        self._begin_index = None
+        rows = _euler_rows(self.sigmas, ts, n)
+        for i in range(n):
+            sigma, sigma_to = self.sigmas[i], self.sigmas[i + 1]      # 0-d fp32 tensors: every op below rounds to fp32
+            sigma_up = (sigma_to ** 2 * (sigma ** 2 - sigma_to ** 2) / sigma ** 2) ** 0.5
+            sigma_down = (sigma_to ** 2 - sigma_up ** 2) ** 0.5
+            rows[i, 2] = float(sigma_down - sigma)
+            rows[i, 6] = float(sigma_up)
+        if not np.isfinite(rows).all():
+            raise ValueError("EulerAncestralDiscreteScheduler: non-finite step coefficients (a sigma of 0 before the last row?)")
+        self._upload(rows, device)
+
+    def _add_noise_coeffs(self, timesteps, dtype):
+        return _sigma_noise_coeffs(self, timesteps, dtype)
+
+    def scale_model_input(self, sample, timestep=None, rep: int = 1):
+        if self._step_index is None:
+            self._init_step_index(timestep)
+        self.is_scale_input_called = True
+        return ops.euler_scale_model_input(sample, self._table, self._step_dev, rep=rep)
+
+    def _before_step(self, timestep):
+        if self.num_inference_steps is None:
+            raise ValueError("Number of inference steps is 'None', you need to run 'set_timesteps' after creating the "
+                             "scheduler")
+        if self._step_index is None:
+            self._init_step_index(timestep)
+        if not 0 <= self._step_index < self.num_inference_steps:
+            raise IndexError(f"EulerAncestralDiscreteScheduler: step {self._step_index} of a {self.num_inference_steps}-step "
+                             "schedule (call set_timesteps() or reset() before another loop)")
+
+    def step(self, model_output, timestep, sample, generator=None, return_dict: bool = True):
+        if isinstance(timestep, int) or (torch.is_tensor(timestep) and timestep.dtype in (torch.int32, torch.int64)):
+            raise ValueError(_INT_TIMESTEP_MSG.format("EulerAncestralDiscreteScheduler"))
+        self._before_step(timestep)
+        # randn_tensor: on the generator's device when one is given, in the model output's dtype, then moved to the model output
+        gdev = generator.device if generator is not None else model_output.device
+        noise = torch.randn(model_output.shape, generator=generator, device=gdev,
+                            dtype=model_output.dtype).to(model_output.device)
+        # (the reference upcasts the sample and returns the model output's dtype; here the two share one dtype)
+        prev = ops.euler_ancestral_step(model_output.contiguous(), sample.contiguous(), noise.contiguous(), self._table,
+                                        self._step_dev, cfg=False, guidance=0.0, pred_type=self._pred, noise_step_stride=0)
+        self._advance()
+        if not return_dict:
+            return (prev, None)
+        return SchedulerOutput(prev_sample=prev)
+
+    def step_cfg(self, model_output_2b, sample, guidance_scale: float, out=None, cfg: bool = True, noise_table=None):
+        """Engine extension: CFG combine (``cfg=False``: a plain model output) + the ancestral step in one kernel, in place when
+        ``out`` is the sample.  ``noise_table`` [steps][numel of the sample], in the model output's dtype, holds every step's
+        noise drawn up front; the kernel reads the row of the device step counter."""
+        if noise_table is None:
+            raise ValueError("EulerAncestralDiscreteScheduler.step_cfg needs the pre-drawn `noise_table` [steps][numel]: the "
+                             "sampler adds fresh noise every step")
+        self._before_step(self.timesteps[0])
+        if noise_table.shape[0] != self.num_inference_steps:
+            raise ValueError(f"EulerAncestralDiscreteScheduler.step_cfg: `noise_table` has {noise_table.shape[0]} rows for a "
+                             f"{self.num_inference_steps}-step schedule")
+        prev = ops.euler_ancestral_step(model_output_2b, sample, noise_table, self._table, self._step_dev, cfg=cfg,
+                                        guidance=float(guidance_scale), out=out, pred_type=self._pred,
+                                        noise_step_stride=sample.numel())
         self._advance()
         return prev
 

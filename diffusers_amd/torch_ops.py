@@ -15,6 +15,7 @@ name ends in ``_``).  Registration happens on import of this module (``import di
     y = torch.ops.mi355x.groupnorm(x, gamma, beta, 32, 1e-5, True)
     y = torch.ops.mi355x.layernorm(x, gamma, beta, 1e-5)
     x_next = torch.ops.mi355x.euler_step(eps, x, table, step_idx, True, 5.0, 0)
+    x_next = torch.ops.mi355x.euler_ancestral_step(eps, x, noise, table, step_idx, True, 5.0, 0, 0)
     x_next, m1 = torch.ops.mi355x.dpmpp_2m_step(eps, x, m1, table, step_idx, begin_idx, True, 5.0, 0)
 """
 from __future__ import annotations
@@ -123,4 +124,19 @@ def _(model_output, sample, history, table, step_idx, begin_idx, cfg, guidance_s
     return torch.empty_like(sample), torch.empty_like(history)
 
 
-OPS = ("gemm", "conv2d_nhwc", "flash_attn", "groupnorm", "layernorm", "euler_step", "dpmpp_2m_step")
+@torch.library.custom_op(f"{NAMESPACE}::euler_ancestral_step", mutates_args=(), device_types="cuda")
+def euler_ancestral_step(model_output: torch.Tensor, sample: torch.Tensor, noise: torch.Tensor, table: torch.Tensor,
+                         step_idx: torch.Tensor, cfg: bool, guidance_scale: float, pred_type: int,
+                         noise_step_stride: int) -> torch.Tensor:
+    """EulerAncestralDiscreteScheduler.step (+ the CFG combine when ``cfg``) from the scheduler's device table and the step's
+    pre-drawn noise (row ``step_idx`` of a table ``noise_step_stride`` elements apart; 0: one block); returns the new sample."""
+    return ops.euler_ancestral_step(model_output, sample, noise, table, step_idx, cfg=cfg, guidance=guidance_scale,
+                                    pred_type=pred_type, noise_step_stride=noise_step_stride)
+
+
+@euler_ancestral_step.register_fake
+def _(model_output, sample, noise, table, step_idx, cfg, guidance_scale, pred_type, noise_step_stride):
+    return torch.empty_like(sample)
+
+
+OPS = ("gemm", "conv2d_nhwc", "flash_attn", "groupnorm", "layernorm", "euler_step", "dpmpp_2m_step", "euler_ancestral_step")

@@ -99,9 +99,11 @@ extern "C" {
  * built against an older header would pass shorter structs and the library would read garbage for the new members
  * (da_gemm_params.vt is a STORE address).  History: 1 = rounds 1-3; 4 = round 4 (da_gemm_params.vt / vt_col0 / ld_vt,
  * da_attention_params.algo); 5 = round 5; 6 = round 6 (da_attention_params.split_ws / split_ws_bytes / kv_split; da_groupnorm_nhwc_bf16 takes `sync`);
- * 7 = da_dpmpp_2m_step, DA_FN_DPMPP_2M_STEP; 8 = this header (da_inpaint_blend, da_conv_in_inpaint; their DA_FN_* numbers are 32 and 33 and
- * DA_FN_DPMPP_2M_STEP moved from 32 to 34: plan files written under version 7 are not valid under version 8). */
-#define DA_ABI_VERSION 8
+ * 7 = da_dpmpp_2m_step, DA_FN_DPMPP_2M_STEP; 8 = da_inpaint_blend, da_conv_in_inpaint (their DA_FN_* numbers are 32 and 33 and
+ * DA_FN_DPMPP_2M_STEP moved from 32 to 34: plan files written under version 7 are not valid under version 8); 9 = this header
+ * (da_euler_ancestral_step; DA_FN_EULER_ANCESTRAL_STEP is 34 and DA_FN_DPMPP_2M_STEP moved to 35: plan files of version 8 are not
+ * valid under version 9). */
+#define DA_ABI_VERSION 9
 int da_version(void);
 size_t da_sizeof_gemm_params(void);
 size_t da_sizeof_attention_params(void);
@@ -425,6 +427,16 @@ int da_euler_step(const void* eps, const void* x, void* out, const float* table,
 int da_x0_linear_step(const void* eps, const void* x, const void* noise, long long noise_step_stride, void* out,
                       const float* table, const int* step_idx, int cfg, float guidance, long long n, int dtype,
                       int pred_type, void* stream);
+/* da_euler_ancestral_step: scheduling_euler_ancestral_discrete.py step ("Euler a") + the CFG combine, one pass.
+ * row = [sigma, sigma_to, dt = sigma_down - sigma, sqrt(sigma^2+1), c_out, sigma^2+1, sigma_up, timestep] (slots 0, 1, 3, 4, 5, 7 as
+ * the Euler row, so da_euler_scale_model_input reads the same table).  prev = x + ((x - x0) / sigma) dt in fp32, then
+ * + T(noise * sigma_up), stored in the tensor dtype T; x0 as da_euler_step forms it; pred_type = DA_PRED_EPSILON or DA_PRED_V.
+ * noise (REQUIRED, dtype T) + *step_idx * noise_step_stride elements = this step's randn (stride 0: one buffer refilled by the
+ * host per step; > 0: every step pre-drawn, the table must hold a row for every step the counter can reach).  A row with
+ * sigma_up == 0 does not read the noise.  out may alias x. */
+int da_euler_ancestral_step(const void* eps, const void* x, const void* noise, long long noise_step_stride, void* out,
+                            const float* table, const int* step_idx, int cfg, float guidance, long long n, int dtype,
+                            int pred_type, void* stream);
 /* dtype = dtype of the model output v AND of out; x_dtype = dtype of the sample (fp32 sample + bf16 model output is the
  * reference's Wan hand-over: the update is formed in fp32 and stored in the model output's dtype, :484,:517) */
 int da_flowmatch_step(const void* v, const void* x, void* out, const float* table, const int* step_idx, int cfg,
@@ -619,8 +631,9 @@ int da_vae_posterior_latents(const void* in, long long sB, long long sC, long lo
 #define DA_FN_CONV_THIN_OUT 31            /* da_conv_thin_out_bf16 */
 #define DA_FN_INPAINT_BLEND 32            /* da_inpaint_blend */
 #define DA_FN_CONV_IN_INPAINT 33          /* da_conv_in_inpaint */
-#define DA_FN_DPMPP_2M_STEP 34            /* da_dpmpp_2m_step */
-#define DA_FN_COUNT 35
+#define DA_FN_EULER_ANCESTRAL_STEP 34     /* da_euler_ancestral_step */
+#define DA_FN_DPMPP_2M_STEP 35            /* da_dpmpp_2m_step */
+#define DA_FN_COUNT 36
 #define DA_PLAN_MAX_ARGS 16
 
 typedef struct da_plan_op {
