@@ -386,11 +386,11 @@ __global__ __launch_bounds__(512) void igemm2_bf16_kernel(const da_gemm_params p
 #pragma unroll
   for (int ih = 0; ih < (PFN ? MH : 1); ++ih)
 #pragma unroll
-    for (int jh = 0; jh < (PFN ? NH : 1); ++jh) res_v[ih][jh] = make_uint2(0, 0);
+    for (int jh = 0; jh < (PFN ? NH : 1); ++jh) res_v[ih][jh] = make_uint2(DA_NEG0_BF2, DA_NEG0_BF2);
 #pragma unroll
   for (int ih = 0; ih < ((PF && STG) ? MH : 1); ++ih)
 #pragma unroll
-    for (int t = 0; t < ((PF && STG) ? TT : 1); ++t) resw[ih][t] = make_uint4(0, 0, 0, 0);
+    for (int t = 0; t < ((PF && STG) ? TT : 1); ++t) resw[ih][t] = make_uint4(DA_NEG0_BF2, DA_NEG0_BF2, DA_NEG0_BF2, DA_NEG0_BF2);
 #pragma unroll
   for (int jh = 0; jh < NH; ++jh) bias_v[jh] = make_uint2(0, 0);
   // LayerNorm fold, consumer side: the 24 (sum, sum of squares) slots of a row this lane finishes are read by its four kq lanes,
@@ -1086,7 +1086,7 @@ __global__ __launch_bounds__(512) void igemm2_bf16_kernel(const da_gemm_params p
           } else {
             const float4 lo = *(const float4*)(stg + row * ROWB + c8 * 32), hi = *(const float4*)(stg + row * ROWB + c8 * 32 + 16);
             float o[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
-            uint4 rw = make_uint4(0, 0, 0, 0);
+            uint4 rw = make_uint4(DA_NEG0_BF2, DA_NEG0_BF2, DA_NEG0_BF2, DA_NEG0_BF2);
             if constexpr (PF) rw = resw[ih][t];
             else if (has_res && inside) rw = *(const uint4*)(resid + (size_t)mo * p.ldr + no);
             o[0] += bf_lo(rw.x); o[1] += bf_hi(rw.x); o[2] += bf_lo(rw.y); o[3] += bf_hi(rw.y);
@@ -1144,7 +1144,7 @@ __global__ __launch_bounds__(512) void igemm2_bf16_kernel(const da_gemm_params p
 #pragma unroll
         for (int e = 0; e < 4; ++e) o[e] = keep[ih][jh][e] * p.alpha;
         ln_apply4(o, ih, n);
-        uint2 rvv = make_uint2(0, 0), rsv = make_uint2(0, 0);
+        uint2 rvv = make_uint2(0, 0), rsv = make_uint2(DA_NEG0_BF2, DA_NEG0_BF2);
         if constexpr (PF) rvv = rowvec_v[ih][jh];
         else if (has_rowvec) rvv = *(const uint2*)((const uint16_t*)p.rowvec + (size_t)bidx * p.ld_rowvec + n);
         if constexpr (PFN) rsv = res_v[ih][jh];

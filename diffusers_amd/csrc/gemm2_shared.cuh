@@ -37,6 +37,11 @@ __device__ __forceinline__ void static_for(F&& f) {
 // so there is no per-tile branch on them either.  FINISH = false stops in front of the residual: the row-contiguous store
 // path adds it (and the output scale) after the values went through LDS -- the same fp32 operations in the same order.
 // GATE: 0 none, 1 bf16 [B][ld_gate], 2 fp32.
+// An ABSENT residual is a vector of NEGATIVE zeros: x + (-0) == x for every x, -0 included, whereas x + (+0) turns the -0 an
+// activation returns for a large negative input (SiLU(-100) = -100 / inf) into +0 -- the first family, which branches on the pointer,
+// keeps that sign, and the two families must agree bit for bit (tests/test_value_domain_gpu.py).
+constexpr uint32_t DA_NEG0_BF2 = 0x80008000u;
+
 template <int ACT, int GATE, bool FINISH>
 __device__ __forceinline__ void epilogue4(const da_gemm_params& p, float* o, int n, int bidx, float brow, uint2 bv, uint2 rv, uint2 resv) {
   o[0] += bf_lo(bv.x); o[1] += bf_hi(bv.x); o[2] += bf_lo(bv.y); o[3] += bf_hi(bv.y);

@@ -59,6 +59,7 @@
 namespace da_gemm3 {
 
 using da_gemm2::epilogue4;
+using da_gemm2::DA_NEG0_BF2;
 
 constexpr int BM = 256, BN = 256;
 constexpr int HALF = 128 * 128;      // bytes of one half-tile (128 rows x 64 bf16)
@@ -308,7 +309,7 @@ __global__ __launch_bounds__(512) void gemm3_bf16_kernel(const da_gemm_params p,
               float o[4];
 #pragma unroll
               for (int e = 0; e < 4; ++e) o[e] = acc[h][hp][i][j][e] * p.alpha;
-              uint2 rvv = make_uint2(0, 0), rsv = make_uint2(0, 0);
+              uint2 rvv = make_uint2(0, 0), rsv = make_uint2(DA_NEG0_BF2, DA_NEG0_BF2);
               if (has_rowvec) rvv = *(const uint2*)((const uint16_t*)p.rowvec + (size_t)bidx * p.ld_rowvec + n);
               if (has_res) rsv = *(const uint2*)((const uint16_t*)p.residual + (size_t)m * p.ldr + n);
               epilogue4<ACT, GATE, true>(p, o, n, bidx, brow, bias_v[hp][j], rvv, rsv);
@@ -380,7 +381,7 @@ __global__ __launch_bounds__(512) void gemm3_bf16_kernel(const da_gemm_params p,
             } else {
               const float4 lo = *(const float4*)(sb + row * ROWB + c8 * 32), hi = *(const float4*)(sb + row * ROWB + c8 * 32 + 16);
               float o[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
-              uint4 rw = make_uint4(0, 0, 0, 0);
+              uint4 rw = make_uint4(DA_NEG0_BF2, DA_NEG0_BF2, DA_NEG0_BF2, DA_NEG0_BF2);
               if (has_res && inside) rw = *(const uint4*)(resid + (size_t)mo * p.ldr + no);
               o[0] += bf_lo(rw.x); o[1] += bf_hi(rw.x); o[2] += bf_lo(rw.y); o[3] += bf_hi(rw.y);
               o[4] += bf_lo(rw.z); o[5] += bf_hi(rw.z); o[6] += bf_lo(rw.w); o[7] += bf_hi(rw.w);

@@ -575,7 +575,15 @@ __global__ __launch_bounds__(256) void rmsnorm_rope_kernel(uint16_t* __restrict_
   }
 }
 
-// Row softmax: fp32 scores [M][ld] -> bf16 probabilities [M][ldo]; one block per row (N up to 2^20).
+// Row softmax: fp32 scores [M][ld] -> bf16 probabilities [M][ldo]; one block per row (N up to 2^20).  N need not be a multiple of 4:
+// the last N % 4 columns of a row are read and written one by one (missing lanes of the quad hold -inf: exp = 0), so nothing past
+// column N is touched; ld / ldo stay multiples of 4 (the 16-byte row loads, the 8-byte stores).
+__device__ __forceinline__ float4 softmax_quad(const float* __restrict__ row, int i, int N) {
+  if (i + 4 <= N) return *(const float4*)(row + i);
+  const float ninf = -__builtin_inff();
+  return make_float4(row[i], i + 1 < N ? row[i + 1] : ninf, i + 2 < N ? row[i + 2] : ninf, ninf);
+}
+
 __global__ __launch_bounds__(256) void softmax_rows_kernel(const float* __restrict__ s, uint16_t* __restrict__ pr,
                                                            int N, long long ld, long long ldo) {
   __shared__ float red[8];
@@ -584,7 +592,7 @@ __global__ __launch_bounds__(256) void softmax_rows_kernel(const float* __restri
   uint16_t* orow = pr + (size_t)blockIdx.x * ldo;
   float mx = -3.0e38f;
   for (int i = t * 4; i < N; i += 1024) {
-    const float4 v = *(const float4*)(row + i);
+    const float4 v = softmax_quad(row, i, N);
     mx = fmaxf(fmaxf(mx, fmaxf(v.x, v.y)), fmaxf(v.z, v.w));
   }
   mx = wave_max(mx);
@@ -593,7 +601,7 @@ __global__ __launch_bounds__(256) void softmax_rows_kernel(const float* __restri
   mx = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
   float sum = 0.f;
   for (int i = t * 4; i < N; i += 1024) {
-    const float4 v = *(const float4*)(row + i);
+    const float4 v = softmax_quad(row, i, N);
     sum += __expf(v.x - mx) + __expf(v.y - mx) + __expf(v.z - mx) + __expf(v.w - mx);
   }
   sum = wave_sum(sum);
@@ -601,11 +609,17 @@ __global__ __launch_bounds__(256) void softmax_rows_kernel(const float* __restri
   __syncthreads();
   const float inv = 1.0f / (red[4] + red[5] + red[6] + red[7]);
   for (int i = t * 4; i < N; i += 1024) {
-    const float4 v = *(const float4*)(row + i);
+    const float4 v = softmax_quad(row, i, N);
     uint2 pk;
     pk.x = pack_bf2(__expf(v.x - mx) * inv, __expf(v.y - mx) * inv);
     pk.y = pack_bf2(__expf(v.z - mx) * inv, __expf(v.w - mx) * inv);
-    *(uint2*)(orow + i) = pk;
+    if (i + 4 <= N) {
+      *(uint2*)(orow + i) = pk;
+    } else {
+      orow[i] = (uint16_t)pk.x;
+      if (i + 1 < N) orow[i + 1] = (uint16_t)(pk.x >> 16);
+      if (i + 2 < N) orow[i + 2] = (uint16_t)pk.y;
+    }
   }
 }
 
@@ -940,7 +954,7 @@ extern "C" int da_rmsnorm_rope_bf16(void* x, int ld, int rows, int rows_per_batc
 
 extern "C" int da_softmax_rows_f32_bf16(const void* scores, void* probs, int M, int N, long long ld, long long ldo,
                                         void* stream) {
-  if (!scores || !probs || M <= 0 || N <= 0 || (N & 3) || (ld & 3) || (ldo & 3)) return DA_ERR_INVALID;
+  if (!scores || !probs || M <= 0 || N <= 0 || (ld & 3) || (ldo & 3)) return DA_ERR_INVALID;
   DA_LAUNCH(softmax_rows_kernel, dim3(M), dim3(256), 0, (hipStream_t)stream, (const float*)scores,
                      (uint16_t*)probs, N, ld, ldo);
   DA_CHECK_LAUNCH();

@@ -728,15 +728,18 @@ def attention(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, *, B: int, H: 
 
 def softmax_rows(scores: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Row softmax of fp32 scores [M][N] -> bf16.  ``out`` may be wider than N (row stride free): columns >= N are left
-    untouched, so a zero-initialised [M][ceil64(N)] buffer is a valid K-padded GEMM operand."""
+    untouched, so a zero-initialised [M][ceil64(N)] buffer is a valid K-padded GEMM operand.  Any N; the row strides of
+    ``scores`` and ``out`` are multiples of 4 (a [M][77] problem is a column view of a [M][80] buffer)."""
     _req(scores, "scores", torch.float32)
     M, N = scores.shape
-    if out is None:
-        out = torch.empty((M, N), device=scores.device, dtype=bf16)
+    if out is None:     # (row stride ceil4(N): the columns of a wider buffer when N is not a multiple of 4)
+        out = torch.empty((M, (N + 3) // 4 * 4), device=scores.device, dtype=bf16)[:, :N]
     else:
         _req(out, "out")
         if out.shape[0] != M or out.shape[1] < N:
             raise ValueError("softmax_rows: out must be [M][>= N]")
+    if _rows2d(scores, "scores") % 4 or _rows2d(out, "out") % 4:
+        raise ValueError("softmax_rows: the row strides of scores and out must be multiples of 4 (view a wider buffer)")
     L.check(L.load().da_softmax_rows_f32_bf16(scores.data_ptr(), out.data_ptr(), M, N, _rows2d(scores, "scores"),
                                               _rows2d(out, "out"), _stream()), "da_softmax_rows_f32_bf16")
     return out

@@ -186,7 +186,11 @@ typedef struct da_gemm_params {
    *     atomics: deterministic).
    *   CONSUMER (the GEMM that reads LN(x)): ln_stats != NULL -> each row's mean / rstd are formed from its ln_parts partials
    *     (fixed order) while the first K slices are in flight, and the epilogue applies the identity above to alpha * acc
-   *     before bias / activation (both GEGLU halves included).  W must be the pre-scaled (gamma o W) in bf16. */
+   *     before bias / activation (both GEGLU halves included).  W must be the pre-scaled (gamma o W) in bf16.
+   *     Value range: rstd = rsqrt(max(s2 / K - mean^2, 0) + eps) is formed in fp32 from the fp32 partials.  Against fp64 the folded
+   *     launch stays within the unfolded path's error (rel-rms 2.0e-3) for rows with |mean| / sigma up to 128 and is 2.3e-3 against
+   *     2.0e-3 at 256 -- where bf16 itself keeps one bit of the row's spread; constant rows of 0 / 1 / -3.5 give c + bias.  A constant
+   *     row of large magnitude is outside it: rstd = eps^-1/2 multiplies the fp32 rounding of acc - mean * s (tests/test_value_domain_gpu.py). */
   float* stats_out;
   int stats_ld;             /* floats per row of stats_out (>= 2 * parts) */
   const float* ln_stats;    /* partials written by the producer of this GEMM's A operand; every row must hold
@@ -370,7 +374,8 @@ int da_attention_bf16(const da_attention_params* p, void* stream);
  *                            scale (NULL = none).  cos/sin are fp32 [>= rope_row0 + rows][D] tables (NULL = no
  *                            rotation); row r of x uses table row rope_row0 + (r % rows_per_batch).
  *   da_softmax_rows_f32_bf16 row softmax of fp32 scores -> bf16 (single-head D=512 VAE mid-block attention,
- *                            attention_processor.py:2767 via vae.py / unet_2d_blocks.py:736-748).
+ *                            attention_processor.py:2767 via vae.py / unet_2d_blocks.py:736-748).  Any N >= 1; the row
+ *                            strides ld / ldo are multiples of 4 (>= N); columns >= N of probs are left untouched.
  * ------------------------------------------------------------------------------------------------------------------ */
 size_t da_groupnorm_workspace_bytes(int B, int HW, int C, int G);
 /* sync (round 6; may be NULL): a device buffer of da_groupnorm_sync_bytes() bytes, ZEROED ONCE by the caller and then owned by the
@@ -378,7 +383,12 @@ size_t da_groupnorm_workspace_bytes(int B, int HW, int C, int G);
  * slab exceeds one CU's LDS but that fit the chip's (<= 256 LDS-resident workgroups) are normalised in ONE launch that reads the tensor
  * once: the parts of a slab exchange their partial statistics through `sync` and wait for each other (all of them are resident).
  * Without it those tensors take the two-kernel form (statistics pass + apply pass = one more read).  Same formula and rounding points
- * either way; the statistics are summed in another order (outputs agree to a bf16 ulp). */
+ * either way; the statistics are summed in another order (outputs agree to a bf16 ulp).
+ * Value range (all forms): the statistics are one-pass, fp32 per thread and fp64 across threads, var = max(E[x^2] - mean^2, 0); the
+ * apply pass is y = x * a + (beta - mean * a) with a = rstd * gamma in fp32, so beta is recovered to |mean| * rstd * |gamma| * 2^-24.
+ * Tested against fp64 up to |mean| / sigma = 64, on constant slabs of 0 / 1 / -3.5, with a 2^15 outlier per group and at scales
+ * 2^-20 and 2^16 (tests/test_value_domain_gpu.py).  Outside: a (nearly) constant slab of large magnitude -- rstd = eps^-1/2 = 316 there,
+ * a slab of 1024 returns beta +- 1.6e-2 (torch's fp32 GroupNorm does the same). */
 size_t da_groupnorm_sync_bytes(void);
 int da_groupnorm_nhwc_bf16(const void* x, const void* x2, int C1, const void* gamma, const void* beta, void* y,
                            void* workspace, int B, int HW, int C, int G, float eps, int act, void* sync, void* stream);
