@@ -17,6 +17,8 @@ _EXPORTS = {
     "AutoencoderKLWan": "autoencoder_kl_wan",
     "FluxTransformer2DModel": "transformer_flux",
     "FluxPipeline": "pipelines",
+    "FluxImg2ImgPipeline": "pipelines",
+    "FluxInpaintPipeline": "pipelines",
     "WanTransformer3DModel": "transformer_wan",
     "WanPipeline": "pipelines",
     "UNet2DModel": "unet_2d",

@@ -151,6 +151,7 @@ SIGNATURES = {
     "da_conv_in_inpaint": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     "da_vae_conv_in_image": (_i, [_vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "da_vae_posterior_latents": (_i, [_vp, _ll, _ll, _ll, _vp, _vp, _vp, _vp, _vp, _i, _ll, _i, _i, _i, _f, _f, _f, _f, _vp]),
+    "da_flux_prepare_latents": (_i, [_vp, _ll, _ll, _ll, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _f, _f, _f, _f, _vp]),
     "da_plan_create": (_i, [C.POINTER(PlanOp), _i, C.POINTER(C.c_void_p)]),
     "da_plan_launch": (_i, [_vp, _vp, C.POINTER(C.c_int)]),
     "da_plan_relocate": (_i, [_vp, _i, C.POINTER(C.c_void_p), C.POINTER(C.c_ulonglong), C.POINTER(C.c_void_p),

@@ -222,6 +222,30 @@ class DiagonalGaussianDistribution:
         mode = L.POSTERIOR_MEAN if eps1 is None else L.POSTERIOR_SAMPLE
         return self._run(mode, eps1=eps1, eps2=noise, scale=scale, shift=shift, a=a, b=b)
 
+    def flux_latents(self, eps1: Optional[torch.Tensor], noise: torch.Tensor, *, batch: Optional[int] = None,
+                     scale: Optional[float] = None, shift: Optional[float] = None, a: float = 0.0, b: float = 1.0,
+                     want_image_latents: bool = False, want_noise: bool = False):
+        """Engine extension (FLUX img2img / inpainting, ops.flux_prepare_latents): ``latents`` as above, then
+        ``scheduler.scale_noise`` = ``a z + b noise`` and FluxPipeline._pack_latents, in one pass; returns the packed
+        ``(latents, image_latents or None, noise or None)``, each (B, (h/2)(w/2), 4 L).  A VAE with a quant_conv is refused.  ``batch``
+        > this distribution's: the posterior (and ``eps1``) is repeated over it, as the reference repeats the image latents."""
+        e = self._enc
+        if e.quant_w is not None:
+            raise NotImplementedError("flux_latents: VAEs with a quant_conv are not packed by the FLUX prepare kernel")
+        B = self._B if batch is None else int(batch)
+        raw, (sB, sC, sP) = self._raw, self._strides
+        if B != self._B:
+            if B % self._B:
+                raise ValueError(f"Cannot duplicate `image` of batch size {self._B} to {B} text prompts.")
+            rep = B // self._B
+            raw = torch.cat([raw] * rep, 0)              # (both layouts are contiguous per image: sB is unchanged)
+            if eps1 is not None:
+                eps1 = torch.cat([eps1] * rep, 0)
+        return ops.flux_prepare_latents(raw, (sB, sC, sP), batch=B, height=self._H, width=self._W, latent_channels=e.latent_channels,
+                                        mode=L.POSTERIOR_MEAN if eps1 is None else L.POSTERIOR_SAMPLE, eps1=eps1, noise=noise,
+                                        scale=scale, shift=shift, a=a, b=b, want_image_latents=want_image_latents,
+                                        want_noise=want_noise)
+
 
 class AutoencoderKL(PretrainedMixin):
     """Drop-in for the reference ``AutoencoderKL`` decode path (inference, bf16, HIP device only)."""

@@ -6,7 +6,7 @@ from typing import Optional
 from . import init as dinit
 from .autoencoder_kl import AutoencoderKL
 from .autoencoder_kl_wan import AutoencoderKLWan
-from .pipelines import (DDPMPipeline, FluxPipeline, StableDiffusionImg2ImgPipeline, StableDiffusionInpaintPipeline,
+from .pipelines import (DDPMPipeline, FluxImg2ImgPipeline, FluxInpaintPipeline, FluxPipeline, StableDiffusionImg2ImgPipeline, StableDiffusionInpaintPipeline,
                         StableDiffusionPipeline, StableDiffusionXLImg2ImgPipeline, StableDiffusionXLInpaintPipeline,
                         StableDiffusionXLPipeline, WanPipeline)
 from .schedulers import DDPMScheduler
@@ -110,15 +110,19 @@ def build_flux_transformer(cfg: dict, seed: int = 5, device="cuda", init_device:
     return tr, state_dict
 
 
-def build_flux_pipeline(device="cuda", tiny: bool = False, seed: int = 5, init_device: Optional[str] = None):
-    """FLUX.1-schnell (BASELINE config 4) or its tiny sibling: transformer + 16-channel VAE + FlowMatch-Euler (shift 1)."""
+def build_flux_pipeline(device="cuda", tiny: bool = False, seed: int = 5, init_device: Optional[str] = None,
+                        with_encoder: bool = False, img2img: bool = False, inpaint: bool = False):
+    """FLUX.1-schnell (BASELINE config 4) or its tiny sibling: transformer + 16-channel VAE + FlowMatch-Euler (shift 1).
+    ``with_encoder``: the VAE's encoder as well; ``img2img``: the same components in a FluxImg2ImgPipeline, ``inpaint``: in a
+    FluxInpaintPipeline (both imply ``with_encoder``)."""
     tcfg = dinit.TINY_FLUX if tiny else dinit.FLUX_SCHNELL
     vcfg = dinit.TINY_FLUX_VAE if tiny else dinit.FLUX_VAE
     idev = init_device or ("cpu" if tiny else str(device))
     tr, _ = build_flux_transformer(tcfg, seed=seed, device=device, init_device=idev)
-    vae, _ = build_vae(vcfg, seed=seed + 1, device=device, init_device=idev)
+    vae, _ = build_vae(vcfg, seed=seed + 1, device=device, init_device=idev, with_encoder=with_encoder or img2img or inpaint)
     sch = FlowMatchEulerDiscreteScheduler(shift=1.0, use_dynamic_shifting=False)
-    return FluxPipeline(scheduler=sch, vae=vae, transformer=tr)
+    cls = FluxInpaintPipeline if inpaint else FluxImg2ImgPipeline if img2img else FluxPipeline
+    return cls(scheduler=sch, vae=vae, transformer=tr)
 
 
 def build_wan_transformer(cfg: dict, seed: int = 9, device="cuda", init_device: Optional[str] = None, state_dict=None):

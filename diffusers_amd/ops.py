@@ -1385,10 +1385,17 @@ def vae_conv_in_image(img: torch.Tensor, w: torch.Tensor, bias: Optional[torch.T
 def conv_thin_out_moments(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor]):
     """The encoder's conv_out (Cin -> 2 L, 3x3) WITHOUT the NCHW layout pass of conv_thin_out: returns ``(y, (sB, sC, sP))`` --
     the implicit-GEMM result [B][H][W][THIN_OUT_PAD] (sC = 1, sP = 16) where conv_thin_out takes that route, else conv_thin_out's
-    NCHW output (sC = H W, sP = 1) -- for vae_posterior_latents to read in place.  Same values as conv_thin_out."""
+    NCHW output (sC = H W, sP = 1) -- for vae_posterior_latents to read in place.  Same values as conv_thin_out.  More than
+    THIN_OUT_PAD output channels (the 16-channel VAEs' conv_out has 2 * 16 = 32) is no thin conv: it runs on the implicit-GEMM conv
+    as it is, NHWC [B][H][W][Cout] (sC = 1, sP = Cout)."""
     _req(x, "x"), _req(w, "w")
     B, H, W_, Cin = x.shape
     Cout = w.shape[0]
+    if Cout > THIN_OUT_PAD:
+        if Cin % 64 or Cout % 4 or w.shape[1] != 9 * Cin:
+            raise ValueError(f"conv_thin_out_moments: a {Cin} -> {Cout} conv_out needs Cin % 64 == 0, Cout % 4 == 0 and a 3x3 weight "
+                             "[Cout][9 Cin] on the implicit-GEMM route")
+        return conv2d_nhwc(x, w, bias, ksize=3), (H * W_ * Cout, 1, Cout)
     if Cin % 64 == 0 and Cout <= 8 and B * H * W_ >= 4096 and w.shape[1] == 9 * Cin:
         wp, bp = pad_thin_out(w, bias)
         y16 = conv2d_nhwc(x, wp, bp, ksize=3)
@@ -1428,6 +1435,47 @@ def vae_posterior_latents(x: torch.Tensor, strides, *, batch: int, hw: int, late
                                               batch, hw, Lc, mode, flags, float(shift or 0.0), float(scale if scale is not None else 1.0),
                                               float(a), float(b), _stream()), "da_vae_posterior_latents")
     return out
+
+
+def flux_prepare_latents(x: torch.Tensor, strides, *, batch: int, height: int, width: int, latent_channels: int, mode: int,
+                         noise: torch.Tensor, eps1: Optional[torch.Tensor] = None, shift: Optional[float] = None,
+                         scale: Optional[float] = None, a: float = 0.0, b: float = 1.0, want_image_latents: bool = False,
+                         want_noise: bool = False):
+    """da_flux_prepare_latents (csrc/vae_encode.hip): the FLUX img2img / inpainting prepare_latents in one pass.  ``x``: the encoder's
+    conv_out result (2 L channels; modes POSTERIOR_MEAN / POSTERIOR_SAMPLE) or latents (L channels; POSTERIOR_NOISE) read through
+    ``strides`` = (sB, sC, sP) in elements; ``height`` x ``width``: the latent grid (both even); ``eps1`` (SAMPLE) and ``noise``: NCHW
+    bf16 [B][L][H][W]; ``a`` / ``b``: scale_noise's coefficients of the sample and of the noise.  Returns the packed bf16
+    [B][(H/2)(W/2)][4 L] tensors ``(latents, image_latents or None, noise or None)``."""
+    _req(x, "x"), _req(noise, "noise")
+    Lc, B, H, W_ = int(latent_channels), int(batch), int(height), int(width)
+    if B <= 0 or Lc <= 0 or H <= 0 or W_ <= 0 or H % 2 or W_ % 2:
+        raise ValueError(f"flux_prepare_latents: a positive batch / channel count and an even latent grid required, got B = {B}, "
+                         f"L = {Lc}, {H} x {W_}")
+    if mode not in (L.POSTERIOR_MEAN, L.POSTERIOR_SAMPLE, L.POSTERIOR_NOISE):
+        raise ValueError(f"flux_prepare_latents: mode {mode} (POSTERIOR_MEAN, POSTERIOR_SAMPLE or POSTERIOR_NOISE)")
+    sB, sC, sP = (int(v) for v in strides)
+    cin = Lc if mode == L.POSTERIOR_NOISE else 2 * Lc
+    hw = H * W_
+    last = (B - 1) * sB + (cin - 1) * sC + (hw - 1) * sP
+    if min(sB, sC, sP) < 0 or last >= x.numel():
+        raise ValueError(f"flux_prepare_latents: strides {strides} reach element {last} of a {x.numel()}-element input")
+    n_lat = B * Lc * hw
+    if (mode == L.POSTERIOR_SAMPLE) != (eps1 is not None):
+        raise ValueError("flux_prepare_latents: eps1 is the posterior noise of POSTERIOR_SAMPLE (and of no other mode)")
+    for t, nm in ((eps1, "eps1"), (noise, "noise")):
+        if t is not None:
+            _req(t, nm)
+            if t.numel() != n_lat or not t.is_contiguous():
+                raise ValueError(f"flux_prepare_latents: {nm} must be a contiguous [B][L][H][W] tensor of {n_lat} elements")
+    flags = (L.LATENTS_SHIFT if shift is not None else 0) | (L.LATENTS_SCALE if scale is not None else 0)
+    shape = (B, (H // 2) * (W_ // 2), 4 * Lc)
+    out = torch.empty(shape, device=x.device, dtype=bf16)
+    img = torch.empty(shape, device=x.device, dtype=bf16) if want_image_latents else None
+    nz = torch.empty(shape, device=x.device, dtype=bf16) if want_noise else None
+    L.check(L.load().da_flux_prepare_latents(x.data_ptr(), sB, sC, sP, _ptr(eps1), noise.data_ptr(), out.data_ptr(), _ptr(img), _ptr(nz),
+                                             B, H, W_, Lc, mode, flags, float(shift or 0.0), float(scale if scale is not None else 1.0),
+                                             float(a), float(b), _stream()), "da_flux_prepare_latents")
+    return out, img, nz
 
 
 def add_noise(x: torch.Tensor, noise: torch.Tensor, a: float, b: float) -> torch.Tensor:

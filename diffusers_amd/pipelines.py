@@ -20,6 +20,7 @@ from typing import Optional, Tuple
 import numpy as np
 import torch
 
+from . import _lib as L
 from . import ops
 from .autoencoder_kl import AutoencoderKL
 from .pipeline_loading import PipelineLoadingMixin
@@ -1389,18 +1390,24 @@ class FluxPipeline(_StepCallbacks, PipelineLoadingMixin):
         sch.step_inplace(v, latents)
         return latents
 
-    def _denoise(self, latents, pe, cond, num_steps, use_graph):
+    def _graph_key_extra(self):
+        """Addresses of static inputs a subclass's captured step reads besides the latents, embeddings and conditioning."""
+        return ()
+
+    def _denoise(self, latents, pe, cond, num_steps, use_graph, begin: int = 0):
+        """``num_steps`` steps from schedule entry ``begin`` (img2img / inpainting start past 0).  The captured step reads its row
+        through the device step counter, so every start replays the same graph: warm-up, capture and replay rewind to ``begin``."""
         sch = self.scheduler
-        sch.reset(0)
+        sch.reset(begin)
         if not use_graph:
             for i in range(num_steps):
                 with ops.weight_prefetch(_pf(self), "apply" if i else "record"):
                     self._step(latents, pe, cond)
-                if not self._after_step(i, latents):
+                if not self._after_step(i, latents, begin):
                     break
             return latents
         key = (tuple(latents.shape), tuple(pe.shape), sch.device_table.data_ptr(), sch.device_step.data_ptr(), use_graph == "plan",
-               id(self.transformer))                        # (a captured step points into THIS model's packed weights)
+               id(self.transformer)) + self._graph_key_extra()   # (a captured step points into THIS model's packed weights)
         if self._graph is None or self._graph_key != key:
             saved = latents.clone()
             s = _side_stream("warm")
@@ -1410,12 +1417,12 @@ class FluxPipeline(_StepCallbacks, PipelineLoadingMixin):
                     self._step(latents, pe, cond)      # warm-up: variant tuning + lazy one-time driver calls
             torch.cuda.current_stream().wait_stream(s)
             latents.copy_(saved)
-            sch.reset(0)
+            sch.reset(begin)
             g = _capture_step(self, lambda: self._step(latents, pe, cond), use_graph)
             self._graph, self._graph_key = g, key
             self._static = {"latents": latents, "pe": pe, "cond": cond}
             latents.copy_(saved)
-            sch.reset(0)
+            sch.reset(begin)
         else:
             st = self._static
             st["latents"].copy_(latents)
@@ -1429,20 +1436,14 @@ class FluxPipeline(_StepCallbacks, PipelineLoadingMixin):
         for i in range(num_steps):
             self._graph.replay()
             done = i + 1
-            if not self._after_step(i, latents):
+            if not self._after_step(i, latents, begin):
                 break
-        sch._step_index = done
+        sch._step_index = begin + done
         return latents
 
-    @torch.no_grad()
-    def __call__(self, prompt=None, prompt_2=None, negative_prompt=None, negative_prompt_2=None, true_cfg_scale: float = 1.0,
-                 height: Optional[int] = None, width: Optional[int] = None, num_inference_steps: int = 28, sigmas=None,
-                 guidance_scale: float = 3.5, num_images_per_prompt: int = 1, generator=None,
-                 latents: Optional[torch.Tensor] = None, prompt_embeds=None, pooled_prompt_embeds=None,
-                 negative_prompt_embeds=None, negative_pooled_prompt_embeds=None, output_type: str = "pt",
-                 return_dict: bool = True, max_sequence_length: int = 512, use_graph: bool = True,
-                 callback_on_step_end=None, callback_on_step_end_tensor_inputs=None):
-        self._arm_callback(callback_on_step_end, callback_on_step_end_tensor_inputs)      # pipeline_flux.py:626-627, :938-945
+    def _prompt_inputs(self, prompt, prompt_2, negative_prompt, num_images_per_prompt, prompt_embeds, pooled_prompt_embeds,
+                       negative_prompt_embeds, negative_pooled_prompt_embeds, max_sequence_length):
+        """``(prompt_embeds, pooled_prompt_embeds)`` of a call: encoded from ``prompt``, or taken as they were passed."""
         if prompt is not None:
             if prompt_embeds is not None:
                 raise ValueError("Cannot forward both `prompt` and `prompt_embeds`. Please make sure to only forward one "
@@ -1461,6 +1462,44 @@ class FluxPipeline(_StepCallbacks, PipelineLoadingMixin):
                              "and `pooled_prompt_embeds`.")
         if negative_prompt_embeds is not None or negative_pooled_prompt_embeds is not None or negative_prompt is not None:
             raise NotImplementedError("true-CFG (negative prompts) is not on the FLUX.1-schnell hot path")
+        return prompt_embeds, pooled_prompt_embeds
+
+    def _set_schedule(self, num_inference_steps, sigmas, seq_len, dev):
+        """pipeline_flux.py:880-907: sigmas = linspace(1, 1 / n, n), mu from the packed sequence length, the model's timesteps."""
+        n = num_inference_steps
+        sig = np.linspace(1.0, 1 / n, n) if sigmas is None else sigmas
+        sc = self.scheduler.config
+        mu = calculate_shift(seq_len, sc.get("base_image_seq_len", 256), sc.get("max_image_seq_len", 4096),
+                             sc.get("base_shift", 0.5), sc.get("max_shift", 1.15))
+        self.scheduler.set_timesteps(sigmas=sig, device=dev, mu=mu)
+        # what the transformer's sinusoid sees: timestep -> latents dtype, / 1000 (pipeline), * 1000 (model), all in bf16
+        t_model = ((self.scheduler.timesteps.to("cpu", bf16) / 1000).to(bf16) * 1000).float()
+        self.scheduler.set_model_timesteps(t_model)
+
+    def _finish(self, latents, height, width, output_type, return_dict):
+        if output_type == "latent":
+            images = latents
+        else:
+            unp = self._unpack_latents(latents, height, width, self.vae_scale_factor).contiguous()
+            vc = self.vae.config
+            images = decode_postprocessed(self.vae, unp, output_type, latents_div=float(vc.scaling_factor),
+                                          latents_add=float(vc.shift_factor or 0.0))
+        if not return_dict:
+            return (images,)
+        return PipelineOutput(images=images)
+
+    @torch.no_grad()
+    def __call__(self, prompt=None, prompt_2=None, negative_prompt=None, negative_prompt_2=None, true_cfg_scale: float = 1.0,
+                 height: Optional[int] = None, width: Optional[int] = None, num_inference_steps: int = 28, sigmas=None,
+                 guidance_scale: float = 3.5, num_images_per_prompt: int = 1, generator=None,
+                 latents: Optional[torch.Tensor] = None, prompt_embeds=None, pooled_prompt_embeds=None,
+                 negative_prompt_embeds=None, negative_pooled_prompt_embeds=None, output_type: str = "pt",
+                 return_dict: bool = True, max_sequence_length: int = 512, use_graph: bool = True,
+                 callback_on_step_end=None, callback_on_step_end_tensor_inputs=None):
+        self._arm_callback(callback_on_step_end, callback_on_step_end_tensor_inputs)      # pipeline_flux.py:626-627, :938-945
+        prompt_embeds, pooled_prompt_embeds = self._prompt_inputs(
+            prompt, prompt_2, negative_prompt, num_images_per_prompt, prompt_embeds, pooled_prompt_embeds, negative_prompt_embeds,
+            negative_pooled_prompt_embeds, max_sequence_length)
         dev = self.device
         height = height or self.default_sample_size * self.vae_scale_factor
         width = width or self.default_sample_size * self.vae_scale_factor
@@ -1481,30 +1520,222 @@ class FluxPipeline(_StepCallbacks, PipelineLoadingMixin):
         img_ids = self._prepare_latent_image_ids(lh // 2, lw // 2)
         txt_ids = torch.zeros(prompt_embeds.shape[1], 3)
 
-        n = num_inference_steps
-        sig = np.linspace(1.0, 1 / n, n) if sigmas is None else sigmas
-        sc = self.scheduler.config
-        mu = calculate_shift(latents.shape[1], sc.get("base_image_seq_len", 256), sc.get("max_image_seq_len", 4096),
-                             sc.get("base_shift", 0.5), sc.get("max_shift", 1.15))
-        self.scheduler.set_timesteps(sigmas=sig, device=dev, mu=mu)
-        # what the transformer's sinusoid sees: timestep -> latents dtype, / 1000 (pipeline), * 1000 (model), all in bf16
-        t_model = ((self.scheduler.timesteps.to("cpu", bf16) / 1000).to(bf16) * 1000).float()
-        self.scheduler.set_model_timesteps(t_model)
+        self._set_schedule(num_inference_steps, sigmas, latents.shape[1], dev)
         self.scheduler.set_begin_index(0)
 
         pe = prompt_embeds.to(device=dev, dtype=bf16).contiguous()
         cond = self.transformer.precompute_conditioning(pooled_prompt_embeds.to(device=dev, dtype=bf16), img_ids, txt_ids)
         latents = self._denoise(latents, pe, cond, len(self.scheduler.timesteps), use_graph)
-        if output_type == "latent":
-            images = latents
+        return self._finish(latents, height, width, output_type, return_dict)
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# FLUX image-to-image and inpainting (pipelines/flux/pipeline_flux_img2img.py, pipeline_flux_inpaint.py)
+# ----------------------------------------------------------------------------------------------------------------------
+def flux_get_timesteps(scheduler, num_inference_steps: int, strength: float):
+    """``get_timesteps`` of the reference's FLUX img2img / inpainting pipelines, as ``(timesteps, num_steps, begin)``.  Unlike the
+    SD / SDXL one (``get_timesteps`` above) it has no ``int()`` around the product: init_timestep = min(n strength, n) stays
+    fractional and t_start = int(max(n - init_timestep, 0)), so n = 4 at strength 0.6 runs 3 steps (SD: 2)."""
+    init_timestep = min(num_inference_steps * strength, num_inference_steps)
+    t_start = int(max(num_inference_steps - init_timestep, 0))
+    begin = t_start * scheduler.order
+    scheduler.set_begin_index(begin)
+    return scheduler.timesteps[begin:], num_inference_steps - t_start, begin
+
+
+class FluxImg2ImgPipeline(FluxPipeline):
+    """pipelines/flux/pipeline_flux_img2img.py on the engine (FLUX.1-schnell protocol, as FluxPipeline): same components, the same
+    captured step, packing, ids and decode; the loop starts at the scheduler's begin index.  The front of the call is ONE kernel
+    (ops.flux_prepare_latents): the encoder's conv_out result -> posterior sample -> (z - shift_factor) * scaling_factor ->
+    scheduler.scale_noise -> the packed tokens.  Draws on ``generator``, in the reference's order: the posterior noise of ``image``
+    (latent shape of the image batch; none when ``image`` is latents), then the noise (latent shape of the whole batch); both in
+    bf16 -- the FLUX pipelines run the VAE in the pipeline dtype and never upcast it.  ``latents=`` (B, 16, h, w) are taken as the
+    noise: moved, not re-drawn.  Not built: resizing (the image's sides set height / width), ``padding_mask_crop``, the Fill and
+    dev (guidance-embedding) checkpoints."""
+
+    def get_timesteps(self, num_inference_steps, strength, device=None):
+        ts, n, _ = flux_get_timesteps(self.scheduler, num_inference_steps, strength)
+        return ts, n
+
+    def _check_transformer(self):
+        pass
+
+    def _prepare_mask(self, mask_image, H, W_, lh, lw, batch):
+        return None
+
+    def _after_prepare(self, packed, mask):
+        return packed[0]
+
+    def _image_call(self, prompt, prompt_2, image, mask_image, height, width, padding_mask_crop, strength, num_inference_steps, sigmas,
+                    num_images_per_prompt, generator, latents, prompt_embeds, pooled_prompt_embeds, negative_prompt,
+                    negative_prompt_embeds, negative_pooled_prompt_embeds, output_type, return_dict, max_sequence_length, use_graph,
+                    callback_on_step_end, callback_on_step_end_tensor_inputs):
+        _check_strength(strength)
+        if image is None:
+            raise ValueError("`image` input cannot be undefined.")
+        if padding_mask_crop is not None:
+            raise NotImplementedError("`padding_mask_crop` (crop, resize and paste-back) is not implemented by the engine pipelines")
+        self._check_transformer()
+        self._arm_callback(callback_on_step_end, callback_on_step_end_tensor_inputs)
+        prompt_embeds, pooled_prompt_embeds = self._prompt_inputs(
+            prompt, prompt_2, negative_prompt, num_images_per_prompt, prompt_embeds, pooled_prompt_embeds, negative_prompt_embeds,
+            negative_pooled_prompt_embeds, max_sequence_length)
+        vc = self.vae.config
+        if vc.get("latents_mean") is not None or vc.get("latents_std") is not None:
+            raise NotImplementedError("AutoencoderKL configs with latents_mean / latents_std are not supported by the engine pipelines")
+        dev, f = self.device, self.vae_scale_factor
+        B = prompt_embeds.shape[0]
+        nch = self.transformer.config.in_channels // 4
+        if nch != vc.latent_channels:
+            raise NotImplementedError(f"a transformer with in_channels = {self.transformer.config.in_channels} does not read the "
+                                      f"{vc.latent_channels}-channel latents of this VAE packed 2 x 2")
+        prep = prepare_image(image, f, nch, dev)
+        if prep[0] == "latents":
+            lh, lw = prep[1].shape[-2], prep[1].shape[-1]
         else:
-            unp = self._unpack_latents(latents, height, width, self.vae_scale_factor).contiguous()
-            vc = self.vae.config
-            images = decode_postprocessed(self.vae, unp, output_type, latents_div=float(vc.scaling_factor),
-                                          latents_add=float(vc.shift_factor or 0.0))
-        if not return_dict:
-            return (images,)
-        return PipelineOutput(images=images)
+            lh, lw = prep[1].shape[-2 if prep[2] else -3] // f, prep[1].shape[-1 if prep[2] else -2] // f
+        H, W_ = lh * f, lw * f
+        if lh % 2 or lw % 2:
+            raise ValueError(f"`image` is {H} x {W_}: height and width have to be divisible by {2 * f} (the engine does not resize)")
+        if (height is not None and height != H) or (width is not None and width != W_):
+            raise ValueError(f"`height` x `width` = {height} x {width} but `image` is {H} x {W_} (the engine does not resize)")
+        mask = self._prepare_mask(mask_image, H, W_, lh, lw, B)
+        seq = (lh // 2) * (lw // 2)
+        self._set_schedule(num_inference_steps, sigmas, seq, dev)
+        n = len(self.scheduler.timesteps)
+        ts, n_steps, begin = flux_get_timesteps(self.scheduler, n, strength)
+        _no_steps(strength, n_steps)
+        a, b = self.scheduler._add_noise_coeffs(ts[:1], bf16)          # sigma of the begin index: a = bf16(1 - bf16(sigma)), b = bf16(sigma)
+
+        # (1) the posterior noise of the image, (2) the noise
+        shape = (B, nch, lh, lw)
+        want = self._inpaint_outputs()
+        if prep[0] == "latents":
+            src = _to_batch(prep[1], B, "images").contiguous()
+            noise = self._noise(shape, generator, latents, dev)
+            packed = ops.flux_prepare_latents(src, (nch * lh * lw, lh * lw, 1), batch=B, height=lh, width=lw, latent_channels=nch,
+                                              mode=L.POSTERIOR_NOISE, noise=noise, a=a[0], b=b[0], want_image_latents=want,
+                                              want_noise=want)
+        else:
+            _, img, nchw, normalize = prep
+            nimg = img.shape[0]
+            if B % nimg:
+                raise ValueError(f"Cannot duplicate `image` of batch size {nimg} to {B} text prompts.")
+            if isinstance(generator, (list, tuple)) and nimg < B:
+                img, nimg = torch.cat([img] * (B // nimg), 0), B
+            dist = self.vae.encode_image(img, nchw=nchw, normalize=normalize)
+            eps1 = dist.draw_noise(generator, dtype=bf16)
+            noise = self._noise(shape, generator, latents, dev)
+            packed = dist.flux_latents(eps1, noise, batch=B, scale=float(vc.scaling_factor),
+                                       shift=float(vc.shift_factor) if vc.get("shift_factor") is not None else None, a=a[0], b=b[0],
+                                       want_image_latents=want, want_noise=want)
+        x = self._after_prepare(packed, mask)
+        img_ids = self._prepare_latent_image_ids(lh // 2, lw // 2)
+        txt_ids = torch.zeros(prompt_embeds.shape[1], 3)
+        pe = prompt_embeds.to(device=dev, dtype=bf16).contiguous()
+        cond = self.transformer.precompute_conditioning(pooled_prompt_embeds.to(device=dev, dtype=bf16), img_ids, txt_ids)
+        x = self._denoise(x, pe, cond, n_steps, use_graph, begin=begin)
+        return self._finish(x, H, W_, output_type, return_dict)
+
+    def _inpaint_outputs(self) -> bool:
+        return False
+
+    @staticmethod
+    def _noise(shape, generator, latents, dev):
+        if latents is None:
+            return _randn(shape, generator, dev, bf16).contiguous()
+        if tuple(latents.shape) != tuple(shape):
+            raise ValueError(f"`latents` has shape {tuple(latents.shape)}, expected {tuple(shape)} (they are taken as the noise)")
+        return latents.to(device=dev, dtype=bf16).contiguous()
+
+    @torch.no_grad()
+    def __call__(self, prompt=None, prompt_2=None, image=None, height: Optional[int] = None, width: Optional[int] = None,
+                 strength: float = 0.6, num_inference_steps: int = 28, sigmas=None, guidance_scale: float = 7.0,
+                 num_images_per_prompt: int = 1, generator=None, latents: Optional[torch.Tensor] = None, prompt_embeds=None,
+                 pooled_prompt_embeds=None, negative_prompt=None, negative_prompt_embeds=None, negative_pooled_prompt_embeds=None,
+                 output_type: str = "pt", return_dict: bool = True, max_sequence_length: int = 512, use_graph: bool = True,
+                 callback_on_step_end=None, callback_on_step_end_tensor_inputs=None):
+        return self._image_call(prompt, prompt_2, image, None, height, width, None, strength, num_inference_steps, sigmas,
+                                num_images_per_prompt, generator, latents, prompt_embeds, pooled_prompt_embeds, negative_prompt,
+                                negative_prompt_embeds, negative_pooled_prompt_embeds, output_type, return_dict, max_sequence_length,
+                                use_graph, callback_on_step_end, callback_on_step_end_tensor_inputs)
+
+
+class FluxInpaintPipeline(FluxImg2ImgPipeline):
+    """pipelines/flux/pipeline_flux_inpaint.py on the engine: the img2img call, and after every scheduler step -- inside the captured
+    step, before the callbacks -- the known region is re-imposed on the packed tokens: ``(1 - mask) * scale_noise(image_latents,
+    next sigma, noise) + mask * latents`` in ONE launch (ops.inpaint_blend_ on the tensors viewed as (B, 1, S * 64)) that reads its
+    coefficients from ``scheduler.add_noise_table()`` with the device step counter: row i + 1 after step i, the clean image latents
+    after the last step.  The mask (binarised at 0.5; 1 repaints, 0 keeps) is brought to the latent grid with nearest
+    interpolation, repeated over the latent channels and packed, in torch, once per call.  The reference also encodes the masked
+    image: a 64-channel transformer never reads the result, and its posterior draw comes after every draw that reaches the output,
+    so it is not computed here.  Refused: ``padding_mask_crop``, a transformer whose in_channels != 64 (the Fill checkpoints)."""
+
+    _inpaint = None        # static inputs of the captured step: mask, image_latents, noise, table
+
+    def _check_transformer(self):
+        if self.transformer.config.in_channels != 64:
+            raise NotImplementedError(f"FluxInpaintPipeline runs a 64-channel transformer (the mask blend after every step); this one "
+                                      f"has in_channels = {self.transformer.config.in_channels} (a Fill checkpoint)")
+
+    def _inpaint_outputs(self) -> bool:
+        return True
+
+    def _prepare_mask(self, mask_image, H, W_, lh, lw, batch):
+        if mask_image is None:
+            raise ValueError("`mask_image` input cannot be undefined.")
+        mask = prepare_mask(mask_image, self.vae_scale_factor, self.device)
+        if tuple(mask.shape[-2:]) != (H, W_):
+            raise ValueError(f"`mask_image` is {mask.shape[-2]} x {mask.shape[-1]} but `image` is {H} x {W_} (the engine does not "
+                             "resize masks)")
+        nch = self.transformer.config.in_channels // 4
+        m = torch.nn.functional.interpolate(mask, size=(lh, lw)).repeat(1, nch, 1, 1)
+        if m.shape[0] != 1:
+            m = _to_batch(m, batch, "masks")
+        m = self._pack_latents(m, m.shape[0], nch, lh, lw).to(bf16)
+        return m.reshape(m.shape[0], 1, -1).contiguous()
+
+    def _after_prepare(self, packed, mask):
+        x, image_latents, noise = packed
+        new = {"mask": mask, "image_latents": image_latents, "noise": noise}
+        old = self._inpaint
+        if old is not None and all(old[k].shape == v.shape and old[k].device == v.device for k, v in new.items()):
+            for k, v in new.items():           # same shapes: refresh the captured step's static inputs in place (no re-capture)
+                old[k].copy_(v)
+        else:
+            old = self._inpaint = new
+        old["table"] = self.scheduler.add_noise_table(bf16)
+        return x
+
+    def _step(self, latents, pe, cond):
+        super()._step(latents, pe, cond)
+        st = self._inpaint
+        B = latents.shape[0]
+        ops.inpaint_blend_(latents.view(B, 1, -1), st["image_latents"].view(B, 1, -1), st["noise"].view(B, 1, -1), st["mask"],
+                           st["table"], self.scheduler.device_step)
+        return latents
+
+    def _graph_key_extra(self):
+        st = self._inpaint or {}
+        return tuple((k, st[k].data_ptr(), tuple(st[k].shape)) for k in ("mask", "image_latents", "noise", "table") if k in st)
+
+    @torch.no_grad()
+    def __call__(self, prompt=None, prompt_2=None, image=None, mask_image=None, masked_image_latents=None,
+                 height: Optional[int] = None, width: Optional[int] = None, padding_mask_crop=None, strength: float = 0.6,
+                 num_inference_steps: int = 28, sigmas=None, guidance_scale: float = 7.0, num_images_per_prompt: int = 1,
+                 generator=None, latents: Optional[torch.Tensor] = None, prompt_embeds=None, pooled_prompt_embeds=None,
+                 negative_prompt=None, negative_prompt_embeds=None, negative_pooled_prompt_embeds=None, output_type: str = "pt",
+                 return_dict: bool = True, max_sequence_length: int = 512, use_graph: bool = True, callback_on_step_end=None,
+                 callback_on_step_end_tensor_inputs=None):
+        if masked_image_latents is not None:
+            raise NotImplementedError("`masked_image_latents`: a 64-channel transformer never reads them (they feed the Fill "
+                                      "checkpoints' extra input channels, which the engine does not run)")
+        if mask_image is None:
+            raise ValueError("`mask_image` input cannot be undefined.")
+        return self._image_call(prompt, prompt_2, image, mask_image, height, width, padding_mask_crop, strength, num_inference_steps,
+                                sigmas, num_images_per_prompt, generator, latents, prompt_embeds, pooled_prompt_embeds, negative_prompt,
+                                negative_prompt_embeds, negative_pooled_prompt_embeds, output_type, return_dict, max_sequence_length,
+                                use_graph, callback_on_step_end, callback_on_step_end_tensor_inputs)
 
 
 class WanPipeline(_StepCallbacks, PipelineLoadingMixin):

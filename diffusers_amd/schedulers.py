@@ -888,6 +888,27 @@ class FlowMatchEulerDiscreteScheduler(_SchedulerBase):
             rows[i, 7] = float(ts_t[i])
         self._upload(rows, device)
 
+    def _add_noise_coeffs(self, timesteps, dtype):
+        """scale_noise (scheduling_flow_match_euler_discrete.py): ``sigma * noise + (1.0 - sigma) * sample`` with sigma cast to the
+        sample's dtype, so a = dtype(1 - dtype(sigma)) and b = dtype(sigma); sigma of the step at ``begin_index`` (img2img: before
+        the first step), at ``step_index`` (after it), or of each timestep's index when no begin index is set."""
+        sig = self.sigmas.to(device="cpu", dtype=dtype)
+        ts = torch.as_tensor(timesteps).reshape(-1).cpu()
+        if self.begin_index is None:
+            idx = [self.index_for_timestep(t) for t in ts]
+        elif self.step_index is not None:
+            idx = [self.step_index] * ts.shape[0]
+        else:
+            idx = [self.begin_index] * ts.shape[0]
+        return [float(1.0 - sig[i]) for i in idx], [float(sig[i]) for i in idx]
+
+    def scale_noise(self, sample: torch.Tensor, timestep, noise: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The reference's forward process of flow matching, ``sigma * noise + (1.0 - sigma) * sample`` on bf16 tensors (every torch
+        op's bf16 rounding kept: ops.add_noise)."""
+        if noise is None:
+            raise ValueError("FlowMatchEulerDiscreteScheduler.scale_noise: `noise` is required")
+        return self.add_noise(sample, noise, timestep)
+
     def step(self, model_output, timestep, sample, s_churn: float = 0.0, s_tmin: float = 0.0,
              s_tmax: float = float("inf"), s_noise: float = 1.0, generator=None, per_token_timesteps=None,
              return_dict: bool = True):

@@ -573,7 +573,26 @@ int da_conv_in_inpaint(const void* x, const void* mask, const void* masked, cons
  *                          NOISE (add_noise alone): z = x[c] (the input is latents, L channels), then the add_noise step.
  *                          Input element (b, channel c, pixel p) at in[b * sB + c * sC + p * sP]: NCHW (sC = HW, sP = 1) or the
  *                          NHWC channel-padded output of the implicit-GEMM conv_out (sC = 1, sP = 16).  eps1 / eps2: NCHW bf16
- *                          [B][L][HW].  L = 4 (the SD / SDXL VAE).
+ *                          [B][L][HW].  L = 4 (the SD / SDXL VAE), or L = 16 (the FLUX / SD3 VAE) with wq == bq == NULL: the
+ *                          16-channel VAEs have no quant_conv, and 32 x 32 weights per thread would spill (DA_ERR_UNSUPPORTED).
+ *   da_flux_prepare_latents  FLUX img2img / inpainting (pipeline_flux_img2img.py prepare_latents + _pack_latents,
+ *                          FlowMatchEulerDiscreteScheduler.scale_noise): the encoder's conv_out result -> the packed, noised tokens
+ *                          the transformer reads, one pass.  `in` through (sB, sC, sP) as above: 2 L channels for MEAN / SAMPLE (no
+ *                          quant_conv), L channels -- latents -- for DA_POSTERIOR_NOISE.  H x W: the latent grid, both even.  Per
+ *                          latent element, the lines above without p's quant_conv, then
+ *                            z as above (MEAN / SAMPLE; NOISE: z = x[c]), the DA_LATENTS_SHIFT / DA_LATENTS_SCALE flags applied
+ *                            x = bf16(bf16(a * z) + bf16(b * noise))          scale_noise: sigma * noise + (1.0 - sigma) * sample;
+ *                                                                             the host passes b = bf16(sigma), a = bf16(1 - b)
+ *                          Outputs, each bf16 [B][(H/2)(W/2)][4 L] in _pack_latents order (token (i, j) = row i (W/2) + j, column
+ *                          c * 4 + di * 2 + dj <- latent (c, 2 i + di, 2 j + dj)), 8-byte aligned: latents_packed <- x (required),
+ *                          image_latents_packed <- z and noise_packed <- the noise re-laid (each may be NULL).  eps1 (SAMPLE only) and
+ *                          noise: NCHW bf16 [B][L][H][W].  Any L > 0 (16 for FLUX).  DA_ERR_INVALID and no launch for: a null
+ *                          required pointer, odd H or W, a mode outside {MEAN, SAMPLE, NOISE}, SAMPLE without eps1, unknown flags,
+ *                          negative strides, misaligned outputs.
+ *                          Like da_vae_conv_in_image and da_vae_posterior_latents it runs once per call, before the loop, and has
+ *                          no DA_FN_* plan number; no existing signature or struct changed, so DA_ABI_VERSION stays 9 (a host built
+ *                          against the previous revision of this header keeps working; one that wants the new entry point looks
+ *                          the symbol up).
  * ------------------------------------------------------------------------------------------------------------------ */
 #define DA_IMAGE_F32_NCHW 0
 #define DA_IMAGE_F32_NHWC 1
@@ -589,6 +608,9 @@ int da_vae_conv_in_image(const void* x, int src, const void* w, const void* bias
 int da_vae_posterior_latents(const void* in, long long sB, long long sC, long long sP, const void* wq, const void* bq,
                              const void* eps1, const void* eps2, void* out, int B, long long HW, int L, int mode, int flags,
                              float shift, float scale, float a, float b, void* stream);
+int da_flux_prepare_latents(const void* in, long long sB, long long sC, long long sP, const void* eps1, const void* noise,
+                            void* latents_packed, void* image_latents_packed, void* noise_packed, int B, int H, int W, int L,
+                            int mode, int flags, float shift, float scale, float a, float b, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------------
  * Launch plans: a recorded sequence of the launch entry points above, owned by the library and replayed by ONE call --
