@@ -89,6 +89,17 @@ FN_IDS = {name: i + 1 for i, name in enumerate((
     "da_conv_thin_out_bf16", "da_inpaint_blend", "da_conv_in_inpaint", "da_euler_ancestral_step",
     "da_dpmpp_2m_step"))}
 FN_COUNT = len(FN_IDS) + 1
+# Launch entry points (a `void* stream` parameter) WITHOUT a DA_FN_* number.  Every one the header declares is in exactly one of
+# FN_IDS, NOT_PLANNABLE and PASS_THROUGH (tests/test_plan_marshalling_cpu.py).
+# NOT_PLANNABLE: real work of a pipeline that runs once per call, before the loop.  A plan cannot replay it, so a successful call
+# under a recording is reported like a foreign torch operator (plan.py: Plan.foreign_ops; record(strict=True) raises).
+NOT_PLANNABLE = ("da_vae_conv_in_image", "da_vae_posterior_latents", "da_flux_prepare_latents")
+# PASS_THROUGH: may run during a recording without being part of the recorded step; name -> why.
+PASS_THROUGH = {
+    "da_gemm_tune": "times trial launches of a problem; its result is a table entry, its outputs are overwritten by the real launch",
+    "da_mfma_probe": "register-only clock probe of the benchmark; writes no memory",
+    "da_plan_launch": "replays an existing plan from inside the library; plans do not nest, the recorder never sees its launches",
+}
 
 
 class PlanOp(C.Structure):

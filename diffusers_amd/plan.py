@@ -13,7 +13,9 @@ the Plan keeps alive (what graph capture does with its pool); tensors that exist
 outlive the plan -- pass them as ``keep=``.
 
 Work that is NOT a launch of this library (a stray ``torch.cat`` in the recorded code) cannot be replayed; the recorder lists
-such torch operators in ``Plan.foreign_ops`` and ``record(strict=True)`` (the default) raises on them.
+such torch operators in ``Plan.foreign_ops`` and ``record(strict=True)`` (the default) raises on them.  The same goes for the
+library's own launch entry points that have no ``DA_FN_*`` number (``_lib.NOT_PLANNABLE``: the once-per-call VAE / FLUX latent
+preparation): they run, and their names join ``foreign_ops``.
 """
 from __future__ import annotations
 
@@ -61,8 +63,9 @@ def _addr(v) -> int:
 
 
 class _Proxy:
-    """Stands in for the ctypes library while a recorder is active: launch entry points are executed and noted, everything else
-    (queries, the tuner) passes through."""
+    """Stands in for the ctypes library while a recorder is active: launch entry points are executed and noted, the launch entry
+    points a plan cannot replay (``_lib.NOT_PLANNABLE``) are executed and reported as foreign, everything else (queries, the tuner:
+    ``_lib.PASS_THROUGH``) passes through."""
 
     def __init__(self, lib, rec: "Recorder"):
         self._lib, self._rec = lib, rec
@@ -70,9 +73,17 @@ class _Proxy:
     def __getattr__(self, name):
         fn = getattr(self._lib, name)
         fid = L.FN_IDS.get(name)
-        if fid is None:
-            return fn
         rec = self._rec
+        if fid is None:
+            if name not in L.NOT_PLANNABLE:
+                return fn
+
+            def unplannable(*args):             # a launch with no DA_FN_* number: the replay would be one launch short
+                status = fn(*args)
+                if status == L.DA_OK:
+                    rec.foreign.append(name)
+                return status
+            return unplannable
 
         def call(*args):
             status = fn(*args)
@@ -190,7 +201,8 @@ class Plan:
                 elif k == "I":
                     next(host)
                 elif k == "Q":
-                    out.update((next(host)[j] or 0) for j in range(parts))
+                    arr = next(host)                # (once per argument: inside the generator it would be taken once per entry)
+                    out.update((arr[j] or 0) for j in range(parts))
         out.discard(0)
         return sorted(out)
 
@@ -397,7 +409,7 @@ def recording(strict: bool = True, private_pool: bool = True):
         if gc_was_on:
             gc.enable()
     if strict and rec.foreign:
-        raise RuntimeError(f"recorded code ran torch operators a plan cannot replay: {sorted(set(rec.foreign))}")
+        raise RuntimeError(f"recorded code ran torch operators or launches a plan cannot replay: {sorted(set(rec.foreign))}")
     if len(rec.streams) > 1:
         raise RuntimeError("recorded launches went to more than one stream; a plan replays on one")
 
