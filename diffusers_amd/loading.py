@@ -20,6 +20,7 @@ What is different here, by design:
 from __future__ import annotations
 
 import hashlib
+import itertools
 import json
 import os
 import warnings
@@ -241,10 +242,22 @@ def read_config(d: Path) -> dict:
 # ----------------------------------------------------------------------------------------------------------------------
 # the mixin
 # ----------------------------------------------------------------------------------------------------------------------
+_WEIGHTS_GENERATION = itertools.count(1)
+
+
 class PretrainedMixin:
     """``from_pretrained`` / ``fuse_lora`` / ``unfuse_lora`` for the engine's model classes."""
 
     _source: Optional[dict] = None     # {"files": [...], "device": ...}: where this model's reference-format weights live
+    _weights_generation: int = 0       # 0 = nothing loaded yet
+
+    def _new_weights_generation(self) -> None:
+        """Every ``load_state_dict`` of a denoiser comes through here: it allocates NEW packed tensors, so a step captured
+        before it (HIP graph or launch plan: raw pointers into the old ones) must not be replayed.  The pipelines' graph keys carry
+        this number, drawn from one counter for every model of the process: unlike ``id(model)`` it changes when the same object
+        is loaded again and is never handed to a second model.  ``_repack_in_place`` (fuse_lora / unfuse_lora) writes over the
+        existing tensors and leaves it alone -- captured steps follow such an edit."""
+        self._weights_generation = next(_WEIGHTS_GENERATION)
 
     @classmethod
     def from_pretrained(cls, pretrained_model_name_or_path, subfolder: Optional[str] = None, torch_dtype=None,

@@ -215,6 +215,12 @@ def _pf(pipe) -> "ops.WeightPrefetch":
     return pf
 
 
+def _weights_token(model) -> int:
+    """A captured step points into ``model``'s packed weights: the number ``load_state_dict`` gave them (loading.PretrainedMixin).
+    It changes when the same object is loaded again -- new tensors under the same ``id()`` -- and two models never share one."""
+    return model._weights_generation
+
+
 class _StepCallbacks:
     """``callback_on_step_end`` of the reference pipelines (pipeline_stable_diffusion_xl.py:857-858, :1239-1247; pipeline_stable_diffusion.py:1064-1071,
     pipeline_flux.py:938-945, pipeline_wan.py:637-644): after every denoising step -- a replayed graph, a replayed plan or an eager step alike -- the
@@ -341,8 +347,9 @@ class _LatentDiffusionBase(_StepCallbacks, PipelineLoadingMixin):
         return (tuple(latents.shape), float(guidance_scale), bool(do_cfg), cond["kvs"][0][0].skv if cond["kvs"] else 0,
                 sch.device_table.data_ptr(), sch.device_step.data_ptr(),
                 self._noise_table.data_ptr() if self._noise_table is not None else 0, float(self._eta),
-                float(self._guidance_rescale), id(self.unet),       # (a captured step points into THIS model's packed weights)
-                sch.graph_buffers(latents))                         # (DPM-Solver++: the loop's begin word, the x0 history)
+                float(self._guidance_rescale), _weights_token(self.unet),
+                sch.graph_buffers(latents),                         # (DPM-Solver++: the loop's begin word, the x0 history)
+                sch.graph_token())                                  # (the sampler kernel, scale_model_input, pred_type)
 
     def _denoise(self, latents, cond, num_steps, guidance_scale, do_cfg, use_graph, begin: int = 0):
         """``num_steps`` steps from schedule entry ``begin`` (img2img / the refiner hand-off start past 0).  The captured step reads
@@ -1394,6 +1401,12 @@ class FluxPipeline(_StepCallbacks, PipelineLoadingMixin):
         """Addresses of static inputs a subclass's captured step reads besides the latents, embeddings and conditioning."""
         return ()
 
+    def _make_graph_key(self, latents, pe):
+        """Everything a captured step depends on besides the contents of its static buffers."""
+        sch = self.scheduler
+        return (tuple(latents.shape), tuple(pe.shape), sch.device_table.data_ptr(), sch.device_step.data_ptr(),
+                _weights_token(self.transformer), sch.graph_buffers(latents), sch.graph_token()) + self._graph_key_extra()
+
     def _denoise(self, latents, pe, cond, num_steps, use_graph, begin: int = 0):
         """``num_steps`` steps from schedule entry ``begin`` (img2img / inpainting start past 0).  The captured step reads its row
         through the device step counter, so every start replays the same graph: warm-up, capture and replay rewind to ``begin``."""
@@ -1406,8 +1419,7 @@ class FluxPipeline(_StepCallbacks, PipelineLoadingMixin):
                 if not self._after_step(i, latents, begin):
                     break
             return latents
-        key = (tuple(latents.shape), tuple(pe.shape), sch.device_table.data_ptr(), sch.device_step.data_ptr(), use_graph == "plan",
-               id(self.transformer)) + self._graph_key_extra()   # (a captured step points into THIS model's packed weights)
+        key = self._make_graph_key(latents, pe) + (use_graph == "plan",)
         if self._graph is None or self._graph_key != key:
             saved = latents.clone()
             s = _side_stream("warm")
@@ -1780,6 +1792,14 @@ class WanPipeline(_StepCallbacks, PipelineLoadingMixin):
             sch.step_inplace(v, latents)
         return latents
 
+    def _make_graph_key(self, latents, cond, guidance_scale, do_cfg):
+        """Everything a captured step depends on besides the contents of its static buffers: `_step` branches on the latents'
+        dtype (fp32 under UniPC, bf16 under FlowMatch-Euler), and UniPC's step reads its coefficient table and its history."""
+        sch = self.scheduler
+        return (tuple(latents.shape), str(latents.dtype), float(guidance_scale), bool(do_cfg), cond["St"],
+                sch.device_table.data_ptr(), sch.device_step.data_ptr(), _weights_token(self.transformer),
+                sch.graph_buffers(latents), sch.graph_token())
+
     def _denoise(self, latents, cond, num_steps, guidance_scale, do_cfg, use_graph):
         sch = self.scheduler
         sch.reset(0)
@@ -1790,8 +1810,7 @@ class WanPipeline(_StepCallbacks, PipelineLoadingMixin):
                 if not self._after_step(i, latents):
                     break
             return latents
-        key = (tuple(latents.shape), float(guidance_scale), do_cfg, cond["St"], sch.device_table.data_ptr(), use_graph == "plan",
-               id(self.transformer))
+        key = self._make_graph_key(latents, cond, guidance_scale, do_cfg) + (use_graph == "plan",)
         if self._graph is None or self._graph_key != key:
             saved = latents.clone()
             s = _side_stream("warm")
@@ -1909,6 +1928,12 @@ class DDPMPipeline(PipelineLoadingMixin):
         eps = self.unet(image, None, sampler_table=sch.device_table, step_idx=sch.device_step, return_dict=False)[0]
         sch.step_inplace(eps, image, noise_table)
 
+    def _make_graph_key(self, image):
+        """Everything a captured step depends on besides the contents of its static buffers."""
+        sch = self.scheduler
+        return (tuple(image.shape), len(sch.timesteps), sch.device_table.data_ptr(), sch.device_step.data_ptr(),
+                _weights_token(self.unet), sch.graph_buffers(image), sch.graph_token())
+
     @torch.no_grad()
     def __call__(self, batch_size: int = 1, generator=None, num_inference_steps: int = 1000, output_type: str = "np",
                  return_dict: bool = True, use_graph: bool = True):
@@ -1932,7 +1957,7 @@ class DDPMPipeline(PipelineLoadingMixin):
                 with ops.weight_prefetch(_pf(self), "apply" if i else "record"):
                     self._step(image, noise_table)
         else:
-            key = (tuple(shape), len(ts), sch.device_table.data_ptr(), use_graph == "plan", id(self.unet))
+            key = self._make_graph_key(image) + (use_graph == "plan",)
             if getattr(self, "_graph_key", None) != key:
                 saved = image.clone()
                 s = _side_stream("warm")

@@ -14,6 +14,7 @@ denoising step is HIP-graph replayable.  ``step_cfg`` additionally fuses the cla
 """
 from __future__ import annotations
 
+import itertools
 import math
 from dataclasses import dataclass
 from typing import List, Optional
@@ -50,11 +51,15 @@ def _alpha_noise_coeffs(alphas_cumprod, timesteps, dtype):
     return [float(v) for v in ac[t] ** 0.5], [float(v) for v in (1 - ac[t]) ** 0.5]
 
 
+_SERIAL = itertools.count(1)     # one number per scheduler object ever built in this process (graph_token)
+
+
 class _SchedulerBase:
     order = 1
     _defaults: dict = {}
 
     def __init__(self, **kwargs):
+        self._serial = next(_SERIAL)
         unknown = set(kwargs) - set(self._defaults)
         if unknown:
             raise TypeError(f"{type(self).__name__}: unexpected config keys {sorted(unknown)}")
@@ -195,6 +200,13 @@ class _SchedulerBase:
     def graph_buffers(self, sample):
         """Engine extension: addresses of device state a captured step reads besides the table and the step counter."""
         return ()
+
+    def graph_token(self):
+        """Engine extension: what a captured step takes from this scheduler BY VALUE -- its class picks the sampler kernel and
+        ``scale_model_input``, ``_pred`` is a kernel argument -- and the object's serial.  The addresses of the table and the step
+        counter do not identify a scheduler: one built after another was dropped gets buffers of the same sizes, which the caching
+        allocator may place where the old ones were.  ``id()`` is reused the same way; the serial never is."""
+        return (type(self).__name__, self._serial, getattr(self, "_pred", None))
 
     def reset(self, index: int = 0):
         """Rewind to step ``index`` (host mirror + device counter)."""
@@ -1053,6 +1065,9 @@ class UniPCMultistepScheduler(_SchedulerBase):
         if self._hist is None or self._hist[0].shape != sample.shape or self._hist[0].dtype != sample.dtype:
             self._hist = tuple(torch.zeros_like(sample) for _ in range(3))     # last_sample, m1, m2
         return self._hist
+
+    def graph_buffers(self, sample):
+        return (self._coef.data_ptr(),) + tuple(h.data_ptr() for h in self._history(sample))
 
     def step(self, model_output, timestep, sample, return_dict: bool = True):
         if self.num_inference_steps is None:

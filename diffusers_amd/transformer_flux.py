@@ -124,6 +124,7 @@ class FluxTransformer2DModel(PretrainedMixin):
         c = self.config
         w = Weights(state_dict, device)
         self.device = torch.device(device)
+        self._new_weights_generation()
         self.time_embedder = TimestepEmbedding(w, "time_text_embed.timestep_embedder")
         self.text_embedder = TimestepEmbedding(w, "time_text_embed.text_embedder")  # Linear -> SiLU -> Linear as well
         self.context_embedder = Linear(w, "context_embedder")

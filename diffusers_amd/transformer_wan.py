@@ -103,6 +103,7 @@ class WanTransformer3DModel(PretrainedMixin):
         c = self.config
         w = Weights(state_dict, device)
         self.device = torch.device(device)
+        self._new_weights_generation()
         pw = w.get("patch_embedding.weight")
         self.patch_w = pw.reshape(pw.shape[0], -1).contiguous()        # [inner][C*pt*ph*pw]
         self.patch_b = w.get("patch_embedding.bias")

@@ -84,6 +84,7 @@ class UNet2DModel(PretrainedMixin):
         c = self.config
         w = Weights(state_dict, device)
         self.device = torch.device(device)
+        self._new_weights_generation()
         boc = tuple(c.block_out_channels)
         n = len(boc)
         groups, eps = c.norm_num_groups, c.norm_eps

@@ -110,6 +110,7 @@ class UNet2DConditionModel(PretrainedMixin):
         c = self.config
         w = Weights(state_dict, device)
         self.device = torch.device(device)
+        self._new_weights_generation()
         self._cond_cache = None   # hoisted K / V^T of the previous weights must not outlive them
         n = len(c.block_out_channels)
         boc = tuple(c.block_out_channels)
