@@ -160,32 +160,33 @@ def _capture_step(pipe, step, mode):
     in the same order, issued by `da_plan_launch` instead of the graph executor; what a host without Python replays).  `step` has
     run once already (warm-up); the caller restores the latents and the step counter afterwards, as it does after a capture."""
     if mode == "plan":
-        from . import plan as P, tuning
-        if any(v[3] > 1 for v in tuning.table().values()):
-            # split-K launches take their workspace per (device, stream); the warm-up ran on a side stream, and allocating (and
-            # zeroing) this stream's inside the recording would be a torch operator the plan cannot replay
-            ops.splitk_workspace(pipe.device, torch.cuda.current_stream().cuda_stream)
-        if ops.ATTN_SPLIT:
-            ops.attn_split_workspace(pipe.device, torch.cuda.current_stream().cuda_stream)
-        if ops.GN_MULTI:
-            ops.gn_sync_workspace(pipe.device, torch.cuda.current_stream().cuda_stream)
+        from . import plan as P
+        # the warm-up ran on a side stream, and allocating (and zeroing) this stream's workspaces inside the recording would be a
+        # torch operator the plan cannot replay
+        _stream_workspaces(pipe.device, torch.cuda.current_stream().cuda_stream)
         with ops.weight_prefetch(_pf(pipe), "apply"):
             pl, _ = P.record(step)
         return pl
     g = torch.cuda.CUDAGraph()
     cs = _side_stream("capture")
-    from . import tuning
-    if ops.ATTN_SPLIT:     # the flash kernel's key-split workspace of the capture stream: allocated (counters zeroed) BEFORE the capture
-        ops.attn_split_workspace(pipe.device, cs.cuda_stream)
-    if ops.GN_MULTI:       # likewise the multi-workgroup GroupNorm's arrival counters
-        ops.gn_sync_workspace(pipe.device, cs.cuda_stream)
-    if any(len(v) > 3 and v[3] > 1 for v in tuning.table().values()):
-        # split-K launches take their workspace per (device, stream): allocated (and its flags zeroed) for the capture stream BEFORE
-        # the capture, so that neither the allocation lands in the graph's private pool nor the zero-fill becomes a graph node
-        ops.splitk_workspace(pipe.device, cs.cuda_stream)
+    # the capture stream's workspaces: allocated (counters and flags zeroed) BEFORE the capture, so that neither the allocation
+    # lands in the graph's private pool nor the zero-fill becomes a graph node
+    _stream_workspaces(pipe.device, cs.cuda_stream)
     with torch.cuda.graph(g, stream=cs, capture_error_mode=GRAPH_CAPTURE_MODE), ops.weight_prefetch(_pf(pipe), "apply"):
         step()
     return g
+
+
+def _stream_workspaces(device, stream: int):
+    """Allocates what kernels of a step take per (device, stream), each where its path is switched on: the flash kernel's
+    key-split workspace, the multi-workgroup GroupNorm's arrival counters, the split-K workspace and flags."""
+    from . import tuning
+    if ops.ATTN_SPLIT:
+        ops.attn_split_workspace(device, stream)
+    if ops.GN_MULTI:
+        ops.gn_sync_workspace(device, stream)
+    if any(len(v) > 3 and v[3] > 1 for v in tuning.table().values()):
+        ops.splitk_workspace(device, stream)
 
 
 _side_streams = {}
@@ -219,6 +220,90 @@ def _weights_token(model) -> int:
     """A captured step points into ``model``'s packed weights: the number ``load_state_dict`` gave them (loading.PretrainedMixin).
     It changes when the same object is loaded again -- new tensors under the same ``id()`` -- and two models never share one."""
     return model._weights_generation
+
+
+def _key_tail(scheduler, model, sample) -> tuple:
+    """The part of every ``_make_graph_key`` that names the scheduler's and the model's side of a captured step: the addresses of
+    the coefficient table and of the device step counter, the generation of the packed weights, the scheduler's further device
+    state (DPM-Solver++: the loop's begin word and the x0 history; UniPC: coefficients and history) and what the step takes
+    from the scheduler by value (the sampler kernel, scale_model_input, pred_type)."""
+    return (scheduler.device_table.data_ptr(), scheduler.device_step.data_ptr(), _weights_token(model),
+            scheduler.graph_buffers(sample), scheduler.graph_token())
+
+
+def _adopt_or_refresh(old: Optional[dict], new: dict) -> dict:
+    """Static inputs a captured step reads by address: ``old`` refreshed in place with the contents of ``new`` (no re-capture)
+    when every entry matches in presence, shape and device; else ``new`` takes its place."""
+    if old is not None and all((old[k] is None) == (v is None) and (v is None or (old[k].shape == v.shape and old[k].device == v.device))
+                               for k, v in new.items()):
+        for k, v in new.items():
+            if v is not None:
+                old[k].copy_(v)
+        return old
+    return new
+
+
+class _CapturedStepLoop:
+    """The denoising loop of every pipeline: ``_step`` run eagerly, or warmed up once on a side stream, captured (HIP graph, or
+    launch plan with ``use_graph="plan"``) and replayed -- by this call and, while ``_make_graph_key`` stays equal, by later ones.
+    A pipeline supplies three hooks, each taking the loop's ``step_args`` unpacked:
+
+      _step(latents, *step_args)             one step, in place on ``latents``; per-step scalars come from the scheduler's device
+                                             table through its device step counter
+      _make_graph_key(latents, *step_args)   everything a captured step depends on besides the contents of its static buffers
+      _refresh_static(captured, new)         copies a new call's ``step_args`` into those of the captured step, ``captured``
+
+    and may override ``_after_step`` (_StepCallbacks, in front of this class in the MRO)."""
+    _graph = None          # the captured step: a torch.cuda.CUDAGraph or a plan.Plan
+    _graph_key = None
+    _static = None         # {"latents", "step_args"}: what the captured step reads and writes
+
+    def _after_step(self, i: int, latents: torch.Tensor, begin: int = 0) -> bool:
+        return True
+
+    def _denoise(self, latents, step_args: tuple, num_steps: int, use_graph, begin: int = 0):
+        """``num_steps`` steps from schedule entry ``begin`` (img2img / inpainting / the refiner hand-off start past 0).  The
+        captured step reads its row through the device step counter, so every start replays the same graph: warm-up, capture
+        and replay rewind to ``begin``."""
+        sch = self.scheduler
+        sch.reset(begin)
+        if not use_graph:
+            for i in range(num_steps):
+                with ops.weight_prefetch(_pf(self), "apply" if i else "record"):
+                    self._step(latents, *step_args)
+                if not self._after_step(i, latents, begin):
+                    break
+            return latents
+        key = self._make_graph_key(latents, *step_args) + (use_graph == "plan",)
+        if self._graph is None or self._graph_key != key:
+            # warm-up on a side stream (variant tuning; lazy one-time driver calls must not happen during capture), then capture
+            saved = latents.clone()
+            s = _side_stream("warm")
+            s.wait_stream(torch.cuda.current_stream())
+            with torch.cuda.stream(s):
+                with ops.weight_prefetch(_pf(self), "record"):
+                    self._step(latents, *step_args)
+            torch.cuda.current_stream().wait_stream(s)
+            latents.copy_(saved)
+            sch.reset(begin)
+            g = _capture_step(self, lambda: self._step(latents, *step_args), use_graph)
+            self._graph, self._graph_key = g, key
+            self._static = {"latents": latents, "step_args": step_args}
+            latents.copy_(saved)
+            sch.reset(begin)
+        else:
+            # same key: refresh the captured step's static inputs (device-to-device copies, no re-capture)
+            self._static["latents"].copy_(latents)
+            latents = self._static["latents"]
+            self._refresh_static(self._static["step_args"], step_args)
+        done = 0
+        for i in range(num_steps):
+            self._graph.replay()
+            done = i + 1
+            if not self._after_step(i, latents, begin):
+                break
+        sch._step_index = begin + done
+        return latents
 
 
 class _StepCallbacks:
@@ -267,15 +352,13 @@ class PipelineOutput:
     images: torch.Tensor
 
 
-class _LatentDiffusionBase(_StepCallbacks, PipelineLoadingMixin):
+class _LatentDiffusionBase(_StepCallbacks, _CapturedStepLoop, PipelineLoadingMixin):
     def __init__(self, vae: AutoencoderKL, unet: UNet2DConditionModel, scheduler):
         self.vae, self.unet, self.scheduler = vae, unet, scheduler
         self.vae_scale_factor = 2 ** (len(vae.config.block_out_channels) - 1) if vae is not None else 8
-        self._graph = None
-        self._graph_key = None
-        self._static = {}
         self._eta = 0.0            # DDIM only: eta > 0 adds pre-drawn variance noise (one row per step) in the fused step
         self._noise_table = None   # [num_inference_steps, *latents.shape]: DDIM eta > 0, or a stochastic sampler (_draw_step_noise)
+        self._noise_buffer = None  # the table's storage, kept over the calls that need none (_fill_noise_table)
         self._guidance_rescale = 0.0   # > 0: rescale_noise_cfg after the CFG combine (pipeline_stable_diffusion.py:69-92)
 
     @property
@@ -320,20 +403,23 @@ class _LatentDiffusionBase(_StepCallbacks, PipelineLoadingMixin):
         come here after every other draw of the call (initial latents, img2img / inpainting noise, the VAE posterior sample),
         which is where the reference's loop would start consuming the generator -- into rows ``begin ... begin + n_steps - 1``
         of a ``[num_inference_steps, *latents.shape]`` table in the latents' dtype (= the model output's); the fused step picks its
-        row with the device step counter, so it stays graph-replayable.  The table is refilled in place while its shape is
-        unchanged: captured graphs keep its address (``_make_graph_key`` carries it)."""
-        if not getattr(self.scheduler, "needs_step_noise", False):
-            if self._eta == 0.0:
-                self._noise_table = None
-            return
+        row with the device step counter, so it stays graph-replayable (``_fill_noise_table``)."""
+        if getattr(self.scheduler, "needs_step_noise", False):
+            self._fill_noise_table(latents, generator, num_inference_steps, n_steps, begin)
+        elif self._eta == 0.0:
+            self._noise_table = None
+
+    def _fill_noise_table(self, latents, generator, num_inference_steps: int, n_steps: int, begin: int = 0):
+        """Rows ``begin ... begin + n_steps - 1`` of the ``[num_inference_steps, *latents.shape]`` noise table, drawn in step order
+        from ``generator`` (``_randn``) in the latents' dtype.  The table is refilled in place while its shape, dtype and device
+        are unchanged: captured steps keep its address (``_make_graph_key`` carries it)."""
         dev = latents.device
         shape = (int(num_inference_steps),) + tuple(latents.shape)
-        table = self._static.get("noise_table")
+        table = self._noise_buffer
         if table is None or tuple(table.shape) != shape or table.dtype != latents.dtype or table.device != dev:
-            table = torch.zeros(shape, device=dev, dtype=latents.dtype)
+            table = self._noise_buffer = torch.zeros(shape, device=dev, dtype=latents.dtype)
         for i in range(n_steps):
             table[begin + i].copy_(_randn(latents.shape, generator, dev, latents.dtype))
-        self._static["noise_table"] = table
         self._noise_table = table
 
     def _make_graph_key(self, latents, cond, guidance_scale, do_cfg):
@@ -345,60 +431,17 @@ class _LatentDiffusionBase(_StepCallbacks, PipelineLoadingMixin):
             # then run deterministic DDIM whatever eta the caller passed)
             sch._ensure(self._eta, sch.timesteps[0])
         return (tuple(latents.shape), float(guidance_scale), bool(do_cfg), cond["kvs"][0][0].skv if cond["kvs"] else 0,
-                sch.device_table.data_ptr(), sch.device_step.data_ptr(),
                 self._noise_table.data_ptr() if self._noise_table is not None else 0, float(self._eta),
-                float(self._guidance_rescale), _weights_token(self.unet),
-                sch.graph_buffers(latents),                         # (DPM-Solver++: the loop's begin word, the x0 history)
-                sch.graph_token())                                  # (the sampler kernel, scale_model_input, pred_type)
+                float(self._guidance_rescale)) + _key_tail(sch, self.unet, latents)
 
-    def _denoise(self, latents, cond, num_steps, guidance_scale, do_cfg, use_graph, begin: int = 0):
-        """``num_steps`` steps from schedule entry ``begin`` (img2img / the refiner hand-off start past 0).  The captured step reads
-        its row from the device step counter, so every start replays the same graph: warm-up, capture and replay rewind to ``begin``."""
-        sch = self.scheduler
-        sch.reset(begin)
-        if not use_graph:
-            for i in range(num_steps):
-                with ops.weight_prefetch(_pf(self), "apply" if i else "record"):
-                    self._step(latents, cond, guidance_scale, do_cfg)
-                if not self._after_step(i, latents, begin):
-                    break
-            return latents
-        key = self._make_graph_key(latents, cond, guidance_scale, do_cfg) + (use_graph == "plan",)
-        if self._graph is None or self._graph_key != key:
-            # warm-up on a side stream (lazy one-time driver calls must not happen during capture), then capture
-            saved = latents.clone()
-            s = _side_stream("warm")
-            s.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(s):
-                with ops.weight_prefetch(_pf(self), "record"):
-                    self._step(latents, cond, guidance_scale, do_cfg)
-            torch.cuda.current_stream().wait_stream(s)
-            latents.copy_(saved)
-            sch.reset(begin)
-            g = _capture_step(self, lambda: self._step(latents, cond, guidance_scale, do_cfg), use_graph)
-            self._graph, self._graph_key = g, key
-            self._static = {"latents": latents, "cond": cond, "noise_table": self._noise_table}
-            latents.copy_(saved)
-            sch.reset(begin)
-        else:
-            # same shapes: refresh the graph's static inputs (device-to-device copies, no re-capture)
-            self._static["latents"].copy_(latents)
-            latents = self._static["latents"]
-            old = self._static["cond"]
-            for kv_old, kv_new in zip(old["kvs"], cond["kvs"]):
-                for a, b in zip(kv_old, kv_new):
-                    a.k.copy_(b.k)
-                    a.vt.copy_(b.vt)
-            if old["aug_emb"] is not None:
-                old["aug_emb"].copy_(cond["aug_emb"])
-        done = 0
-        for i in range(num_steps):
-            self._graph.replay()
-            done = i + 1
-            if not self._after_step(i, latents, begin):
-                break
-        sch._step_index = begin + done
-        return latents
+    def _refresh_static(self, captured, new):
+        old, cond = captured[0], new[0]
+        for kv_old, kv_new in zip(old["kvs"], cond["kvs"]):
+            for a, b in zip(kv_old, kv_new):
+                a.k.copy_(b.k)
+                a.vt.copy_(b.vt)
+        if old["aug_emb"] is not None:
+            old["aug_emb"].copy_(cond["aug_emb"])
 
     def _decode(self, latents, output_type):
         if output_type == "latent":
@@ -518,7 +561,7 @@ class StableDiffusionXLPipeline(_LatentDiffusionBase):
             ids = torch.cat([ids, ids], dim=0)
         cond = self.unet.precompute_conditioning(pe.contiguous(), {"text_embeds": te, "time_ids": ids})
         self._draw_step_noise(latents, generator, len(self.scheduler.timesteps), num_inference_steps)
-        latents = self._denoise(latents, cond, num_inference_steps, guidance_scale, do_cfg, use_graph)
+        latents = self._denoise(latents, (cond, guidance_scale, do_cfg), num_inference_steps, use_graph)
         images = self._decode(latents, output_type)
         if not return_dict:
             return (images,)
@@ -541,6 +584,16 @@ class StableDiffusionPipeline(_LatentDiffusionBase):
             raise ValueError("`prompt=` needs the pipeline's tokenizer / text_encoder; without them pass `prompt_embeds`")
         return encode_prompt_sd(self.tokenizer, self.text_encoder, prompt, device or self.device, num_images_per_prompt,
                                 do_classifier_free_guidance, negative_prompt, clip_skip)
+
+    def _set_eta(self, eta, latents, generator, num_inference_steps, n_steps, begin):
+        """DDIM's eta for a loop of ``n_steps`` steps from schedule entry ``begin``.  The reference draws the variance noise of a
+        step inside scheduler.step (scheduling_ddim.py:500-507), from ``generator`` in the latents' dtype: the same draws, in the
+        same order, are made up front into the rows the device step counter selects, so the step stays graph-replayable."""
+        self._eta, self._noise_table = float(eta), None
+        if eta > 0:
+            if not hasattr(self.scheduler, "_get_variance"):
+                raise ValueError("eta > 0 is a DDIMScheduler option")
+            self._fill_noise_table(latents, generator, num_inference_steps, n_steps, begin)
 
     @torch.no_grad()
     def __call__(self, prompt=None, height: Optional[int] = None, width: Optional[int] = None,
@@ -585,24 +638,12 @@ class StableDiffusionPipeline(_LatentDiffusionBase):
         if do_cfg:
             pe = torch.cat([negative_prompt_embeds.to(device=dev, dtype=bf16), pe], dim=0)
         cond = self.unet.precompute_conditioning(pe.contiguous(), None)
-        self._eta, self._noise_table = float(eta), None
-        if eta > 0:
-            if not hasattr(self.scheduler, "_get_variance"):
-                raise ValueError("eta > 0 is a DDIMScheduler option (pipeline_stable_diffusion.py:608-625 passes it only "
-                                 "to schedulers whose step() accepts it)")
-            # the reference draws one randn per step inside scheduler.step (scheduling_ddim.py:500-507), from `generator`
-            # in the latents dtype: same draws, in the same order, made up front so the step stays graph-replayable
-            gdev = generator.device if generator is not None else dev
-            draws = [torch.randn(latents.shape, generator=generator, device=gdev, dtype=bf16)
-                     for _ in range(num_inference_steps)]
-            table = torch.stack(draws).to(dev).contiguous()
-            if self._static.get("noise_table") is not None and self._static["noise_table"].shape == table.shape:
-                self._static["noise_table"].copy_(table)       # keep the address the captured graph reads
-                table = self._static["noise_table"]
-            self._static["noise_table"] = table
-            self._noise_table = table
+        if eta > 0 and not hasattr(self.scheduler, "_get_variance"):
+            raise ValueError("eta > 0 is a DDIMScheduler option (pipeline_stable_diffusion.py:608-625 passes it only "
+                             "to schedulers whose step() accepts it)")
+        self._set_eta(eta, latents, generator, num_inference_steps, num_inference_steps, 0)
         self._draw_step_noise(latents, generator, num_inference_steps, num_inference_steps)
-        latents = self._denoise(latents, cond, num_inference_steps, guidance_scale, do_cfg, use_graph)
+        latents = self._denoise(latents, (cond, guidance_scale, do_cfg), num_inference_steps, use_graph)
         images = self._decode(latents, output_type)
         if not return_dict:
             return (images,)
@@ -880,7 +921,7 @@ class StableDiffusionXLImg2ImgPipeline(_Img2ImgMixin, StableDiffusionXLPipeline)
             ids = torch.cat([neg_ids.to(dev).repeat(B, 1), ids], dim=0)
         cond = self.unet.precompute_conditioning(pe.contiguous(), {"text_embeds": te, "time_ids": ids})
         self._draw_step_noise(latents, generator, num_inference_steps, n_steps, begin)
-        latents = self._denoise(latents, cond, n_steps, guidance_scale, do_cfg, use_graph, begin=begin)
+        latents = self._denoise(latents, (cond, guidance_scale, do_cfg), n_steps, use_graph, begin=begin)
         images = self._decode(latents, output_type)
         if not return_dict:
             return (images,)
@@ -889,24 +930,6 @@ class StableDiffusionXLImg2ImgPipeline(_Img2ImgMixin, StableDiffusionXLPipeline)
 
 class StableDiffusionImg2ImgPipeline(_Img2ImgMixin, StableDiffusionPipeline):
     """pipeline_stable_diffusion_img2img.py (__call__ :860-1132): SD1.5 img2img on the engine (DDIM by default, eta included)."""
-
-    def _set_eta(self, eta, latents, generator, num_inference_steps, n_steps, begin):
-        """DDIM's eta for a loop of ``n_steps`` steps from schedule entry ``begin``: the per-step variance noise, pre-drawn."""
-        dev = self.device
-        self._eta, self._noise_table = float(eta), None
-        if eta > 0:
-            if not hasattr(self.scheduler, "_get_variance"):
-                raise ValueError("eta > 0 is a DDIMScheduler option")
-            # one draw per step that runs, in order (scheduling_ddim.py:500-507), in the rows the device step counter selects
-            gdev = generator.device if generator is not None else dev
-            table = torch.zeros((num_inference_steps,) + tuple(latents.shape), device=dev, dtype=bf16)
-            for i in range(n_steps):
-                table[begin + i] = torch.randn(latents.shape, generator=generator, device=gdev, dtype=bf16).to(dev)
-            if self._static.get("noise_table") is not None and self._static["noise_table"].shape == table.shape:
-                self._static["noise_table"].copy_(table)
-                table = self._static["noise_table"]
-            self._static["noise_table"] = table
-            self._noise_table = table
 
     @torch.no_grad()
     def __call__(self, prompt=None, image=None, strength: float = 0.8, num_inference_steps: int = 50, timesteps=None,
@@ -955,7 +978,7 @@ class StableDiffusionImg2ImgPipeline(_Img2ImgMixin, StableDiffusionPipeline):
         cond = self.unet.precompute_conditioning(pe.contiguous(), None)
         self._set_eta(eta, latents, generator, num_inference_steps, n_steps, begin)
         self._draw_step_noise(latents, generator, num_inference_steps, n_steps, begin)
-        latents = self._denoise(latents, cond, n_steps, guidance_scale, do_cfg, use_graph, begin=begin)
+        latents = self._denoise(latents, (cond, guidance_scale, do_cfg), n_steps, use_graph, begin=begin)
         images = self._decode(latents, output_type)
         if not return_dict:
             return (images,)
@@ -1134,17 +1157,10 @@ class _InpaintMixin:
             mask_lat, masked = _to_batch(mask_lat, batch, "masks"), _to_batch(masked, batch, "images")
         elif mask_lat.shape[0] != 1:
             mask_lat = _to_batch(mask_lat, batch, "masks")
-        new = {"mask": mask_lat.contiguous(), "image_latents": image_latents, "noise": noise.contiguous(),
-               "masked": masked.contiguous() if masked is not None else None}
-        old = self._inpaint
-        if old is not None and all((old[k] is None) == (v is None) and (v is None or (old[k].shape == v.shape and old[k].device == v.device))
-                                   for k, v in new.items()):
-            for k, v in new.items():           # same shapes: refresh the captured step's static inputs in place (no re-capture)
-                if v is not None:
-                    old[k].copy_(v)
-        else:
-            old = self._inpaint = new
-        old["table"] = self.scheduler.add_noise_table(bf16) if nu == 4 else None
+        st = self._inpaint = _adopt_or_refresh(self._inpaint, {
+            "mask": mask_lat.contiguous(), "image_latents": image_latents, "noise": noise.contiguous(),
+            "masked": masked.contiguous() if masked is not None else None})
+        st["table"] = self.scheduler.add_noise_table(bf16) if nu == 4 else None
         return start.contiguous()
 
     def _predict_noise(self, latents, cond, do_cfg):
@@ -1229,7 +1245,7 @@ class StableDiffusionInpaintPipeline(_InpaintMixin, StableDiffusionImg2ImgPipeli
         cond = self.unet.precompute_conditioning(pe.contiguous(), None)
         self._set_eta(eta, latents, generator, num_inference_steps, n_steps, begin)
         self._draw_step_noise(latents, generator, num_inference_steps, n_steps, begin)
-        latents = self._denoise(latents, cond, n_steps, guidance_scale, do_cfg, use_graph, begin=begin)
+        latents = self._denoise(latents, (cond, guidance_scale, do_cfg), n_steps, use_graph, begin=begin)
         images = self._decode(latents, output_type)
         if not return_dict:
             return (images,)
@@ -1329,7 +1345,7 @@ class StableDiffusionXLInpaintPipeline(_InpaintMixin, StableDiffusionXLImg2ImgPi
             ids = torch.cat([neg_ids.to(dev).repeat(B, 1), ids], dim=0)
         cond = self.unet.precompute_conditioning(pe.contiguous(), {"text_embeds": te, "time_ids": ids})
         self._draw_step_noise(latents, generator, num_inference_steps, n_steps, begin)
-        latents = self._denoise(latents, cond, n_steps, guidance_scale, do_cfg, use_graph, begin=begin)
+        latents = self._denoise(latents, (cond, guidance_scale, do_cfg), n_steps, use_graph, begin=begin)
         images = self._decode(latents, output_type)
         if not return_dict:
             return (images,)
@@ -1344,7 +1360,7 @@ def calculate_shift(image_seq_len, base_seq_len: int = 256, max_seq_len: int = 4
     return image_seq_len * m + b
 
 
-class FluxPipeline(_StepCallbacks, PipelineLoadingMixin):
+class FluxPipeline(_StepCallbacks, _CapturedStepLoop, PipelineLoadingMixin):
     """pipelines/flux/pipeline_flux.py:654-980 for pre-computed prompt embeddings (FLUX.1-schnell protocol: no true-CFG,
     no guidance embedding).  The step body -- transformer forward + FlowMatch-Euler update -- is captured once in a HIP
     graph and replayed; latents stay in the packed (B, (h/2)(w/2), 64) layout of the reference throughout the loop."""
@@ -1357,9 +1373,6 @@ class FluxPipeline(_StepCallbacks, PipelineLoadingMixin):
         self.text_encoder_2, self.tokenizer_2 = text_encoder_2, tokenizer_2
         self.vae_scale_factor = 2 ** (len(vae.config.block_out_channels) - 1) if vae is not None else 8
         self.default_sample_size = 128
-        self._graph = None
-        self._graph_key = None
-        self._static = {}
 
     @property
     def device(self):
@@ -1401,57 +1414,18 @@ class FluxPipeline(_StepCallbacks, PipelineLoadingMixin):
         """Addresses of static inputs a subclass's captured step reads besides the latents, embeddings and conditioning."""
         return ()
 
-    def _make_graph_key(self, latents, pe):
-        """Everything a captured step depends on besides the contents of its static buffers."""
-        sch = self.scheduler
-        return (tuple(latents.shape), tuple(pe.shape), sch.device_table.data_ptr(), sch.device_step.data_ptr(),
-                _weights_token(self.transformer), sch.graph_buffers(latents), sch.graph_token()) + self._graph_key_extra()
+    def _make_graph_key(self, latents, pe, cond=None):
+        """Everything a captured step depends on besides the contents of its static buffers (the conditioning is one of them)."""
+        return ((tuple(latents.shape), tuple(pe.shape)) + _key_tail(self.scheduler, self.transformer, latents)
+                + self._graph_key_extra())
 
-    def _denoise(self, latents, pe, cond, num_steps, use_graph, begin: int = 0):
-        """``num_steps`` steps from schedule entry ``begin`` (img2img / inpainting start past 0).  The captured step reads its row
-        through the device step counter, so every start replays the same graph: warm-up, capture and replay rewind to ``begin``."""
-        sch = self.scheduler
-        sch.reset(begin)
-        if not use_graph:
-            for i in range(num_steps):
-                with ops.weight_prefetch(_pf(self), "apply" if i else "record"):
-                    self._step(latents, pe, cond)
-                if not self._after_step(i, latents, begin):
-                    break
-            return latents
-        key = self._make_graph_key(latents, pe) + (use_graph == "plan",)
-        if self._graph is None or self._graph_key != key:
-            saved = latents.clone()
-            s = _side_stream("warm")
-            s.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(s):
-                with ops.weight_prefetch(_pf(self), "record"):
-                    self._step(latents, pe, cond)      # warm-up: variant tuning + lazy one-time driver calls
-            torch.cuda.current_stream().wait_stream(s)
-            latents.copy_(saved)
-            sch.reset(begin)
-            g = _capture_step(self, lambda: self._step(latents, pe, cond), use_graph)
-            self._graph, self._graph_key = g, key
-            self._static = {"latents": latents, "pe": pe, "cond": cond}
-            latents.copy_(saved)
-            sch.reset(begin)
-        else:
-            st = self._static
-            st["latents"].copy_(latents)
-            st["pe"].copy_(pe)
-            st["cond"]["pooled_emb"].copy_(cond["pooled_emb"])
-            if st["cond"]["cos"] is not cond["cos"]:     # a different id grid of the same size (e.g. HxW after WxH)
-                st["cond"]["cos"].copy_(cond["cos"])
-                st["cond"]["sin"].copy_(cond["sin"])
-            latents = st["latents"]
-        done = 0
-        for i in range(num_steps):
-            self._graph.replay()
-            done = i + 1
-            if not self._after_step(i, latents, begin):
-                break
-        sch._step_index = begin + done
-        return latents
+    def _refresh_static(self, captured, new):
+        (pe0, cond0), (pe, cond) = captured, new
+        pe0.copy_(pe)
+        cond0["pooled_emb"].copy_(cond["pooled_emb"])
+        if cond0["cos"] is not cond["cos"]:     # a different id grid of the same size (e.g. HxW after WxH)
+            cond0["cos"].copy_(cond["cos"])
+            cond0["sin"].copy_(cond["sin"])
 
     def _prompt_inputs(self, prompt, prompt_2, negative_prompt, num_images_per_prompt, prompt_embeds, pooled_prompt_embeds,
                        negative_prompt_embeds, negative_pooled_prompt_embeds, max_sequence_length):
@@ -1537,7 +1511,7 @@ class FluxPipeline(_StepCallbacks, PipelineLoadingMixin):
 
         pe = prompt_embeds.to(device=dev, dtype=bf16).contiguous()
         cond = self.transformer.precompute_conditioning(pooled_prompt_embeds.to(device=dev, dtype=bf16), img_ids, txt_ids)
-        latents = self._denoise(latents, pe, cond, len(self.scheduler.timesteps), use_graph)
+        latents = self._denoise(latents, (pe, cond), len(self.scheduler.timesteps), use_graph)
         return self._finish(latents, height, width, output_type, return_dict)
 
 
@@ -1646,7 +1620,7 @@ class FluxImg2ImgPipeline(FluxPipeline):
         txt_ids = torch.zeros(prompt_embeds.shape[1], 3)
         pe = prompt_embeds.to(device=dev, dtype=bf16).contiguous()
         cond = self.transformer.precompute_conditioning(pooled_prompt_embeds.to(device=dev, dtype=bf16), img_ids, txt_ids)
-        x = self._denoise(x, pe, cond, n_steps, use_graph, begin=begin)
+        x = self._denoise(x, (pe, cond), n_steps, use_graph, begin=begin)
         return self._finish(x, H, W_, output_type, return_dict)
 
     def _inpaint_outputs(self) -> bool:
@@ -1709,14 +1683,8 @@ class FluxInpaintPipeline(FluxImg2ImgPipeline):
 
     def _after_prepare(self, packed, mask):
         x, image_latents, noise = packed
-        new = {"mask": mask, "image_latents": image_latents, "noise": noise}
-        old = self._inpaint
-        if old is not None and all(old[k].shape == v.shape and old[k].device == v.device for k, v in new.items()):
-            for k, v in new.items():           # same shapes: refresh the captured step's static inputs in place (no re-capture)
-                old[k].copy_(v)
-        else:
-            old = self._inpaint = new
-        old["table"] = self.scheduler.add_noise_table(bf16)
+        st = self._inpaint = _adopt_or_refresh(self._inpaint, {"mask": mask, "image_latents": image_latents, "noise": noise})
+        st["table"] = self.scheduler.add_noise_table(bf16)
         return x
 
     def _step(self, latents, pe, cond):
@@ -1750,7 +1718,7 @@ class FluxInpaintPipeline(FluxImg2ImgPipeline):
                                 use_graph, callback_on_step_end, callback_on_step_end_tensor_inputs)
 
 
-class WanPipeline(_StepCallbacks, PipelineLoadingMixin):
+class WanPipeline(_StepCallbacks, _CapturedStepLoop, PipelineLoadingMixin):
     """pipelines/wan/pipeline_wan.py:380-700 (Wan 2.1 T2V) for pre-computed prompt embeddings: the denoising loop.
     The reference runs the transformer twice per step (cond / uncond, :613-632); here the two are one batch-2 call
     (identical arithmetic per sample, twice the GEMM M) and ``uncond + g (cond - uncond)`` is fused into the FlowMatch
@@ -1766,9 +1734,6 @@ class WanPipeline(_StepCallbacks, PipelineLoadingMixin):
         self.scheduler, self.transformer, self.vae = scheduler, transformer, vae
         self.text_encoder, self.tokenizer = text_encoder, tokenizer          # optional caller-side transformers modules
         self.vae_scale_factor_temporal, self.vae_scale_factor_spatial = 4, 8
-        self._graph = None
-        self._graph_key = None
-        self._static = {}
 
     @property
     def device(self):
@@ -1795,52 +1760,13 @@ class WanPipeline(_StepCallbacks, PipelineLoadingMixin):
     def _make_graph_key(self, latents, cond, guidance_scale, do_cfg):
         """Everything a captured step depends on besides the contents of its static buffers: `_step` branches on the latents'
         dtype (fp32 under UniPC, bf16 under FlowMatch-Euler), and UniPC's step reads its coefficient table and its history."""
-        sch = self.scheduler
-        return (tuple(latents.shape), str(latents.dtype), float(guidance_scale), bool(do_cfg), cond["St"],
-                sch.device_table.data_ptr(), sch.device_step.data_ptr(), _weights_token(self.transformer),
-                sch.graph_buffers(latents), sch.graph_token())
+        return (tuple(latents.shape), str(latents.dtype), float(guidance_scale), bool(do_cfg),
+                cond["St"]) + _key_tail(self.scheduler, self.transformer, latents)
 
-    def _denoise(self, latents, cond, num_steps, guidance_scale, do_cfg, use_graph):
-        sch = self.scheduler
-        sch.reset(0)
-        if not use_graph:
-            for i in range(num_steps):
-                with ops.weight_prefetch(_pf(self), "apply" if i else "record"):
-                    self._step(latents, cond, guidance_scale, do_cfg)
-                if not self._after_step(i, latents):
-                    break
-            return latents
-        key = self._make_graph_key(latents, cond, guidance_scale, do_cfg) + (use_graph == "plan",)
-        if self._graph is None or self._graph_key != key:
-            saved = latents.clone()
-            s = _side_stream("warm")
-            s.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(s):
-                with ops.weight_prefetch(_pf(self), "record"):
-                    self._step(latents, cond, guidance_scale, do_cfg)
-            torch.cuda.current_stream().wait_stream(s)
-            latents.copy_(saved)
-            sch.reset(0)
-            g = _capture_step(self, lambda: self._step(latents, cond, guidance_scale, do_cfg), use_graph)
-            self._graph, self._graph_key = g, key
-            self._static = {"latents": latents, "cond": cond}
-            latents.copy_(saved)
-            sch.reset(0)
-        else:
-            st = self._static
-            st["latents"].copy_(latents)
-            for (k0, v0), (k1, v1) in zip(st["cond"]["kvs"], cond["kvs"]):
-                k0.copy_(k1)
-                v0.copy_(v1)
-            latents = st["latents"]
-        done = 0
-        for i in range(num_steps):
-            self._graph.replay()
-            done = i + 1
-            if not self._after_step(i, latents):
-                break
-        sch._step_index = done
-        return latents
+    def _refresh_static(self, captured, new):
+        for (k0, v0), (k1, v1) in zip(captured[0]["kvs"], new[0]["kvs"]):
+            k0.copy_(k1)
+            v0.copy_(v1)
 
     @torch.no_grad()
     def __call__(self, prompt=None, negative_prompt=None, height: int = 480, width: int = 832, num_frames: int = 81,
@@ -1894,7 +1820,7 @@ class WanPipeline(_StepCallbacks, PipelineLoadingMixin):
         if do_cfg:
             pe = torch.cat([negative_prompt_embeds.to(device=dev, dtype=bf16), pe], dim=0)   # [uncond ; cond]
         cond = self.transformer.precompute_conditioning(pe.contiguous())
-        latents = self._denoise(latents, cond, len(self.scheduler.timesteps), guidance_scale, do_cfg, use_graph)
+        latents = self._denoise(latents, (cond, guidance_scale, do_cfg), len(self.scheduler.timesteps), use_graph)
         if output_type != "latent":
             with _exclusive_decode():
                 video = self.vae.decode(latents, return_dict=False, denormalize=True)[0]        # [B][3][F][H][W]
@@ -1907,7 +1833,7 @@ class WanPipeline(_StepCallbacks, PipelineLoadingMixin):
         return PipelineOutput(images=latents)
 
 
-class DDPMPipeline(PipelineLoadingMixin):
+class DDPMPipeline(_CapturedStepLoop, PipelineLoadingMixin):
     """pipelines/ddpm/pipeline_ddpm.py:40-130: unconditional ancestral sampling.  The initial image and the per-step
     variance noise are drawn on the host from ``generator`` in fp32 in the reference's order (initial image first, then
     one draw per step with t > 0) and rounded to bf16, so a seeded run consumes the same random stream as the
@@ -1928,11 +1854,12 @@ class DDPMPipeline(PipelineLoadingMixin):
         eps = self.unet(image, None, sampler_table=sch.device_table, step_idx=sch.device_step, return_dict=False)[0]
         sch.step_inplace(eps, image, noise_table)
 
-    def _make_graph_key(self, image):
-        """Everything a captured step depends on besides the contents of its static buffers."""
-        sch = self.scheduler
-        return (tuple(image.shape), len(sch.timesteps), sch.device_table.data_ptr(), sch.device_step.data_ptr(),
-                _weights_token(self.unet), sch.graph_buffers(image), sch.graph_token())
+    def _make_graph_key(self, image, noise_table=None):
+        """Everything a captured step depends on besides the contents of its static buffers (the noise table is one of them)."""
+        return (tuple(image.shape), len(self.scheduler.timesteps)) + _key_tail(self.scheduler, self.unet, image)
+
+    def _refresh_static(self, captured, new):
+        captured[0].copy_(new[0])
 
     @torch.no_grad()
     def __call__(self, batch_size: int = 1, generator=None, num_inference_steps: int = 1000, output_type: str = "np",
@@ -1951,35 +1878,7 @@ class DDPMPipeline(PipelineLoadingMixin):
         draws = [torch.randn(shape, generator=generator, device=gdev, dtype=torch.float32) if t > 0 else
                  torch.zeros(shape, dtype=torch.float32, device=gdev) for t in ts]
         noise_table = torch.stack(draws).to(device=dev, dtype=bf16).contiguous()
-        sch.reset(0)
-        if not use_graph:
-            for i, _ in enumerate(ts):
-                with ops.weight_prefetch(_pf(self), "apply" if i else "record"):
-                    self._step(image, noise_table)
-        else:
-            key = self._make_graph_key(image) + (use_graph == "plan",)
-            if getattr(self, "_graph_key", None) != key:
-                saved = image.clone()
-                s = _side_stream("warm")
-                s.wait_stream(torch.cuda.current_stream())
-                with torch.cuda.stream(s):
-                    with ops.weight_prefetch(_pf(self), "record"):
-                        self._step(image, noise_table)          # warm-up: variant tuning, lazy driver calls
-                torch.cuda.current_stream().wait_stream(s)
-                image.copy_(saved)
-                sch.reset(0)
-                g = _capture_step(self, lambda: self._step(image, noise_table), use_graph)
-                self._graph, self._graph_key = g, key
-                self._static = {"image": image, "noise": noise_table}
-                image.copy_(saved)
-                sch.reset(0)
-            else:
-                self._static["image"].copy_(image)
-                self._static["noise"].copy_(noise_table)
-                image = self._static["image"]
-            for _ in ts:
-                self._graph.replay()
-            sch._step_index = len(ts)
+        image = self._denoise(image, (noise_table,), len(ts), use_graph)
         out = postprocess_images(image.contiguous(), output_type)    # pipeline_ddpm.py:118-121
         if not return_dict:
             return (out,)

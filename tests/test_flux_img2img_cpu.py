@@ -165,7 +165,7 @@ def test_draw_order_and_start_latents(emulated, kind, monkeypatch):
     assert pipe.vae.config.force_upcast
     img = _image()
     starts = []
-    monkeypatch.setattr(type(pipe), "_denoise", lambda self, x, pe, cond, n, ug, begin=0: starts.append((x.clone(), n, begin)) or x)
+    monkeypatch.setattr(type(pipe), "_denoise", lambda self, x, step_args, n, ug, begin=0: starts.append((x.clone(), n, begin)) or x)
     extra = dict(mask_image=_rect_mask()) if kind == "inpaint" else {}
     pipe(image=img, strength=0.6, generator=torch.Generator().manual_seed(21), **extra, **_embeds(), **KW)
     (start, n_steps, begin), = starts

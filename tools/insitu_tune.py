@@ -84,7 +84,7 @@ def main():
             """Re-capture the step with the live table, then time `replays` graph replays (two groups, the faster one)."""
             pipe._graph = None
             lat.copy_(lat0)
-            pipe._denoise(lat, cond, 1, bench.GUIDANCE, True, True)       # warm-up eager step + capture + one replay
+            pipe._denoise(lat, (cond, bench.GUIDANCE, True), 1, True)       # warm-up eager step + capture + one replay
             best = 1e9
             for _ in range(2):
                 lat.copy_(lat0)
