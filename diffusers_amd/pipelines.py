@@ -130,23 +130,27 @@ def _per_prompt(t: Optional[torch.Tensor], n: int) -> Optional[torch.Tensor]:
     return t.repeat_interleave(n, dim=0)
 
 
-def denoising_end_steps(scheduler, denoising_end) -> int:
-    """Steps of the scheduler's current schedule that run when the loop stops at the fraction ``denoising_end`` of the training
-    timesteps (pipeline_stable_diffusion_xl.py:1164-1183: base + refiner workflows): those whose timestep is at or above the cut-off."""
-    n = len(scheduler.timesteps)
-    if denoising_end is None or not isinstance(denoising_end, float) or not 0.0 < denoising_end < 1.0:
-        return n
+def denoising_end_steps(scheduler, denoising_end, timesteps=None) -> int:
+    """Steps of the scheduler's current schedule -- of ``timesteps``, the tail an img2img loop runs, when given -- that run when the
+    loop stops at the fraction ``denoising_end`` of the training timesteps (pipeline_stable_diffusion_xl.py:1164-1183: base +
+    refiner workflows): those whose timestep is at or above the cut-off."""
+    timesteps = scheduler.timesteps if timesteps is None else timesteps
+    if not _denoising_value_valid(denoising_end):
+        return len(timesteps)
     n_train = scheduler.config.num_train_timesteps
     cutoff = int(round(n_train - denoising_end * n_train))
-    return len([t for t in scheduler.timesteps.tolist() if t >= cutoff])
+    return len([t for t in timesteps.tolist() if t >= cutoff])
 
 
-def _refuse_custom_schedule(scheduler, timesteps, sigmas):
-    """retrieve_timesteps (pipeline_stable_diffusion_xl.py:144-167) for a scheduler whose set_timesteps takes a step count only."""
-    if (timesteps is not None or sigmas is not None) and isinstance(scheduler, (DPMSolverMultistepScheduler,
-                                                                                EulerAncestralDiscreteScheduler)):
-        raise ValueError(f"The current scheduler class {type(scheduler)}'s `set_timesteps` does not support custom "
-                         "timestep or sigma schedules. Please check whether you are using the correct scheduler.")
+def _output(images, return_dict: bool):
+    return PipelineOutput(images=images) if return_dict else (images,)
+
+
+def _check_latents_batch(latents, batch: int):
+    """(the reference's prepare_latents takes supplied latents unchecked and fails inside the U-Net; here a stale batch would meet
+    a captured step of another size)"""
+    if latents.shape[0] != batch:
+        raise ValueError(f"`latents` holds {latents.shape[0]} samples, the prompt embeddings (x num_images_per_prompt) {batch}")
 
 
 def _scales_model_input(scheduler) -> bool:
@@ -454,6 +458,63 @@ class _LatentDiffusionBase(_StepCallbacks, _CapturedStepLoop, PipelineLoadingMix
                                       "engine pipelines (decode the returned output_type='latent' tensor yourself)")
         return decode_postprocessed(self.vae, latents, output_type, latents_div=float(vc.scaling_factor))
 
+    # ---- the parts of a call the six SD / SDXL pipelines share (the flavours add _prompt_inputs and _conditioning) ------------
+    def _arm(self, guidance_scale, guidance_rescale, callback_on_step_end, callback_on_step_end_tensor_inputs) -> bool:
+        """What every call sets before anything reads it; returns ``do_cfg``."""
+        self._guidance_rescale = float(guidance_rescale)    # pipeline_stable_diffusion_xl.py:849, :1227-1229
+        self._arm_callback(callback_on_step_end, callback_on_step_end_tensor_inputs)
+        return guidance_scale > 1.0
+
+    def _takes_custom_schedule(self) -> bool:
+        return isinstance(self.scheduler, EulerDiscreteScheduler)
+
+    def _set_schedule(self, num_inference_steps, timesteps, sigmas):
+        """retrieve_timesteps (pipeline_stable_diffusion_xl.py:144-167): a custom timestep / sigma schedule replaces the step count,
+        for a scheduler whose ``set_timesteps`` takes one."""
+        custom = {k: v for k, v in (("timesteps", timesteps), ("sigmas", sigmas)) if v is not None}
+        if not custom:
+            self.scheduler.set_timesteps(num_inference_steps, device=self.device)
+        elif not self._takes_custom_schedule():
+            raise ValueError(f"The current scheduler class {type(self.scheduler)}'s `set_timesteps` does not support custom "
+                             "timestep or sigma schedules. Please check whether you are using the correct scheduler.")
+        else:
+            self.scheduler.set_timesteps(device=self.device, **custom)
+
+    def _noise_latents(self, latents, generator, batch: int, height: int, width: int):
+        """prepare_latents of the txt2img pipelines.  The noise is drawn with a plain ``torch.randn`` on the generator's device,
+        on the CPU without one -- NOT with ``_randn``, which draws on the target device without a generator and takes generator
+        lists: seeded results depend on it.  (Like the reference's prepare_latents, user-supplied latents are taken as they are:
+        no shape check, pipeline_stable_diffusion_xl.py:707-727.)"""
+        if latents is None:
+            shape = (batch, self.unet.config.in_channels, height // self.vae_scale_factor, width // self.vae_scale_factor)
+            gdev = generator.device if generator is not None else torch.device("cpu")
+            latents = torch.randn(shape, generator=generator, device=gdev, dtype=bf16)
+        latents = latents.to(device=self.device, dtype=bf16).contiguous()
+        _check_latents_batch(latents, batch)
+        return ops.mul_scalar(latents, float(self.scheduler.init_noise_sigma))
+
+    def _set_eta(self, eta, latents, generator, num_inference_steps, n_steps, begin):
+        """DDIM's eta for a loop of ``n_steps`` steps from schedule entry ``begin``.  The reference draws the variance noise of a
+        step inside scheduler.step (scheduling_ddim.py:500-507), from ``generator`` in the latents' dtype: the same draws, in the
+        same order, are made up front into the rows the device step counter selects, so the step stays graph-replayable."""
+        if eta < 0.0 or eta > 1.0:
+            raise ValueError("eta (DDIM) must be in [0, 1]")
+        self._eta, self._noise_table = float(eta), None
+        if eta > 0:
+            if not hasattr(self.scheduler, "_get_variance"):
+                raise ValueError("eta > 0 is a DDIMScheduler option")
+            self._fill_noise_table(latents, generator, num_inference_steps, n_steps, begin)
+
+    def _finish(self, latents, generator, cond, guidance_scale, do_cfg, n_steps, begin, use_graph, output_type, return_dict,
+                eta: float = 0.0):
+        """From the start latents to the result: the noise tables (DDIM's eta, then a stochastic sampler's: the call's last
+        draws), ``n_steps`` steps from schedule entry ``begin``, decode."""
+        num_inference_steps = len(self.scheduler.timesteps)
+        self._set_eta(eta, latents, generator, num_inference_steps, n_steps, begin)
+        self._draw_step_noise(latents, generator, num_inference_steps, n_steps, begin)
+        latents = self._denoise(latents, (cond, guidance_scale, do_cfg), n_steps, use_graph, begin=begin)
+        return _output(self._decode(latents, output_type), return_dict)
+
 
 class StableDiffusionXLPipeline(_LatentDiffusionBase):
     def __init__(self, vae, unet, scheduler, text_encoder=None, text_encoder_2=None, tokenizer=None, tokenizer_2=None,
@@ -490,6 +551,52 @@ class StableDiffusionXLPipeline(_LatentDiffusionBase):
                              "`unet.config.time_embedding_type` and `text_encoder_2.config.projection_dim`.")
         return torch.tensor([add_time_ids], dtype=torch.float32)
 
+    def _prompt_inputs(self, prompt, prompt_2, negative_prompt, negative_prompt_2, num_images_per_prompt, prompt_embeds,
+                       negative_prompt_embeds, pooled_prompt_embeds, negative_pooled_prompt_embeds, clip_skip, do_cfg):
+        """``(prompt_embeds, negative_prompt_embeds, pooled_prompt_embeds, negative_pooled_prompt_embeds)`` of a call: encoded from
+        ``prompt``, or as they were passed, ``num_images_per_prompt`` times each."""
+        if prompt is not None:
+            if prompt_embeds is not None:
+                raise ValueError("Cannot forward both `prompt` and `prompt_embeds`. Please make sure to only forward one "
+                                 "of the two.")
+            embeds = self.encode_prompt(prompt, prompt_2, self.device, num_images_per_prompt, do_cfg, negative_prompt,
+                                        negative_prompt_2, clip_skip)
+        else:
+            embeds = tuple(_per_prompt(t, num_images_per_prompt) for t in (prompt_embeds, negative_prompt_embeds,
+                                                                           pooled_prompt_embeds, negative_pooled_prompt_embeds))
+        pe, npe, te, nte = embeds
+        if pe is None or te is None:
+            raise ValueError("Provide either `prompt` (with the text encoders given to the pipeline) or `prompt_embeds` "
+                             "and `pooled_prompt_embeds`.")
+        if do_cfg and (npe is None or nte is None):
+            raise ValueError("classifier-free guidance needs `negative_prompt_embeds` and "
+                             "`negative_pooled_prompt_embeds`")
+        return pe, npe, te, nte
+
+    def _conditioning(self, prompt_embeds, negative_prompt_embeds, pooled_prompt_embeds, negative_pooled_prompt_embeds, ids, neg_ids,
+                      do_cfg):
+        """The step's conditioning: embeddings and added time ids (one row each: txt2img passes the same ``ids`` twice) on the
+        device, per sample, the negative half in front with CFG."""
+        dev = self.device
+        pe = prompt_embeds.to(device=dev, dtype=bf16)
+        te = pooled_prompt_embeds.to(device=dev, dtype=bf16)
+        batch = pe.shape[0]
+        ids = ids.to(dev).repeat(batch, 1)
+        if do_cfg:
+            pe = torch.cat([negative_prompt_embeds.to(device=dev, dtype=bf16), pe], dim=0)
+            te = torch.cat([negative_pooled_prompt_embeds.to(device=dev, dtype=bf16), te], dim=0)
+            ids = torch.cat([neg_ids.to(dev).repeat(batch, 1), ids], dim=0)
+        return self.unet.precompute_conditioning(pe.contiguous(), {"text_embeds": te, "time_ids": ids})
+
+    def _takes_custom_schedule(self) -> bool:
+        """(whatever else the scheduler is, its own ``set_timesteps`` answers)"""
+        return not isinstance(self.scheduler, (DPMSolverMultistepScheduler, EulerAncestralDiscreteScheduler))
+
+    def _set_schedule(self, num_inference_steps, timesteps, sigmas):
+        if timesteps is not None and sigmas is not None:    # retrieve_timesteps, :142-143
+            raise ValueError("Only one of `timesteps` or `sigmas` can be passed. Please choose one to set custom values")
+        super()._set_schedule(num_inference_steps, timesteps, sigmas)
+
     @torch.no_grad()
     def __call__(self, prompt=None, height: Optional[int] = None, width: Optional[int] = None,
                  num_inference_steps: int = 50, guidance_scale: float = 5.0, latents: Optional[torch.Tensor] = None,
@@ -500,72 +607,20 @@ class StableDiffusionXLPipeline(_LatentDiffusionBase):
                  prompt_2=None, negative_prompt=None, negative_prompt_2=None, num_images_per_prompt: int = 1,
                  clip_skip=None, guidance_rescale: float = 0.0, callback_on_step_end=None,
                  callback_on_step_end_tensor_inputs=None, timesteps=None, sigmas=None, denoising_end: Optional[float] = None):
-        do_cfg = guidance_scale > 1.0
-        self._guidance_rescale = float(guidance_rescale)    # pipeline_stable_diffusion_xl.py:849, :1227-1229
-        if timesteps is not None and sigmas is not None:    # retrieve_timesteps, :142-143
-            raise ValueError("Only one of `timesteps` or `sigmas` can be passed. Please choose one to set custom values")
-        self._arm_callback(callback_on_step_end, callback_on_step_end_tensor_inputs)
-        if prompt is not None:
-            if prompt_embeds is not None:
-                raise ValueError("Cannot forward both `prompt` and `prompt_embeds`. Please make sure to only forward one "
-                                 "of the two.")
-            prompt_embeds, negative_prompt_embeds, pooled_prompt_embeds, negative_pooled_prompt_embeds = \
-                self.encode_prompt(prompt, prompt_2, self.device, num_images_per_prompt, do_cfg, negative_prompt,
-                                   negative_prompt_2, clip_skip)
-        else:
-            prompt_embeds, negative_prompt_embeds, pooled_prompt_embeds, negative_pooled_prompt_embeds = (
-                _per_prompt(t, num_images_per_prompt) for t in (prompt_embeds, negative_prompt_embeds, pooled_prompt_embeds,
-                                                                negative_pooled_prompt_embeds))
-        if prompt_embeds is None or pooled_prompt_embeds is None:
-            raise ValueError("Provide either `prompt` (with the text encoders given to the pipeline) or `prompt_embeds` "
-                             "and `pooled_prompt_embeds`.")
-        if do_cfg and (negative_prompt_embeds is None or negative_pooled_prompt_embeds is None):
-            raise ValueError("classifier-free guidance needs `negative_prompt_embeds` and "
-                             "`negative_pooled_prompt_embeds`")
-        dev = self.device
+        do_cfg = self._arm(guidance_scale, guidance_rescale, callback_on_step_end, callback_on_step_end_tensor_inputs)
+        embeds = self._prompt_inputs(prompt, prompt_2, negative_prompt, negative_prompt_2, num_images_per_prompt, prompt_embeds,
+                                     negative_prompt_embeds, pooled_prompt_embeds, negative_pooled_prompt_embeds, clip_skip, do_cfg)
         height = height or self.default_sample_size * self.vae_scale_factor
         width = width or self.default_sample_size * self.vae_scale_factor
-        original_size = original_size or (height, width)
-        target_size = target_size or (height, width)
-        B = prompt_embeds.shape[0]
-        # retrieve_timesteps (:144-167): a custom timestep / sigma schedule replaces the step count; denoising_end (:1164-1183) then
-        # keeps the leading steps down to its cut-off (the loop below simply runs fewer replays of the same captured step)
-        _refuse_custom_schedule(self.scheduler, timesteps, sigmas)
-        if timesteps is not None:
-            self.scheduler.set_timesteps(timesteps=timesteps, device=dev)
-        elif sigmas is not None:
-            self.scheduler.set_timesteps(sigmas=sigmas, device=dev)
-        else:
-            self.scheduler.set_timesteps(num_inference_steps, device=dev)
-        num_inference_steps = denoising_end_steps(self.scheduler, denoising_end)
-        shape = (B, self.unet.config.in_channels, height // self.vae_scale_factor, width // self.vae_scale_factor)
-        if latents is None:
-            gdev = generator.device if generator is not None else torch.device("cpu")
-            latents = torch.randn(shape, generator=generator, device=gdev, dtype=bf16)
-        # (like the reference's prepare_latents, user-supplied latents are taken as they are: no shape check,
-        #  pipeline_stable_diffusion_xl.py:707-727)
-        latents = latents.to(device=dev, dtype=bf16).contiguous()
-        if latents.shape[0] != B:
-            # (the reference's prepare_latents takes supplied latents unchecked and fails inside the U-Net; here a stale batch would
-            #  meet a captured step of another size)
-            raise ValueError(f"`latents` holds {latents.shape[0]} samples, the prompt embeddings (x num_images_per_prompt) {B}")
-        latents = ops.mul_scalar(latents, float(self.scheduler.init_noise_sigma))
-
-        pe = prompt_embeds.to(device=dev, dtype=bf16)
-        te = pooled_prompt_embeds.to(device=dev, dtype=bf16)
-        ids = self._get_add_time_ids(original_size, crops_coords_top_left, target_size, te.shape[-1]).to(dev)
-        ids = ids.repeat(B, 1)
-        if do_cfg:
-            pe = torch.cat([negative_prompt_embeds.to(device=dev, dtype=bf16), pe], dim=0)
-            te = torch.cat([negative_pooled_prompt_embeds.to(device=dev, dtype=bf16), te], dim=0)
-            ids = torch.cat([ids, ids], dim=0)
-        cond = self.unet.precompute_conditioning(pe.contiguous(), {"text_embeds": te, "time_ids": ids})
-        self._draw_step_noise(latents, generator, len(self.scheduler.timesteps), num_inference_steps)
-        latents = self._denoise(latents, (cond, guidance_scale, do_cfg), num_inference_steps, use_graph)
-        images = self._decode(latents, output_type)
-        if not return_dict:
-            return (images,)
-        return PipelineOutput(images=images)
+        # denoising_end (:1164-1183) keeps the leading steps down to its cut-off: the loop simply runs fewer replays of the same
+        # captured step
+        self._set_schedule(num_inference_steps, timesteps, sigmas)
+        latents = self._noise_latents(latents, generator, embeds[0].shape[0], height, width)
+        ids = self._get_add_time_ids(original_size or (height, width), crops_coords_top_left, target_size or (height, width),
+                                     embeds[2].shape[-1])
+        cond = self._conditioning(*embeds, ids, ids, do_cfg)
+        return self._finish(latents, generator, cond, guidance_scale, do_cfg, denoising_end_steps(self.scheduler, denoising_end), 0,
+                            use_graph, output_type, return_dict)
 
 
 class StableDiffusionPipeline(_LatentDiffusionBase):
@@ -585,15 +640,27 @@ class StableDiffusionPipeline(_LatentDiffusionBase):
         return encode_prompt_sd(self.tokenizer, self.text_encoder, prompt, device or self.device, num_images_per_prompt,
                                 do_classifier_free_guidance, negative_prompt, clip_skip)
 
-    def _set_eta(self, eta, latents, generator, num_inference_steps, n_steps, begin):
-        """DDIM's eta for a loop of ``n_steps`` steps from schedule entry ``begin``.  The reference draws the variance noise of a
-        step inside scheduler.step (scheduling_ddim.py:500-507), from ``generator`` in the latents' dtype: the same draws, in the
-        same order, are made up front into the rows the device step counter selects, so the step stays graph-replayable."""
-        self._eta, self._noise_table = float(eta), None
-        if eta > 0:
-            if not hasattr(self.scheduler, "_get_variance"):
-                raise ValueError("eta > 0 is a DDIMScheduler option")
-            self._fill_noise_table(latents, generator, num_inference_steps, n_steps, begin)
+    def _prompt_inputs(self, prompt, negative_prompt, num_images_per_prompt, prompt_embeds, negative_prompt_embeds, clip_skip, do_cfg):
+        """``(prompt_embeds, negative_prompt_embeds)`` of a call: encoded from ``prompt``, or as they were passed,
+        ``num_images_per_prompt`` times each."""
+        if prompt is not None:
+            if prompt_embeds is not None:
+                raise ValueError("Cannot forward both `prompt` and `prompt_embeds`. Please make sure to only forward one "
+                                 "of the two.")
+            pe, npe = self.encode_prompt(prompt, self.device, num_images_per_prompt, do_cfg, negative_prompt, clip_skip)
+        else:
+            pe, npe = (_per_prompt(t, num_images_per_prompt) for t in (prompt_embeds, negative_prompt_embeds))
+        if pe is None:
+            raise ValueError("Provide either `prompt` (with the text encoder given to the pipeline) or `prompt_embeds`.")
+        if do_cfg and npe is None:
+            raise ValueError("classifier-free guidance needs `negative_prompt_embeds`")
+        return pe, npe
+
+    def _conditioning(self, prompt_embeds, negative_prompt_embeds, do_cfg):
+        pe = prompt_embeds.to(device=self.device, dtype=bf16)
+        if do_cfg:
+            pe = torch.cat([negative_prompt_embeds.to(device=self.device, dtype=bf16), pe], dim=0)
+        return self.unet.precompute_conditioning(pe.contiguous(), None)
 
     @torch.no_grad()
     def __call__(self, prompt=None, height: Optional[int] = None, width: Optional[int] = None,
@@ -602,52 +669,20 @@ class StableDiffusionPipeline(_LatentDiffusionBase):
                  output_type: str = "pt", return_dict: bool = True, generator=None, use_graph: bool = True,
                  negative_prompt=None, num_images_per_prompt: int = 1, clip_skip=None, guidance_rescale: float = 0.0,
                  callback_on_step_end=None, callback_on_step_end_tensor_inputs=None):
-        self._guidance_rescale = float(guidance_rescale)    # pipeline_stable_diffusion.py:1057-1059
-        self._arm_callback(callback_on_step_end, callback_on_step_end_tensor_inputs)
-        if eta < 0.0 or eta > 1.0:
-            raise ValueError("eta (DDIM) must be in [0, 1]")
-        do_cfg = guidance_scale > 1.0
-        if prompt is not None:
-            if prompt_embeds is not None:
-                raise ValueError("Cannot forward both `prompt` and `prompt_embeds`. Please make sure to only forward one "
-                                 "of the two.")
-            prompt_embeds, negative_prompt_embeds = self.encode_prompt(prompt, self.device, num_images_per_prompt, do_cfg,
-                                                                        negative_prompt, clip_skip)
-        else:
-            prompt_embeds, negative_prompt_embeds = (_per_prompt(t, num_images_per_prompt) for t in (prompt_embeds, negative_prompt_embeds))
-        if prompt_embeds is None:
-            raise ValueError("Provide either `prompt` (with the text encoder given to the pipeline) or `prompt_embeds`.")
-        if do_cfg and negative_prompt_embeds is None:
-            raise ValueError("classifier-free guidance needs `negative_prompt_embeds`")
-        dev = self.device
+        do_cfg = self._arm(guidance_scale, guidance_rescale, callback_on_step_end, callback_on_step_end_tensor_inputs)
+        embeds = self._prompt_inputs(prompt, negative_prompt, num_images_per_prompt, prompt_embeds, negative_prompt_embeds, clip_skip,
+                                     do_cfg)
         height = height or self.unet.config.sample_size * self.vae_scale_factor
         width = width or self.unet.config.sample_size * self.vae_scale_factor
-        B = prompt_embeds.shape[0]
-        self.scheduler.set_timesteps(num_inference_steps, device=dev)
-        shape = (B, self.unet.config.in_channels, height // self.vae_scale_factor, width // self.vae_scale_factor)
-        if latents is None:
-            gdev = generator.device if generator is not None else torch.device("cpu")
-            latents = torch.randn(shape, generator=generator, device=gdev, dtype=bf16)
-        latents = latents.to(device=dev, dtype=bf16).contiguous()
-        if latents.shape[0] != B:
-            # (the reference's prepare_latents takes supplied latents unchecked and fails inside the U-Net; here a stale batch would
-            #  meet a captured step of another size)
-            raise ValueError(f"`latents` holds {latents.shape[0]} samples, the prompt embeddings (x num_images_per_prompt) {B}")
-        latents = ops.mul_scalar(latents, float(self.scheduler.init_noise_sigma))
-        pe = prompt_embeds.to(device=dev, dtype=bf16)
-        if do_cfg:
-            pe = torch.cat([negative_prompt_embeds.to(device=dev, dtype=bf16), pe], dim=0)
-        cond = self.unet.precompute_conditioning(pe.contiguous(), None)
+        self._set_schedule(num_inference_steps, None, None)
+        latents = self._noise_latents(latents, generator, embeds[0].shape[0], height, width)
+        cond = self._conditioning(*embeds, do_cfg)
         if eta > 0 and not hasattr(self.scheduler, "_get_variance"):
+            # (this pipeline's own wording of `_set_eta`'s refusal)
             raise ValueError("eta > 0 is a DDIMScheduler option (pipeline_stable_diffusion.py:608-625 passes it only "
                              "to schedulers whose step() accepts it)")
-        self._set_eta(eta, latents, generator, num_inference_steps, num_inference_steps, 0)
-        self._draw_step_noise(latents, generator, num_inference_steps, num_inference_steps)
-        latents = self._denoise(latents, (cond, guidance_scale, do_cfg), num_inference_steps, use_graph)
-        images = self._decode(latents, output_type)
-        if not return_dict:
-            return (images,)
-        return PipelineOutput(images=images)
+        return self._finish(latents, generator, cond, guidance_scale, do_cfg, len(self.scheduler.timesteps), 0, use_graph,
+                            output_type, return_dict, eta)
 
 
 # ----------------------------------------------------------------------------------------------------------------------
@@ -746,6 +781,24 @@ class _Img2ImgMixin:
         ts, n, _ = get_timesteps(self.scheduler, num_inference_steps, strength, denoising_start)
         return ts, n
 
+    def _image_schedule(self, num_inference_steps, timesteps, sigmas, strength, denoising_start=None):
+        """The schedule of an image-conditioned call and the tail of it that runs: ``(timesteps, num_steps, begin)`` of
+        ``get_timesteps``, refused when no step is left."""
+        _check_strength(strength)
+        self._set_schedule(num_inference_steps, timesteps, sigmas)
+        ts, n_steps, begin = get_timesteps(self.scheduler, len(self.scheduler.timesteps), strength, denoising_start)
+        _no_steps(strength, n_steps)
+        return ts, n_steps, begin
+
+    def _start_latents(self, image, mask_image, masked_image_latents, height, width, latents, timestep, batch: int, generator,
+                       strength: float, add_noise: bool, noise_dtype, padding_mask_crop=None):
+        """The hook of ``_image_call``: where the loop starts (the arguments of ``_InpaintMixin._inpaint_prepare``, which
+        takes its place in the inpainting pipelines).  Img2img: ``image`` encoded and noised to ``timestep``, or -- SDXL's
+        shortcut -- ``latents`` as they are."""
+        if latents is not None:
+            return latents.to(device=self.device, dtype=bf16).clone()
+        return self._img2img_latents(image, timestep, batch, generator, add_noise, noise_dtype)
+
     def _img2img_latents(self, image, timestep, batch: int, generator, add_noise: bool, noise_dtype):
         vc = self.vae.config
         if vc.get("latents_mean") is not None or vc.get("latents_std") is not None:
@@ -834,6 +887,47 @@ class StableDiffusionXLImg2ImgPipeline(_Img2ImgMixin, StableDiffusionXLPipeline)
         # (built in the prompt embeddings' dtype, as the reference does; the U-Net reads them as fp32)
         return (torch.tensor([add_time_ids], dtype=dtype).float(), torch.tensor([add_neg_time_ids], dtype=dtype).float())
 
+    _task = "img2img"
+
+    def _image_call(self, prompt, prompt_2, image, mask_image, masked_image_latents, height, width, padding_mask_crop, strength,
+                    num_inference_steps, timesteps, sigmas, denoising_start, denoising_end, guidance_scale, negative_prompt,
+                    negative_prompt_2, num_images_per_prompt, eta, generator, latents, prompt_embeds, negative_prompt_embeds,
+                    pooled_prompt_embeds, negative_pooled_prompt_embeds, output_type, return_dict, guidance_rescale, original_size,
+                    crops_coords_top_left, target_size, negative_original_size, negative_crops_coords_top_left, negative_target_size,
+                    aesthetic_score, negative_aesthetic_score, clip_skip, callback_on_step_end, callback_on_step_end_tensor_inputs,
+                    use_graph):
+        """The call of the SDXL img2img and inpainting pipelines; ``_start_latents`` is what differs."""
+        if image is None and latents is None:
+            raise ValueError("`image` input cannot be undefined.")
+        if eta != 0.0:
+            raise NotImplementedError(f"eta applies to DDIM; the SDXL {self._task} engine pipeline runs the Euler scheduler")
+        # (the refiner side of a base + refiner hand-off starts from the base's latents: no noise is added)
+        denoising_start = denoising_start if _denoising_value_valid(denoising_start) else None
+        if denoising_start is not None and _denoising_value_valid(denoising_end) and denoising_start >= denoising_end:
+            raise ValueError(f"`denoising_start`: {denoising_start} cannot be larger than or equal to `denoising_end`: "
+                             f"{denoising_end} when using type float.")
+        do_cfg = self._arm(guidance_scale, guidance_rescale, callback_on_step_end, callback_on_step_end_tensor_inputs)
+        embeds = self._prompt_inputs(prompt, prompt_2, negative_prompt, negative_prompt_2, num_images_per_prompt, prompt_embeds,
+                                     negative_prompt_embeds, pooled_prompt_embeds, negative_pooled_prompt_embeds, clip_skip, do_cfg)
+        B = embeds[0].shape[0]
+        ts, n_steps, begin = self._image_schedule(num_inference_steps, timesteps, sigmas, strength, denoising_start)
+        # the reference's upcast path (force_upcast): the posterior noise is drawn in fp32
+        latents = self._start_latents(image, mask_image, masked_image_latents, height, width, latents, ts[:1].repeat(B), B, generator,
+                                      strength, denoising_start is None, torch.float32 if self.vae.config.force_upcast else bf16,
+                                      padding_mask_crop)
+        _check_latents_batch(latents, B)
+        if _denoising_value_valid(denoising_end):
+            n_steps = denoising_end_steps(self.scheduler, denoising_end, ts)
+        height, width = latents.shape[-2] * self.vae_scale_factor, latents.shape[-1] * self.vae_scale_factor
+        original_size = original_size or (height, width)
+        target_size = target_size or (height, width)
+        ids, neg_ids = self._get_add_time_ids(original_size, tuple(crops_coords_top_left), target_size, aesthetic_score,
+                                              negative_aesthetic_score, negative_original_size or original_size,
+                                              tuple(negative_crops_coords_top_left), negative_target_size or target_size,
+                                              text_encoder_projection_dim=int(embeds[2].shape[-1]))
+        cond = self._conditioning(*embeds, ids, neg_ids, do_cfg)
+        return self._finish(latents, generator, cond, guidance_scale, do_cfg, n_steps, begin, use_graph, output_type, return_dict)
+
     @torch.no_grad()
     def __call__(self, prompt=None, prompt_2=None, image=None, strength: float = 0.3, num_inference_steps: int = 50,
                  timesteps=None, sigmas=None, denoising_start: Optional[float] = None, denoising_end: Optional[float] = None,
@@ -846,90 +940,35 @@ class StableDiffusionXLImg2ImgPipeline(_Img2ImgMixin, StableDiffusionXLPipeline)
                  negative_crops_coords_top_left: Tuple[int, int] = (0, 0), negative_target_size: Optional[Tuple[int, int]] = None,
                  aesthetic_score: float = 6.0, negative_aesthetic_score: float = 2.5, clip_skip=None,
                  callback_on_step_end=None, callback_on_step_end_tensor_inputs=None, use_graph: bool = True):
-        _check_strength(strength)
-        if image is None and latents is None:
-            raise ValueError("`image` input cannot be undefined.")
-        if eta != 0.0:
-            raise NotImplementedError("eta applies to DDIM; the SDXL img2img engine pipeline runs the Euler scheduler")
-        if (denoising_end is not None and denoising_start is not None and _denoising_value_valid(denoising_end)
-                and _denoising_value_valid(denoising_start) and denoising_start >= denoising_end):
-            raise ValueError(f"`denoising_start`: {denoising_start} cannot be larger than or equal to `denoising_end`: "
-                             f"{denoising_end} when using type float.")
-        if timesteps is not None and sigmas is not None:
-            raise ValueError("Only one of `timesteps` or `sigmas` can be passed. Please choose one to set custom values")
-        do_cfg = guidance_scale > 1.0
-        self._guidance_rescale = float(guidance_rescale)
-        self._arm_callback(callback_on_step_end, callback_on_step_end_tensor_inputs)
-        if prompt is not None:
-            if prompt_embeds is not None:
-                raise ValueError("Cannot forward both `prompt` and `prompt_embeds`. Please make sure to only forward one "
-                                 "of the two.")
-            prompt_embeds, negative_prompt_embeds, pooled_prompt_embeds, negative_pooled_prompt_embeds = \
-                self.encode_prompt(prompt, prompt_2, self.device, num_images_per_prompt, do_cfg, negative_prompt,
-                                   negative_prompt_2, clip_skip)
-        else:
-            prompt_embeds, negative_prompt_embeds, pooled_prompt_embeds, negative_pooled_prompt_embeds = (
-                _per_prompt(t, num_images_per_prompt) for t in (prompt_embeds, negative_prompt_embeds, pooled_prompt_embeds,
-                                                                negative_pooled_prompt_embeds))
-        if prompt_embeds is None or pooled_prompt_embeds is None:
-            raise ValueError("Provide either `prompt` (with the text encoders given to the pipeline) or `prompt_embeds` "
-                             "and `pooled_prompt_embeds`.")
-        if do_cfg and (negative_prompt_embeds is None or negative_pooled_prompt_embeds is None):
-            raise ValueError("classifier-free guidance needs `negative_prompt_embeds` and "
-                             "`negative_pooled_prompt_embeds`")
-        dev = self.device
-        B = prompt_embeds.shape[0]
-        _refuse_custom_schedule(self.scheduler, timesteps, sigmas)
-        if timesteps is not None:
-            self.scheduler.set_timesteps(timesteps=timesteps, device=dev)
-        elif sigmas is not None:
-            self.scheduler.set_timesteps(sigmas=sigmas, device=dev)
-        else:
-            self.scheduler.set_timesteps(num_inference_steps, device=dev)
-        num_inference_steps = len(self.scheduler.timesteps)
-        ts, n_steps, begin = get_timesteps(self.scheduler, num_inference_steps, strength,
-                                           denoising_start if _denoising_value_valid(denoising_start) else None)
-        _no_steps(strength, n_steps)
-        latent_timestep = ts[:1].repeat(B)
-        add_noise = not _denoising_value_valid(denoising_start)
-        if latents is None:
-            # the reference's upcast path (force_upcast): the posterior noise is drawn in fp32
-            latents = self._img2img_latents(image, latent_timestep, B, generator, add_noise,
-                                            torch.float32 if self.vae.config.force_upcast else bf16)
-        else:
-            latents = latents.to(device=dev, dtype=bf16).clone()
-        if latents.shape[0] != B:
-            raise ValueError(f"`latents` holds {latents.shape[0]} samples, the prompt embeddings (x num_images_per_prompt) {B}")
-        if _denoising_value_valid(denoising_end):
-            cutoff = int(round(self.scheduler.config.num_train_timesteps - denoising_end * self.scheduler.config.num_train_timesteps))
-            n_steps = len([t for t in ts.tolist() if t >= cutoff])
-        height, width = latents.shape[-2] * self.vae_scale_factor, latents.shape[-1] * self.vae_scale_factor
-        original_size = original_size or (height, width)
-        target_size = target_size or (height, width)
-        negative_original_size = negative_original_size or original_size
-        negative_target_size = negative_target_size or target_size
-        pe = prompt_embeds.to(device=dev, dtype=bf16)
-        te = pooled_prompt_embeds.to(device=dev, dtype=bf16)
-        ids, neg_ids = self._get_add_time_ids(original_size, tuple(crops_coords_top_left), target_size, aesthetic_score,
-                                              negative_aesthetic_score, negative_original_size,
-                                              tuple(negative_crops_coords_top_left), negative_target_size,
-                                              text_encoder_projection_dim=int(te.shape[-1]))
-        ids = ids.to(dev).repeat(B, 1)
-        if do_cfg:
-            pe = torch.cat([negative_prompt_embeds.to(device=dev, dtype=bf16), pe], dim=0)
-            te = torch.cat([negative_pooled_prompt_embeds.to(device=dev, dtype=bf16), te], dim=0)
-            ids = torch.cat([neg_ids.to(dev).repeat(B, 1), ids], dim=0)
-        cond = self.unet.precompute_conditioning(pe.contiguous(), {"text_embeds": te, "time_ids": ids})
-        self._draw_step_noise(latents, generator, num_inference_steps, n_steps, begin)
-        latents = self._denoise(latents, (cond, guidance_scale, do_cfg), n_steps, use_graph, begin=begin)
-        images = self._decode(latents, output_type)
-        if not return_dict:
-            return (images,)
-        return PipelineOutput(images=images)
+        return self._image_call(prompt, prompt_2, image, None, None, None, None, None, strength, num_inference_steps, timesteps,
+                                sigmas, denoising_start, denoising_end, guidance_scale, negative_prompt, negative_prompt_2,
+                                num_images_per_prompt, eta, generator, latents, prompt_embeds, negative_prompt_embeds,
+                                pooled_prompt_embeds, negative_pooled_prompt_embeds, output_type, return_dict, guidance_rescale,
+                                original_size, crops_coords_top_left, target_size, negative_original_size,
+                                negative_crops_coords_top_left, negative_target_size, aesthetic_score, negative_aesthetic_score,
+                                clip_skip, callback_on_step_end, callback_on_step_end_tensor_inputs, use_graph)
 
 
 class StableDiffusionImg2ImgPipeline(_Img2ImgMixin, StableDiffusionPipeline):
     """pipeline_stable_diffusion_img2img.py (__call__ :860-1132): SD1.5 img2img on the engine (DDIM by default, eta included)."""
+
+    def _image_call(self, prompt, image, mask_image, masked_image_latents, height, width, padding_mask_crop, strength,
+                    num_inference_steps, timesteps, sigmas, guidance_scale, negative_prompt, num_images_per_prompt, eta, generator,
+                    latents, prompt_embeds, negative_prompt_embeds, output_type, return_dict, clip_skip, guidance_rescale,
+                    callback_on_step_end, callback_on_step_end_tensor_inputs, use_graph):
+        """The call of the SD img2img and inpainting pipelines; ``_start_latents`` is what differs."""
+        if image is None:
+            raise ValueError("`image` input cannot be undefined.")
+        do_cfg = self._arm(guidance_scale, guidance_rescale, callback_on_step_end, callback_on_step_end_tensor_inputs)
+        embeds = self._prompt_inputs(prompt, negative_prompt, num_images_per_prompt, prompt_embeds, negative_prompt_embeds, clip_skip,
+                                     do_cfg)
+        B = embeds[0].shape[0]
+        ts, n_steps, begin = self._image_schedule(num_inference_steps, timesteps, sigmas, strength)
+        # (no upcast in this pipeline: the posterior noise is drawn in the VAE's dtype)
+        latents = self._start_latents(image, mask_image, masked_image_latents, height, width, latents, ts[:1].repeat(B), B, generator,
+                                      strength, True, bf16, padding_mask_crop)
+        cond = self._conditioning(*embeds, do_cfg)
+        return self._finish(latents, generator, cond, guidance_scale, do_cfg, n_steps, begin, use_graph, output_type, return_dict, eta)
 
     @torch.no_grad()
     def __call__(self, prompt=None, image=None, strength: float = 0.8, num_inference_steps: int = 50, timesteps=None,
@@ -937,52 +976,10 @@ class StableDiffusionImg2ImgPipeline(_Img2ImgMixin, StableDiffusionPipeline):
                  eta: float = 0.0, generator=None, prompt_embeds=None, negative_prompt_embeds=None, output_type: str = "pt",
                  return_dict: bool = True, clip_skip=None, guidance_rescale: float = 0.0, callback_on_step_end=None,
                  callback_on_step_end_tensor_inputs=None, use_graph: bool = True):
-        _check_strength(strength)
-        if image is None:
-            raise ValueError("`image` input cannot be undefined.")
-        if eta < 0.0 or eta > 1.0:
-            raise ValueError("eta (DDIM) must be in [0, 1]")
-        self._guidance_rescale = float(guidance_rescale)
-        self._arm_callback(callback_on_step_end, callback_on_step_end_tensor_inputs)
-        do_cfg = guidance_scale > 1.0
-        if prompt is not None:
-            if prompt_embeds is not None:
-                raise ValueError("Cannot forward both `prompt` and `prompt_embeds`. Please make sure to only forward one "
-                                 "of the two.")
-            prompt_embeds, negative_prompt_embeds = self.encode_prompt(prompt, self.device, num_images_per_prompt, do_cfg,
-                                                                        negative_prompt, clip_skip)
-        else:
-            prompt_embeds, negative_prompt_embeds = (_per_prompt(t, num_images_per_prompt) for t in (prompt_embeds, negative_prompt_embeds))
-        if prompt_embeds is None:
-            raise ValueError("Provide either `prompt` (with the text encoder given to the pipeline) or `prompt_embeds`.")
-        if do_cfg and negative_prompt_embeds is None:
-            raise ValueError("classifier-free guidance needs `negative_prompt_embeds`")
-        dev = self.device
-        B = prompt_embeds.shape[0]
-        if timesteps is not None or sigmas is not None:
-            if not isinstance(self.scheduler, EulerDiscreteScheduler):
-                raise ValueError(f"The current scheduler class {type(self.scheduler)}'s `set_timesteps` does not support custom "
-                                 "timestep or sigma schedules. Please check whether you are using the correct scheduler.")
-            self.scheduler.set_timesteps(timesteps=timesteps, sigmas=sigmas, device=dev)
-        else:
-            self.scheduler.set_timesteps(num_inference_steps, device=dev)
-        num_inference_steps = len(self.scheduler.timesteps)
-        ts, n_steps, begin = get_timesteps(self.scheduler, num_inference_steps, strength)
-        _no_steps(strength, n_steps)
-        latent_timestep = ts[:1].repeat(B)
-        # (no upcast in this pipeline: the posterior noise is drawn in the VAE's dtype)
-        latents = self._img2img_latents(image, latent_timestep, B, generator, True, bf16)
-        pe = prompt_embeds.to(device=dev, dtype=bf16)
-        if do_cfg:
-            pe = torch.cat([negative_prompt_embeds.to(device=dev, dtype=bf16), pe], dim=0)
-        cond = self.unet.precompute_conditioning(pe.contiguous(), None)
-        self._set_eta(eta, latents, generator, num_inference_steps, n_steps, begin)
-        self._draw_step_noise(latents, generator, num_inference_steps, n_steps, begin)
-        latents = self._denoise(latents, (cond, guidance_scale, do_cfg), n_steps, use_graph, begin=begin)
-        images = self._decode(latents, output_type)
-        if not return_dict:
-            return (images,)
-        return PipelineOutput(images=images)
+        return self._image_call(prompt, image, None, None, None, None, None, strength, num_inference_steps, timesteps, sigmas,
+                                guidance_scale, negative_prompt, num_images_per_prompt, eta, generator, None, prompt_embeds,
+                                negative_prompt_embeds, output_type, return_dict, clip_skip, guidance_rescale, callback_on_step_end,
+                                callback_on_step_end_tensor_inputs, use_graph)
 
 
 # ----------------------------------------------------------------------------------------------------------------------
@@ -1163,6 +1160,15 @@ class _InpaintMixin:
         st["table"] = self.scheduler.add_noise_table(bf16) if nu == 4 else None
         return start.contiguous()
 
+    def _check_inpaint_inputs(self, image, ip_adapter_image, ip_adapter_image_embeds):
+        if image is None:
+            raise ValueError("`image` input cannot be undefined.")
+        if ip_adapter_image is not None or ip_adapter_image_embeds is not None:
+            raise NotImplementedError("`ip_adapter_image` / `ip_adapter_image_embeds`: IP-Adapter is outside this engine")
+
+    def _start_latents(self, *args, **kw):
+        return self._inpaint_prepare(*args, **kw)
+
     def _predict_noise(self, latents, cond, do_cfg):
         st = self._inpaint
         if st is None or st["masked"] is None:
@@ -1201,60 +1207,18 @@ class StableDiffusionInpaintPipeline(_InpaintMixin, StableDiffusionImg2ImgPipeli
                  negative_prompt_embeds=None, ip_adapter_image=None, ip_adapter_image_embeds=None, output_type: str = "pt",
                  return_dict: bool = True, clip_skip=None, guidance_rescale: float = 0.0, callback_on_step_end=None,
                  callback_on_step_end_tensor_inputs=None, use_graph: bool = True):
-        _check_strength(strength)
-        if image is None:
-            raise ValueError("`image` input cannot be undefined.")
-        if ip_adapter_image is not None or ip_adapter_image_embeds is not None:
-            raise NotImplementedError("`ip_adapter_image` / `ip_adapter_image_embeds`: IP-Adapter is outside this engine")
-        if eta < 0.0 or eta > 1.0:
-            raise ValueError("eta (DDIM) must be in [0, 1]")
-        self._guidance_rescale = float(guidance_rescale)
-        self._arm_callback(callback_on_step_end, callback_on_step_end_tensor_inputs)
-        do_cfg = guidance_scale > 1.0
-        if prompt is not None:
-            if prompt_embeds is not None:
-                raise ValueError("Cannot forward both `prompt` and `prompt_embeds`. Please make sure to only forward one "
-                                 "of the two.")
-            prompt_embeds, negative_prompt_embeds = self.encode_prompt(prompt, self.device, num_images_per_prompt, do_cfg,
-                                                                        negative_prompt, clip_skip)
-        else:
-            prompt_embeds, negative_prompt_embeds = (_per_prompt(t, num_images_per_prompt) for t in (prompt_embeds, negative_prompt_embeds))
-        if prompt_embeds is None:
-            raise ValueError("Provide either `prompt` (with the text encoder given to the pipeline) or `prompt_embeds`.")
-        if do_cfg and negative_prompt_embeds is None:
-            raise ValueError("classifier-free guidance needs `negative_prompt_embeds`")
-        dev = self.device
-        B = prompt_embeds.shape[0]
-        if timesteps is not None or sigmas is not None:
-            if not isinstance(self.scheduler, EulerDiscreteScheduler):
-                raise ValueError(f"The current scheduler class {type(self.scheduler)}'s `set_timesteps` does not support custom "
-                                 "timestep or sigma schedules. Please check whether you are using the correct scheduler.")
-            self.scheduler.set_timesteps(timesteps=timesteps, sigmas=sigmas, device=dev)
-        else:
-            self.scheduler.set_timesteps(num_inference_steps, device=dev)
-        num_inference_steps = len(self.scheduler.timesteps)
-        ts, n_steps, begin = get_timesteps(self.scheduler, num_inference_steps, strength)
-        _no_steps(strength, n_steps)
-        latent_timestep = ts[:1].repeat(B)
-        # (no upcast in this pipeline: the posterior noise is drawn in the VAE's dtype)
-        latents = self._inpaint_prepare(image, mask_image, masked_image_latents, height, width, latents, latent_timestep, B,
-                                        generator, strength, True, bf16, padding_mask_crop)
-        pe = prompt_embeds.to(device=dev, dtype=bf16)
-        if do_cfg:
-            pe = torch.cat([negative_prompt_embeds.to(device=dev, dtype=bf16), pe], dim=0)
-        cond = self.unet.precompute_conditioning(pe.contiguous(), None)
-        self._set_eta(eta, latents, generator, num_inference_steps, n_steps, begin)
-        self._draw_step_noise(latents, generator, num_inference_steps, n_steps, begin)
-        latents = self._denoise(latents, (cond, guidance_scale, do_cfg), n_steps, use_graph, begin=begin)
-        images = self._decode(latents, output_type)
-        if not return_dict:
-            return (images,)
-        return PipelineOutput(images=images)
+        self._check_inpaint_inputs(image, ip_adapter_image, ip_adapter_image_embeds)
+        return self._image_call(prompt, image, mask_image, masked_image_latents, height, width, padding_mask_crop, strength,
+                                num_inference_steps, timesteps, sigmas, guidance_scale, negative_prompt, num_images_per_prompt, eta,
+                                generator, latents, prompt_embeds, negative_prompt_embeds, output_type, return_dict, clip_skip,
+                                guidance_rescale, callback_on_step_end, callback_on_step_end_tensor_inputs, use_graph)
 
 
 class StableDiffusionXLInpaintPipeline(_InpaintMixin, StableDiffusionXLImg2ImgPipeline):
     """pipeline_stable_diffusion_xl_inpaint.py: SDXL inpainting on the engine, 4-channel and 9-channel U-Nets (see _InpaintMixin);
     ``denoising_start`` / ``denoising_end`` as in the img2img pipeline."""
+
+    _task = "inpainting"
 
     @torch.no_grad()
     def __call__(self, prompt=None, prompt_2=None, image=None, mask_image=None, masked_image_latents=None,
@@ -1270,86 +1234,14 @@ class StableDiffusionXLInpaintPipeline(_InpaintMixin, StableDiffusionXLImg2ImgPi
                  negative_target_size: Optional[Tuple[int, int]] = None, aesthetic_score: float = 6.0,
                  negative_aesthetic_score: float = 2.5, clip_skip=None, callback_on_step_end=None,
                  callback_on_step_end_tensor_inputs=None, use_graph: bool = True):
-        _check_strength(strength)
-        if image is None:
-            raise ValueError("`image` input cannot be undefined.")
-        if ip_adapter_image is not None or ip_adapter_image_embeds is not None:
-            raise NotImplementedError("`ip_adapter_image` / `ip_adapter_image_embeds`: IP-Adapter is outside this engine")
-        if eta != 0.0:
-            raise NotImplementedError("eta applies to DDIM; the SDXL inpainting engine pipeline runs the Euler scheduler")
-        if (denoising_end is not None and denoising_start is not None and _denoising_value_valid(denoising_end)
-                and _denoising_value_valid(denoising_start) and denoising_start >= denoising_end):
-            raise ValueError(f"`denoising_start`: {denoising_start} cannot be larger than or equal to `denoising_end`: "
-                             f"{denoising_end} when using type float.")
-        if timesteps is not None and sigmas is not None:
-            raise ValueError("Only one of `timesteps` or `sigmas` can be passed. Please choose one to set custom values")
-        do_cfg = guidance_scale > 1.0
-        self._guidance_rescale = float(guidance_rescale)
-        self._arm_callback(callback_on_step_end, callback_on_step_end_tensor_inputs)
-        if prompt is not None:
-            if prompt_embeds is not None:
-                raise ValueError("Cannot forward both `prompt` and `prompt_embeds`. Please make sure to only forward one "
-                                 "of the two.")
-            prompt_embeds, negative_prompt_embeds, pooled_prompt_embeds, negative_pooled_prompt_embeds = \
-                self.encode_prompt(prompt, prompt_2, self.device, num_images_per_prompt, do_cfg, negative_prompt,
-                                   negative_prompt_2, clip_skip)
-        else:
-            prompt_embeds, negative_prompt_embeds, pooled_prompt_embeds, negative_pooled_prompt_embeds = (
-                _per_prompt(t, num_images_per_prompt) for t in (prompt_embeds, negative_prompt_embeds, pooled_prompt_embeds,
-                                                                negative_pooled_prompt_embeds))
-        if prompt_embeds is None or pooled_prompt_embeds is None:
-            raise ValueError("Provide either `prompt` (with the text encoders given to the pipeline) or `prompt_embeds` "
-                             "and `pooled_prompt_embeds`.")
-        if do_cfg and (negative_prompt_embeds is None or negative_pooled_prompt_embeds is None):
-            raise ValueError("classifier-free guidance needs `negative_prompt_embeds` and "
-                             "`negative_pooled_prompt_embeds`")
-        dev = self.device
-        B = prompt_embeds.shape[0]
-        _refuse_custom_schedule(self.scheduler, timesteps, sigmas)
-        if timesteps is not None:
-            self.scheduler.set_timesteps(timesteps=timesteps, device=dev)
-        elif sigmas is not None:
-            self.scheduler.set_timesteps(sigmas=sigmas, device=dev)
-        else:
-            self.scheduler.set_timesteps(num_inference_steps, device=dev)
-        num_inference_steps = len(self.scheduler.timesteps)
-        ts, n_steps, begin = get_timesteps(self.scheduler, num_inference_steps, strength,
-                                           denoising_start if _denoising_value_valid(denoising_start) else None)
-        _no_steps(strength, n_steps)
-        latent_timestep = ts[:1].repeat(B)
-        add_noise = not _denoising_value_valid(denoising_start)
-        # the reference's upcast path (force_upcast): the posterior noise is drawn in fp32
-        latents = self._inpaint_prepare(image, mask_image, masked_image_latents, height, width, latents, latent_timestep, B,
-                                        generator, strength, add_noise, torch.float32 if self.vae.config.force_upcast else bf16,
-                                        padding_mask_crop)
-        if latents.shape[0] != B:
-            raise ValueError(f"`latents` holds {latents.shape[0]} samples, the prompt embeddings (x num_images_per_prompt) {B}")
-        if _denoising_value_valid(denoising_end):
-            cutoff = int(round(self.scheduler.config.num_train_timesteps - denoising_end * self.scheduler.config.num_train_timesteps))
-            n_steps = len([t for t in ts.tolist() if t >= cutoff])
-        height, width = latents.shape[-2] * self.vae_scale_factor, latents.shape[-1] * self.vae_scale_factor
-        original_size = original_size or (height, width)
-        target_size = target_size or (height, width)
-        negative_original_size = negative_original_size or original_size
-        negative_target_size = negative_target_size or target_size
-        pe = prompt_embeds.to(device=dev, dtype=bf16)
-        te = pooled_prompt_embeds.to(device=dev, dtype=bf16)
-        ids, neg_ids = self._get_add_time_ids(original_size, tuple(crops_coords_top_left), target_size, aesthetic_score,
-                                              negative_aesthetic_score, negative_original_size,
-                                              tuple(negative_crops_coords_top_left), negative_target_size,
-                                              text_encoder_projection_dim=int(te.shape[-1]))
-        ids = ids.to(dev).repeat(B, 1)
-        if do_cfg:
-            pe = torch.cat([negative_prompt_embeds.to(device=dev, dtype=bf16), pe], dim=0)
-            te = torch.cat([negative_pooled_prompt_embeds.to(device=dev, dtype=bf16), te], dim=0)
-            ids = torch.cat([neg_ids.to(dev).repeat(B, 1), ids], dim=0)
-        cond = self.unet.precompute_conditioning(pe.contiguous(), {"text_embeds": te, "time_ids": ids})
-        self._draw_step_noise(latents, generator, num_inference_steps, n_steps, begin)
-        latents = self._denoise(latents, (cond, guidance_scale, do_cfg), n_steps, use_graph, begin=begin)
-        images = self._decode(latents, output_type)
-        if not return_dict:
-            return (images,)
-        return PipelineOutput(images=images)
+        self._check_inpaint_inputs(image, ip_adapter_image, ip_adapter_image_embeds)
+        return self._image_call(prompt, prompt_2, image, mask_image, masked_image_latents, height, width, padding_mask_crop, strength,
+                                num_inference_steps, timesteps, sigmas, denoising_start, denoising_end, guidance_scale,
+                                negative_prompt, negative_prompt_2, num_images_per_prompt, eta, generator, latents, prompt_embeds,
+                                negative_prompt_embeds, pooled_prompt_embeds, negative_pooled_prompt_embeds, output_type, return_dict,
+                                guidance_rescale, original_size, crops_coords_top_left, target_size, negative_original_size,
+                                negative_crops_coords_top_left, negative_target_size, aesthetic_score, negative_aesthetic_score,
+                                clip_skip, callback_on_step_end, callback_on_step_end_tensor_inputs, use_graph)
 
 
 def calculate_shift(image_seq_len, base_seq_len: int = 256, max_seq_len: int = 4096, base_shift: float = 0.5,
@@ -1470,9 +1362,7 @@ class FluxPipeline(_StepCallbacks, _CapturedStepLoop, PipelineLoadingMixin):
             vc = self.vae.config
             images = decode_postprocessed(self.vae, unp, output_type, latents_div=float(vc.scaling_factor),
                                           latents_add=float(vc.shift_factor or 0.0))
-        if not return_dict:
-            return (images,)
-        return PipelineOutput(images=images)
+        return _output(images, return_dict)
 
     @torch.no_grad()
     def __call__(self, prompt=None, prompt_2=None, negative_prompt=None, negative_prompt_2=None, true_cfg_scale: float = 1.0,
@@ -1828,9 +1718,7 @@ class WanPipeline(_StepCallbacks, _CapturedStepLoop, PipelineLoadingMixin):
             latents = postprocess_images(video, output_type)
             if output_type == "pt":
                 latents = latents.permute(0, 2, 1, 3, 4)
-        if not return_dict:
-            return (latents,)
-        return PipelineOutput(images=latents)
+        return _output(latents, return_dict)
 
 
 class DDPMPipeline(_CapturedStepLoop, PipelineLoadingMixin):
@@ -1880,6 +1768,4 @@ class DDPMPipeline(_CapturedStepLoop, PipelineLoadingMixin):
         noise_table = torch.stack(draws).to(device=dev, dtype=bf16).contiguous()
         image = self._denoise(image, (noise_table,), len(ts), use_graph)
         out = postprocess_images(image.contiguous(), output_type)    # pipeline_ddpm.py:118-121
-        if not return_dict:
-            return (out,)
-        return PipelineOutput(images=out)
+        return _output(out, return_dict)
