@@ -24,7 +24,7 @@ from . import _lib as L
 from . import ops
 from .autoencoder_kl import AutoencoderKL
 from .pipeline_loading import PipelineLoadingMixin
-from .schedulers import (DDIMScheduler, DDPMScheduler, DPMSolverMultistepScheduler, EulerAncestralDiscreteScheduler,
+from .schedulers import (DDPMScheduler, DPMSolverMultistepScheduler, EulerAncestralDiscreteScheduler,
                          EulerDiscreteScheduler, FlowMatchEulerDiscreteScheduler, UniPCMultistepScheduler)
 from .transformer_flux import FluxTransformer2DModel
 from .transformer_wan import WanTransformer3DModel
@@ -151,11 +151,6 @@ def _check_latents_batch(latents, batch: int):
     a captured step of another size)"""
     if latents.shape[0] != batch:
         raise ValueError(f"`latents` holds {latents.shape[0]} samples, the prompt embeddings (x num_images_per_prompt) {batch}")
-
-
-def _scales_model_input(scheduler) -> bool:
-    """Schedulers whose ``scale_model_input`` divides by sqrt(sigma^2 + 1) (slot 3 of their table row); identity for the others."""
-    return isinstance(scheduler, (EulerDiscreteScheduler, EulerAncestralDiscreteScheduler))
 
 
 def _capture_step(pipe, step, mode):
@@ -377,7 +372,7 @@ class _LatentDiffusionBase(_StepCallbacks, _CapturedStepLoop, PipelineLoadingMix
         """scale_model_input + CFG batch doubling + the U-Net forward of one step."""
         sch = self.scheduler
         rep = 2 if do_cfg else 1
-        if _scales_model_input(sch):
+        if sch.scales_model_input:
             x_in = sch.scale_model_input(latents, sch.timesteps[0], rep=rep)
         else:
             x_in = ops.mul_scalar(latents, 1.0, rep=rep) if rep > 1 else latents  # DDIM, DPM-Solver++: scale_model_input = identity
@@ -429,11 +424,10 @@ class _LatentDiffusionBase(_StepCallbacks, _CapturedStepLoop, PipelineLoadingMix
     def _make_graph_key(self, latents, cond, guidance_scale, do_cfg):
         """Everything a captured step depends on besides the contents of its static buffers."""
         sch = self.scheduler
-        if isinstance(sch, DDIMScheduler):
-            # set_timesteps() invalidated the coefficient table; rebuild it for THIS call's eta before the key reads its
-            # address (reading `device_table` first would rebuild it in place for eta = 0, and a replayed graph would
-            # then run deterministic DDIM whatever eta the caller passed)
-            sch._ensure(self._eta, sch.timesteps[0])
+        # DDIM: set_timesteps() invalidated the coefficient table; have it rebuilt for THIS call's eta before the key reads its
+        # address (reading `device_table` first would rebuild it in place for eta = 0, and a replayed graph would then run
+        # deterministic DDIM whatever eta the caller passed).  A no-op for every other scheduler.
+        sch.ensure_table(self._eta)
         return (tuple(latents.shape), float(guidance_scale), bool(do_cfg), cond["kvs"][0][0].skv if cond["kvs"] else 0,
                 self._noise_table.data_ptr() if self._noise_table is not None else 0, float(self._eta),
                 float(self._guidance_rescale)) + _key_tail(sch, self.unet, latents)
@@ -501,7 +495,7 @@ class _LatentDiffusionBase(_StepCallbacks, _CapturedStepLoop, PipelineLoadingMix
             raise ValueError("eta (DDIM) must be in [0, 1]")
         self._eta, self._noise_table = float(eta), None
         if eta > 0:
-            if not hasattr(self.scheduler, "_get_variance"):
+            if not self.scheduler.takes_eta:
                 raise ValueError("eta > 0 is a DDIMScheduler option")
             self._fill_noise_table(latents, generator, num_inference_steps, n_steps, begin)
 
@@ -677,7 +671,7 @@ class StableDiffusionPipeline(_LatentDiffusionBase):
         self._set_schedule(num_inference_steps, None, None)
         latents = self._noise_latents(latents, generator, embeds[0].shape[0], height, width)
         cond = self._conditioning(*embeds, do_cfg)
-        if eta > 0 and not hasattr(self.scheduler, "_get_variance"):
+        if eta > 0 and not self.scheduler.takes_eta:
             # (this pipeline's own wording of `_set_eta`'s refusal)
             raise ValueError("eta > 0 is a DDIMScheduler option (pipeline_stable_diffusion.py:608-625 passes it only "
                              "to schedulers whose step() accepts it)")
@@ -1174,7 +1168,7 @@ class _InpaintMixin:
         if st is None or st["masked"] is None:
             return super()._predict_noise(latents, cond, do_cfg)
         sch = self.scheduler
-        euler = _scales_model_input(sch)
+        euler = sch.scales_model_input
         if euler:
             if sch._step_index is None:
                 sch._init_step_index(sch.timesteps[0])

@@ -43,20 +43,22 @@ def _betas(beta_schedule, beta_start, beta_end, n, trained_betas=None):
     raise NotImplementedError(f"{beta_schedule} is not implemented")
 
 
-def _alpha_noise_coeffs(alphas_cumprod, timesteps, dtype):
-    """DDIM / DDPM add_noise (scheduling_ddim.py, scheduling_ddpm.py): sqrt(abar_t) and sqrt(1 - abar_t) of abar cast to the
-    latents' dtype, each op in that dtype."""
-    ac = alphas_cumprod.to(dtype=dtype)
-    t = torch.as_tensor(timesteps).reshape(-1).cpu().long()
-    return [float(v) for v in ac[t] ** 0.5], [float(v) for v in (1 - ac[t]) ** 0.5]
-
+_INT_TIMESTEP_MSG = ("Passing integer indices (e.g. from `enumerate(timesteps)`) as timesteps to `{}.step()` is not supported. "
+                     "Make sure to pass one of the `scheduler.timesteps` as a timestep.")
 
 _SERIAL = itertools.count(1)     # one number per scheduler object ever built in this process (graph_token)
 
 
 class _SchedulerBase:
     order = 1
+    init_noise_sigma = 1.0        # (the two Euler classes: a property of their sigmas)
     _defaults: dict = {}
+    # what the pipelines ask a scheduler instead of looking at its class
+    needs_step_noise = False      # a stochastic sampler: the pipelines pre-draw one randn per step (see EulerAncestralDiscreteScheduler)
+    scales_model_input = False    # ``scale_model_input`` divides by sqrt(sigma^2 + 1) (slot 3 of the table row); identity otherwise
+    takes_eta = False             # ``step`` / ``step_cfg`` take DDIM's ``eta``
+    _tuple_tail = ()              # what ``step(return_dict=False)`` returns after the sample: the reference's (prev,) or (prev, None)
+    _bounded_steps = False        # a step past the end of the schedule is refused (it would read a table row that is not there)
 
     def __init__(self, **kwargs):
         self._serial = next(_SERIAL)
@@ -71,6 +73,7 @@ class _SchedulerBase:
         self._table = None          # device [n_steps][8] fp32
         self._step_dev = None       # device int32 scalar
         self._device = None
+        self._noise_coef = None     # device [n_steps + 1][2] fp32 (add_noise_table)
         self.num_inference_steps = None
 
     @classmethod
@@ -83,6 +86,14 @@ class _SchedulerBase:
         src.update(kwargs)
         known = {k: (tuple(v) if isinstance(v, list) else v) for k, v in src.items() if k in cls._defaults}
         return cls(**known)
+
+    def _set_vp_ladder(self):
+        """The fp32 variance-preserving training ladder of Euler, Euler a, DDIM and DDPM: ``betas`` -> ``alphas`` ->
+        ``alphas_cumprod``.  (DPM-Solver++ builds its own in float64 and rounds once: not bit-equal to this one.)"""
+        c = self.config
+        self.betas = _betas(c.beta_schedule, c.beta_start, c.beta_end, c.num_train_timesteps, c.trained_betas)
+        self.alphas = 1.0 - self.betas
+        self.alphas_cumprod = torch.cumprod(self.alphas, dim=0)
 
     # -- reference-compatible index bookkeeping (scheduling_euler_discrete.py:293-324, :640-683) --
     @property
@@ -137,14 +148,17 @@ class _SchedulerBase:
         finally:
             self._begin_index, self._step_index = keep
         rows[n] = 1.0, 0.0
-        host = torch.from_numpy(rows)
-        dev = self.timesteps.device
-        old = getattr(self, "_noise_coef", None)
-        if old is not None and old.device == dev and tuple(old.shape) == tuple(host.shape):
-            old.copy_(host)
-        else:
-            self._noise_coef = host.to(dev)
+        self._refresh_device("_noise_coef", torch.from_numpy(rows), self.timesteps.device)
         return self._noise_coef
+
+    def _noise_index(self, timesteps):
+        """The schedule entry whose sigma ``add_noise`` uses, per timestep (scheduling_euler_discrete.py add_noise and its copies):
+        the step at ``begin_index`` (img2img: before the first step), at ``step_index`` (after it), or each timestep's own index
+        when no begin index is set."""
+        ts = torch.as_tensor(timesteps).reshape(-1).cpu()
+        if self.begin_index is None:
+            return [self.index_for_timestep(t) for t in ts]
+        return [self.step_index if self.step_index is not None else self.begin_index] * ts.shape[0]
 
     def index_for_timestep(self, timestep, schedule_timesteps=None):
         ts = self._timesteps_host if schedule_timesteps is None else np.asarray(schedule_timesteps.cpu())
@@ -162,22 +176,74 @@ class _SchedulerBase:
         if self._step_dev is not None:
             self._step_dev.fill_(int(self._step_index))
 
+    def _refresh_device(self, attr: str, host: torch.Tensor, device, same_device=None) -> bool:
+        """Device buffer ``self.<attr>`` <- ``host``: IN PLACE while its shape and device are unchanged, so that HIP graphs that
+        captured its address (the pipelines' per-step graph) stay valid across set_timesteps() calls; a new buffer otherwise.
+        True when the old buffer was kept."""
+        old = getattr(self, attr)
+        if same_device is None:
+            same_device = old is not None and old.device == device
+        if old is not None and same_device and tuple(old.shape) == tuple(host.shape):
+            old.copy_(host)
+            return True
+        setattr(self, attr, host.to(device))
+        return False
+
     def _upload(self, rows: np.ndarray, device):
         dev = torch.device(device) if device is not None else torch.device("cuda")
         host = torch.from_numpy(np.ascontiguousarray(rows, dtype=np.float32))
-        if (self._table is not None and self._device == dev and tuple(self._table.shape) == tuple(host.shape)):
-            # same schedule length as before: refresh IN PLACE so that HIP graphs that captured these two device
-            # addresses (the pipelines' per-step graph) stay valid across set_timesteps() calls
-            self._table.copy_(host)
+        # (the table and the step counter are one pair: a captured step holds both addresses)
+        if self._refresh_device("_table", host, dev, same_device=self._device == dev):
             self._step_dev.zero_()
             return
         self._device = dev
-        self._table = host.to(dev)
         self._step_dev = torch.zeros((), dtype=torch.int32, device=dev)
+
+    def _set_schedule(self, n: int, timesteps: torch.Tensor, timesteps_host: np.ndarray, rows, device):
+        """The common tail of every ``set_timesteps``: the new schedule, no step or begin index, the rows uploaded (``None``: the
+        caller uploads them itself -- classes whose row math can still refuse the schedule, and DDIM, later, per eta)."""
+        self.num_inference_steps = n
+        self.timesteps = timesteps
+        self._timesteps_host = timesteps_host
+        self._step_index = None
+        self._begin_index = None
+        if rows is not None:
+            self._upload(rows, device)
+
+    def _require_schedule(self):
+        if self.num_inference_steps is None:
+            raise ValueError("Number of inference steps is 'None', you need to run 'set_timesteps' after creating the "
+                             "scheduler")
+
+    def _refuse_int_timestep(self, timestep):
+        if isinstance(timestep, int) or (torch.is_tensor(timestep) and timestep.dtype in (torch.int32, torch.int64)):
+            raise ValueError(_INT_TIMESTEP_MSG.format(type(self).__name__))
+
+    def _before_step(self, timestep):
+        """What every fused-step entry point does first: the loop's first call finds its row (host index + device counter)."""
+        if self._bounded_steps:
+            self._require_schedule()
+        if self._step_index is None:
+            self._init_step_index(timestep)
+        if self._bounded_steps and not 0 <= self._step_index < self.num_inference_steps:
+            raise IndexError(f"{type(self).__name__}: step {self._step_index} of a {self.num_inference_steps}-step "
+                             "schedule (call set_timesteps() or reset() before another loop)")
 
     def _advance(self):
         self._step_index += 1
         ops.advance_step(self._step_dev)
+
+    @staticmethod
+    def _draw_like_reference(model_output, generator):
+        """The reference's randn_tensor inside ``step()``: drawn on the generator's device when one is given, in the model output's
+        dtype, then moved to the model output."""
+        gdev = generator.device if generator is not None else model_output.device
+        return torch.randn(model_output.shape, generator=generator, device=gdev, dtype=model_output.dtype).to(model_output.device)
+
+    def _result(self, prev, return_dict: bool):
+        if not return_dict:
+            return (prev,) + self._tuple_tail
+        return SchedulerOutput(prev_sample=prev)
 
     # engine extension: handles for graph capture
     @property
@@ -200,6 +266,10 @@ class _SchedulerBase:
     def graph_buffers(self, sample):
         """Engine extension: addresses of device state a captured step reads besides the table and the step counter."""
         return ()
+
+    def ensure_table(self, eta: float = 0.0) -> None:
+        """Engine extension: have the table a step with this ``eta`` reads in place before ``device_table``'s address is taken.
+        Only DDIM's rows depend on a ``step`` argument."""
 
     def graph_token(self):
         """Engine extension: what a captured step takes from this scheduler BY VALUE -- its class picks the sampler kernel and
@@ -275,26 +345,57 @@ def _euler_rows(sigmas: torch.Tensor, ts, n: int) -> np.ndarray:
     return rows
 
 
-_INT_TIMESTEP_MSG = ("Passing integer indices (e.g. from `enumerate(timesteps)`) as timesteps to `{}.step()` is not supported. "
-                     "Make sure to pass one of the `scheduler.timesteps` as a timestep.")
+class _EulerBase(_SchedulerBase):
+    """What EulerDiscreteScheduler and EulerAncestralDiscreteScheduler share (scheduling_euler_discrete.py and its copy
+    scheduling_euler_ancestral_discrete.py): the fp32 VP training ladder as k-diffusion sigmas, ``init_noise_sigma``,
+    ``scale_model_input``, add_noise = x + n sigma, and a schedule as float32 timesteps with sigmas interpolated from the ladder."""
+
+    scales_model_input = True
+    _tuple_tail = (None,)
+
+    def _init_ladder(self):
+        c = self.config
+        self._set_vp_ladder()
+        sig = (((1 - self.alphas_cumprod) / self.alphas_cumprod) ** 0.5).flip(0)
+        ts = np.linspace(0, c.num_train_timesteps - 1, c.num_train_timesteps, dtype=float)[::-1].copy()
+        self.timesteps = torch.from_numpy(ts).to(dtype=torch.float32)
+        self._timesteps_host = self.timesteps.numpy()
+        self.sigmas = torch.cat([sig, torch.zeros(1)])
+        self.is_scale_input_called = False
+
+    @property
+    def init_noise_sigma(self):
+        max_sigma = self.sigmas.max()
+        if self.config.timestep_spacing in ("linspace", "trailing"):
+            return max_sigma
+        return (max_sigma ** 2 + 1) ** 0.5
+
+    def _training_sigmas(self) -> np.ndarray:
+        return (((1 - self.alphas_cumprod) / self.alphas_cumprod) ** 0.5).numpy()
+
+    def _set_sigma_schedule(self, sig, ts, num_inference_steps, device) -> np.ndarray:
+        """Sigma ladder (terminal value included) + model timesteps -> the scheduler's state; returns the Euler rows, which the
+        caller uploads (Euler a after putting its own two slots in)."""
+        self.sigmas = torch.from_numpy(sig).to(dtype=torch.float32)    # kept on the CPU like the reference
+        ts32 = ts.astype(np.float32)
+        self._set_schedule(num_inference_steps, torch.from_numpy(ts32).to(device=device), ts32, None, device)
+        return _euler_rows(self.sigmas, ts, num_inference_steps)
+
+    def _add_noise_coeffs(self, timesteps, dtype):
+        """scheduling_euler_discrete.py add_noise: x + n sigma, sigma of the entry ``_noise_index`` picks; sigmas cast to
+        ``dtype``."""
+        sig = self.sigmas.to(dtype=dtype)
+        idx = self._noise_index(timesteps)
+        return [1.0] * len(idx), [float(sig[i]) for i in idx]
+
+    def scale_model_input(self, sample, timestep=None, rep: int = 1):
+        if self._step_index is None:
+            self._init_step_index(timestep)
+        self.is_scale_input_called = True
+        return ops.euler_scale_model_input(sample, self._table, self._step_dev, rep=rep)
 
 
-def _sigma_noise_coeffs(sch, timesteps, dtype):
-    """add_noise = x + n sigma of the k-diffusion style schedulers (scheduling_euler_discrete.py add_noise): sigma of the step at
-    ``begin_index`` (img2img: before the first step), at ``step_index`` (after it), or of each timestep's index when no begin
-    index is set; sigmas cast to ``dtype``."""
-    sig = sch.sigmas.to(dtype=dtype)
-    ts = torch.as_tensor(timesteps).reshape(-1).cpu()
-    if sch.begin_index is None:
-        idx = [sch.index_for_timestep(t) for t in ts]
-    elif sch.step_index is not None:
-        idx = [sch.step_index] * ts.shape[0]
-    else:
-        idx = [sch.begin_index] * ts.shape[0]
-    return [1.0] * len(idx), [float(sig[i]) for i in idx]
-
-
-class EulerDiscreteScheduler(_SchedulerBase):
+class EulerDiscreteScheduler(_EulerBase):
     _defaults = dict(num_train_timesteps=1000, beta_start=0.0001, beta_end=0.02, beta_schedule="linear",
                      trained_betas=None, prediction_type="epsilon", interpolation_type="linear",
                      use_karras_sigmas=False, use_exponential_sigmas=False, use_beta_sigmas=False, sigma_min=None,
@@ -317,22 +418,7 @@ class EulerDiscreteScheduler(_SchedulerBase):
             self._pred = L.PRED_TYPES[c.prediction_type]
         else:
             raise ValueError(f"prediction_type given as {c.prediction_type} must be one of `epsilon`, or `v_prediction`")
-        self.betas = _betas(c.beta_schedule, c.beta_start, c.beta_end, c.num_train_timesteps, c.trained_betas)
-        self.alphas = 1.0 - self.betas
-        self.alphas_cumprod = torch.cumprod(self.alphas, dim=0)
-        sig = (((1 - self.alphas_cumprod) / self.alphas_cumprod) ** 0.5).flip(0)
-        ts = np.linspace(0, c.num_train_timesteps - 1, c.num_train_timesteps, dtype=float)[::-1].copy()
-        self.timesteps = torch.from_numpy(ts).to(dtype=torch.float32)
-        self._timesteps_host = self.timesteps.numpy()
-        self.sigmas = torch.cat([sig, torch.zeros(1)])
-        self.is_scale_input_called = False
-
-    @property
-    def init_noise_sigma(self):
-        max_sigma = self.sigmas.max()
-        if self.config.timestep_spacing in ("linspace", "trailing"):
-            return max_sigma
-        return (max_sigma ** 2 + 1) ** 0.5
+        self._init_ladder()
 
     def set_timesteps(self, num_inference_steps: int = None, device=None, timesteps=None, sigmas=None):
         c = self.config
@@ -351,17 +437,17 @@ class EulerDiscreteScheduler(_SchedulerBase):
         if num_inference_steps is None:
             num_inference_steps = len(timesteps) if timesteps is not None else len(sigmas) - 1
         self.num_inference_steps = num_inference_steps
-        n_train = c.num_train_timesteps
-        base = (((1 - self.alphas_cumprod) / self.alphas_cumprod) ** 0.5).numpy()
+        base = self._training_sigmas()
+        log_base = np.log(base)
         if sigmas is not None:
             sig_full = np.array(sigmas).astype(np.float32)
-            ts = np.array([_sigma_to_t(s_, np.log(base)) for s_ in sig_full[:-1]])
-            self._finish_timesteps(sig_full, ts, num_inference_steps, device)
+            ts = np.array([_sigma_to_t(s_, log_base) for s_ in sig_full[:-1]])
+            self._upload(self._set_sigma_schedule(sig_full, ts, num_inference_steps, device), device)
             return
         if timesteps is not None:
             ts = np.array(timesteps).astype(np.float32)
         else:
-            ts = _euler_spaced_timesteps(c.timestep_spacing, n_train, num_inference_steps, c.steps_offset)
+            ts = _euler_spaced_timesteps(c.timestep_spacing, c.num_train_timesteps, num_inference_steps, c.steps_offset)
         sig = np.interp(ts, np.arange(0, len(base)), base)
         if c.use_karras_sigmas or c.use_exponential_sigmas:
             # a re-spaced sigma ladder between the interpolated extremes (scheduling_euler_discrete.py:446-452, :520-585);
@@ -370,65 +456,40 @@ class EulerDiscreteScheduler(_SchedulerBase):
             smin = c.sigma_min if c.sigma_min is not None else sig[-1].item()
             smax = c.sigma_max if c.sigma_max is not None else sig[0].item()
             sig = _respaced_sigmas(smin, smax, num_inference_steps, karras=c.use_karras_sigmas)
-            ts = np.array([_sigma_to_t(s_, np.log(base)) for s_ in sig])
+            ts = np.array([_sigma_to_t(s_, log_base) for s_ in sig])
         if c.final_sigmas_type == "sigma_min":
             last = float(((1 - self.alphas_cumprod[0]) / self.alphas_cumprod[0]) ** 0.5)
         elif c.final_sigmas_type == "zero":
             last = 0
         else:
             raise ValueError(f"`final_sigmas_type` must be one of 'zero', or 'sigma_min', but got {c.final_sigmas_type}")
-        self._finish_timesteps(np.concatenate([sig, [last]]).astype(np.float32), ts, num_inference_steps, device)
+        sig = np.concatenate([sig, [last]]).astype(np.float32)
+        self._upload(self._set_sigma_schedule(sig, ts, num_inference_steps, device), device)
 
-    def _finish_timesteps(self, sig, ts, num_inference_steps, device):
-        """Sigma ladder (terminal value included) + model timesteps -> the scheduler's state and the device coefficient table."""
-        self.sigmas = torch.from_numpy(sig).to(dtype=torch.float32)  # kept on CPU like the reference
-        self.timesteps = torch.from_numpy(ts.astype(np.float32)).to(device=device)
-        self._timesteps_host = ts.astype(np.float32)
-        self._step_index = None
-        self._begin_index = None
-        self._upload(_euler_rows(self.sigmas, ts, num_inference_steps), device)
-
-    def _add_noise_coeffs(self, timesteps, dtype):
-        """scheduling_euler_discrete.py add_noise: x + n sigma, sigma of the step at ``begin_index`` (img2img: before the first
-        step), at ``step_index`` (after it), or of each timestep's index when no begin index is set; sigmas cast to ``dtype``."""
-        return _sigma_noise_coeffs(self, timesteps, dtype)
-
-    def scale_model_input(self, sample, timestep=None, rep: int = 1):
-        if self._step_index is None:
-            self._init_step_index(timestep)
-        self.is_scale_input_called = True
-        return ops.euler_scale_model_input(sample, self._table, self._step_dev, rep=rep)
+    def _run(self, model_output, sample, cfg, guidance, out=None):
+        """The one caller of this class's fused step (da_euler_step)."""
+        prev = ops.euler_step(model_output, sample, self._table, self._step_dev, cfg=cfg, guidance=guidance, out=out,
+                              pred_type=self._pred)
+        self._advance()
+        return prev
 
     def step(self, model_output, timestep, sample, s_churn: float = 0.0, s_tmin: float = 0.0,
              s_tmax: float = float("inf"), s_noise: float = 1.0, generator=None, return_dict: bool = True):
-        if isinstance(timestep, int) or (torch.is_tensor(timestep) and timestep.dtype in (torch.int32, torch.int64)):
-            raise ValueError("Passing integer indices (e.g. from `enumerate(timesteps)`) as timesteps to "
-                             "`EulerDiscreteScheduler.step()` is not supported. Make sure to pass one of the "
-                             "`scheduler.timesteps` as a timestep.")
+        self._refuse_int_timestep(timestep)
         if s_churn != 0.0:
             raise NotImplementedError("s_churn > 0 (stochastic Euler) is not on the hot path")
-        if self._step_index is None:
-            self._init_step_index(timestep)
-        prev = ops.euler_step(model_output.contiguous(), sample.contiguous(), self._table, self._step_dev, cfg=False,
-                              guidance=0.0, pred_type=self._pred)
-        self._advance()
-        if not return_dict:
-            return (prev, None)
-        return SchedulerOutput(prev_sample=prev)
+        self._before_step(timestep)
+        return self._result(self._run(model_output.contiguous(), sample.contiguous(), False, 0.0), return_dict)
 
     def step_cfg(self, model_output_2b, sample, guidance_scale: float, out=None, cfg: bool = True):
         """Engine extension: CFG combine + Euler step in one kernel; model_output_2b = [uncond ; cond] (``cfg=False``:
         a plain model output -- the ``guidance_scale <= 1`` loop of the pipelines -- with the same in-place ``out``)."""
-        if self._step_index is None:
-            self._init_step_index(self.timesteps[0])
-        prev = ops.euler_step(model_output_2b, sample, self._table, self._step_dev, cfg=cfg,
-                              guidance=float(guidance_scale), out=out, pred_type=self._pred)
-        self._advance()
-        return prev
+        self._before_step(self.timesteps[0])
+        return self._run(model_output_2b, sample, cfg, float(guidance_scale), out)
 
 
 # ----------------------------------------------------------------------------------------------------------------------
-class EulerAncestralDiscreteScheduler(_SchedulerBase):
+class EulerAncestralDiscreteScheduler(_EulerBase):
     """schedulers/scheduling_euler_ancestral_discrete.py ("Euler a"): the Euler step towards ``sigma_down`` plus fresh noise of
     scale ``sigma_up`` per step, with sigma_down^2 + sigma_up^2 = sigma_to^2.  The table row is the Euler row with
     dt = sigma_down - sigma in slot 2 and sigma_up in slot 6, both evaluated with fp32 torch scalar ops in the reference's order;
@@ -440,6 +501,7 @@ class EulerAncestralDiscreteScheduler(_SchedulerBase):
                      prediction_type="epsilon", timestep_spacing="linspace", steps_offset=0, rescale_betas_zero_snr=False)
     needs_step_noise = True          # the pipelines pre-draw one randn per step that runs, after every other draw of the call ...
     step_noise_dtype = "model_output"  # ... in the model output's dtype (scheduling_euler_ancestral_discrete.py: randn_tensor(dtype=))
+    _bounded_steps = True
 
     def __init__(self, **kwargs):
         super().__init__(**kwargs)
@@ -451,37 +513,16 @@ class EulerAncestralDiscreteScheduler(_SchedulerBase):
         if c.prediction_type not in ("epsilon", "v_prediction"):
             raise ValueError(f"prediction_type given as {c.prediction_type} must be one of `epsilon`, or `v_prediction`")
         self._pred = L.PRED_TYPES[c.prediction_type]
-        self.betas = _betas(c.beta_schedule, c.beta_start, c.beta_end, c.num_train_timesteps, c.trained_betas)
-        self.alphas = 1.0 - self.betas
-        self.alphas_cumprod = torch.cumprod(self.alphas, dim=0)
-        sig = (((1 - self.alphas_cumprod) / self.alphas_cumprod) ** 0.5).flip(0)
-        ts = np.linspace(0, c.num_train_timesteps - 1, c.num_train_timesteps, dtype=float)[::-1].copy()
-        self.timesteps = torch.from_numpy(ts).to(dtype=torch.float32)
-        self._timesteps_host = self.timesteps.numpy()
-        self.sigmas = torch.cat([sig, torch.zeros(1)])
-        self.is_scale_input_called = False
-
-    @property
-    def init_noise_sigma(self):
-        max_sigma = self.sigmas.max()
-        if self.config.timestep_spacing in ("linspace", "trailing"):
-            return max_sigma
-        return (max_sigma ** 2 + 1) ** 0.5
+        self._init_ladder()
 
     def set_timesteps(self, num_inference_steps: int, device=None):
         c = self.config
         n = int(num_inference_steps)
         self.num_inference_steps = n
         ts = _euler_spaced_timesteps(c.timestep_spacing, c.num_train_timesteps, n, c.steps_offset)
-        base = (((1 - self.alphas_cumprod) / self.alphas_cumprod) ** 0.5).numpy()
+        base = self._training_sigmas()
         sig = np.interp(ts, np.arange(0, len(base)), base)
-        sig = np.concatenate([sig, [0.0]]).astype(np.float32)
-        self.sigmas = torch.from_numpy(sig)                           # kept on the CPU like the reference
-        self.timesteps = torch.from_numpy(ts.astype(np.float32)).to(device=device)
-        self._timesteps_host = ts.astype(np.float32)
-        self._step_index = None
-        self._begin_index = None
-        rows = _euler_rows(self.sigmas, ts, n)
+        rows = self._set_sigma_schedule(np.concatenate([sig, [0.0]]).astype(np.float32), ts, n, device)
         for i in range(n):
             sigma, sigma_to = self.sigmas[i], self.sigmas[i + 1]      # 0-d fp32 tensors: every op below rounds to fp32
             sigma_up = (sigma_to ** 2 * (sigma ** 2 - sigma_to ** 2) / sigma ** 2) ** 0.5
@@ -492,40 +533,20 @@ class EulerAncestralDiscreteScheduler(_SchedulerBase):
             raise ValueError("EulerAncestralDiscreteScheduler: non-finite step coefficients (a sigma of 0 before the last row?)")
         self._upload(rows, device)
 
-    def _add_noise_coeffs(self, timesteps, dtype):
-        return _sigma_noise_coeffs(self, timesteps, dtype)
-
-    def scale_model_input(self, sample, timestep=None, rep: int = 1):
-        if self._step_index is None:
-            self._init_step_index(timestep)
-        self.is_scale_input_called = True
-        return ops.euler_scale_model_input(sample, self._table, self._step_dev, rep=rep)
-
-    def _before_step(self, timestep):
-        if self.num_inference_steps is None:
-            raise ValueError("Number of inference steps is 'None', you need to run 'set_timesteps' after creating the "
-                             "scheduler")
-        if self._step_index is None:
-            self._init_step_index(timestep)
-        if not 0 <= self._step_index < self.num_inference_steps:
-            raise IndexError(f"EulerAncestralDiscreteScheduler: step {self._step_index} of a {self.num_inference_steps}-step "
-                             "schedule (call set_timesteps() or reset() before another loop)")
+    def _run(self, model_output, sample, noise, noise_step_stride, cfg, guidance, out=None):
+        """The one caller of this class's fused step (da_euler_ancestral_step)."""
+        prev = ops.euler_ancestral_step(model_output, sample, noise, self._table, self._step_dev, cfg=cfg, guidance=guidance,
+                                        out=out, pred_type=self._pred, noise_step_stride=noise_step_stride)
+        self._advance()
+        return prev
 
     def step(self, model_output, timestep, sample, generator=None, return_dict: bool = True):
-        if isinstance(timestep, int) or (torch.is_tensor(timestep) and timestep.dtype in (torch.int32, torch.int64)):
-            raise ValueError(_INT_TIMESTEP_MSG.format("EulerAncestralDiscreteScheduler"))
+        self._refuse_int_timestep(timestep)
         self._before_step(timestep)
-        # randn_tensor: on the generator's device when one is given, in the model output's dtype, then moved to the model output
-        gdev = generator.device if generator is not None else model_output.device
-        noise = torch.randn(model_output.shape, generator=generator, device=gdev,
-                            dtype=model_output.dtype).to(model_output.device)
+        noise = self._draw_like_reference(model_output, generator)
         # (the reference upcasts the sample and returns the model output's dtype; here the two share one dtype)
-        prev = ops.euler_ancestral_step(model_output.contiguous(), sample.contiguous(), noise.contiguous(), self._table,
-                                        self._step_dev, cfg=False, guidance=0.0, pred_type=self._pred, noise_step_stride=0)
-        self._advance()
-        if not return_dict:
-            return (prev, None)
-        return SchedulerOutput(prev_sample=prev)
+        prev = self._run(model_output.contiguous(), sample.contiguous(), noise.contiguous(), 0, False, 0.0)
+        return self._result(prev, return_dict)
 
     def step_cfg(self, model_output_2b, sample, guidance_scale: float, out=None, cfg: bool = True, noise_table=None):
         """Engine extension: CFG combine (``cfg=False``: a plain model output) + the ancestral step in one kernel, in place when
@@ -538,20 +559,71 @@ class EulerAncestralDiscreteScheduler(_SchedulerBase):
         if noise_table.shape[0] != self.num_inference_steps:
             raise ValueError(f"EulerAncestralDiscreteScheduler.step_cfg: `noise_table` has {noise_table.shape[0]} rows for a "
                              f"{self.num_inference_steps}-step schedule")
-        prev = ops.euler_ancestral_step(model_output_2b, sample, noise_table, self._table, self._step_dev, cfg=cfg,
-                                        guidance=float(guidance_scale), out=out, pred_type=self._pred,
-                                        noise_step_stride=sample.numel())
+        return self._run(model_output_2b, sample, noise_table, sample.numel(), cfg, float(guidance_scale), out)
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+class _AlphaBarBase(_SchedulerBase):
+    """What DDIMScheduler and DDPMScheduler share: the fp32 VP ladder read at int64 timesteps, add_noise from it, the int64
+    timestep spacing, ``step()`` indexed by timestep (the reference's two are stateless), and the fused step da_x0_linear_step."""
+
+    _tuple_tail = (None,)
+
+    def _init_ladder(self):
+        self._set_vp_ladder()
+        self.timesteps = torch.from_numpy(np.arange(0, self.config.num_train_timesteps)[::-1].copy().astype(np.int64))
+        self._timesteps_host = self.timesteps.numpy()
+
+    def _add_noise_coeffs(self, timesteps, dtype):
+        """DDIM / DDPM add_noise (scheduling_ddim.py, scheduling_ddpm.py): sqrt(abar_t) and sqrt(1 - abar_t) of abar cast to the
+        latents' dtype, each op in that dtype."""
+        ac = self.alphas_cumprod.to(dtype=dtype)
+        t = torch.as_tensor(timesteps).reshape(-1).cpu().long()
+        return [float(v) for v in ac[t] ** 0.5], [float(v) for v in (1 - ac[t]) ** 0.5]
+
+    def _spaced_timesteps(self, n: int, too_many: str = "", unsupported: str = "") -> np.ndarray:
+        """The int64 model timesteps of an ``n``-step schedule (scheduling_ddim.py:347-371, the same three branches in
+        scheduling_ddpm.py); ``too_many`` / ``unsupported``: how the calling class's wording of the two refusals goes on."""
+        c = self.config
+        n_train = c.num_train_timesteps
+        if n > n_train:
+            raise ValueError(f"`num_inference_steps`: {n} cannot be larger than `self.config.train_timesteps`: {n_train}{too_many}")
+        self.num_inference_steps = n
+        if c.timestep_spacing == "linspace":
+            return np.linspace(0, n_train - 1, n).round()[::-1].copy().astype(np.int64)
+        if c.timestep_spacing == "leading":
+            ts = (np.arange(0, n) * (n_train // n)).round()[::-1].copy().astype(np.int64)
+            ts += c.steps_offset
+            return ts
+        if c.timestep_spacing == "trailing":
+            ts = np.round(np.arange(n_train, 0, -(n_train / n))).astype(np.int64)
+            ts -= 1
+            return ts
+        raise ValueError(f"{c.timestep_spacing} is not supported.{unsupported}")
+
+    def _seek(self, timestep) -> int:
+        """``step()`` is stateless in the reference (indexed by timestep): honour out-of-order calls."""
+        idx = self.index_for_timestep(timestep)
+        if idx != self._step_index:
+            self._step_index = idx
+            self._sync_device_step()
+        return idx
+
+    def _run(self, model_output, sample, noise, noise_step_stride, cfg, guidance, out=None):
+        """The one caller of these classes' fused step (da_x0_linear_step)."""
+        prev = ops.x0_linear_step(model_output, sample, noise, self._table, self._step_dev, cfg=cfg, guidance=guidance, out=out,
+                                  noise_step_stride=noise_step_stride, pred_type=self._pred)
         self._advance()
         return prev
 
 
-# ----------------------------------------------------------------------------------------------------------------------
-class DDIMScheduler(_SchedulerBase):
+class DDIMScheduler(_AlphaBarBase):
     _defaults = dict(num_train_timesteps=1000, beta_start=0.0001, beta_end=0.02, beta_schedule="linear",
                      trained_betas=None, clip_sample=True, set_alpha_to_one=True, steps_offset=0,
                      prediction_type="epsilon", thresholding=False, dynamic_thresholding_ratio=0.995,
                      clip_sample_range=1.0, sample_max_value=1.0, timestep_spacing="leading",
                      rescale_betas_zero_snr=False)
+    takes_eta = True
 
     def __init__(self, **kwargs):
         super().__init__(**kwargs)
@@ -562,17 +634,9 @@ class DDIMScheduler(_SchedulerBase):
             raise ValueError(f"prediction_type given as {c.prediction_type} must be one of `epsilon`, `sample`, or "
                              "`v_prediction`")
         self._pred = L.PRED_TYPES[c.prediction_type]
-        self.betas = _betas(c.beta_schedule, c.beta_start, c.beta_end, c.num_train_timesteps, c.trained_betas)
-        self.alphas = 1.0 - self.betas
-        self.alphas_cumprod = torch.cumprod(self.alphas, dim=0)
+        self._init_ladder()
         self.final_alpha_cumprod = torch.tensor(1.0) if c.set_alpha_to_one else self.alphas_cumprod[0]
-        self.init_noise_sigma = 1.0
-        self.timesteps = torch.from_numpy(np.arange(0, c.num_train_timesteps)[::-1].copy().astype(np.int64))
-        self._timesteps_host = self.timesteps.numpy()
         self._eta = None
-
-    def _add_noise_coeffs(self, timesteps, dtype):
-        return _alpha_noise_coeffs(self.alphas_cumprod, timesteps, dtype)
 
     def _get_variance(self, timestep, prev_timestep):
         a_t = self.alphas_cumprod[timestep]
@@ -582,30 +646,11 @@ class DDIMScheduler(_SchedulerBase):
         return (b_prev / b_t) * (1 - a_t / a_prev)
 
     def set_timesteps(self, num_inference_steps: int, device=None):
-        c = self.config
-        if num_inference_steps > c.num_train_timesteps:
-            raise ValueError(f"`num_inference_steps`: {num_inference_steps} cannot be larger than "
-                             f"`self.config.train_timesteps`: {c.num_train_timesteps} as the unet model trained with "
-                             f"this scheduler can only handle maximal {c.num_train_timesteps} timesteps.")
-        self.num_inference_steps = num_inference_steps
-        n_train = c.num_train_timesteps
-        if c.timestep_spacing == "linspace":
-            ts = np.linspace(0, n_train - 1, num_inference_steps).round()[::-1].copy().astype(np.int64)
-        elif c.timestep_spacing == "leading":
-            ratio = n_train // num_inference_steps
-            ts = (np.arange(0, num_inference_steps) * ratio).round()[::-1].copy().astype(np.int64)
-            ts += c.steps_offset
-        elif c.timestep_spacing == "trailing":
-            ratio = n_train / num_inference_steps
-            ts = np.round(np.arange(n_train, 0, -ratio)).astype(np.int64)
-            ts -= 1
-        else:
-            raise ValueError(f"{c.timestep_spacing} is not supported. Please make sure to choose one of 'leading' or "
-                             "'trailing'.")
-        self.timesteps = torch.from_numpy(ts).to(device)
-        self._timesteps_host = ts
-        self._step_index = None
-        self._begin_index = None
+        ts = self._spaced_timesteps(
+            num_inference_steps,
+            f" as the unet model trained with this scheduler can only handle maximal {self.config.num_train_timesteps} timesteps.",
+            " Please make sure to choose one of 'leading' or 'trailing'.")
+        self._set_schedule(num_inference_steps, torch.from_numpy(ts).to(device), ts, None, device)
         self._device_req = device
         self._eta = None   # table rows are rebuilt lazily for the eta of the first step(); buffers are reused in place
 
@@ -645,68 +690,57 @@ class DDIMScheduler(_SchedulerBase):
     def _ensure(self, eta, timestep):
         if self._table is None or self._eta != eta:
             self._rebuild(eta)
-        if self._step_index is None:
-            self._init_step_index(timestep)
+        self._before_step(timestep)
+
+    def ensure_table(self, eta: float = 0.0) -> None:
+        """Engine extension: the rows of ``eta`` built (in place where the buffers exist) and the loop's first row found, before a
+        captured step's key reads ``device_table``'s address -- reading it first builds the rows of eta 0."""
+        self._ensure(eta, self.timesteps[0])
 
     def step(self, model_output, timestep, sample, eta: float = 0.0, use_clipped_model_output: bool = False,
              generator=None, variance_noise=None, return_dict: bool = True):
-        if self.num_inference_steps is None:
-            raise ValueError("Number of inference steps is 'None', you need to run 'set_timesteps' after creating "
-                             "the scheduler")
+        self._require_schedule()
         if use_clipped_model_output:
             raise NotImplementedError("use_clipped_model_output is not on the hot path")
         self._ensure(eta, timestep)
-        # DDIM is stateless in the reference (indexed by timestep): honour out-of-order calls
-        idx = self.index_for_timestep(timestep)
-        if idx != self._step_index:
-            self._step_index = idx
-            self._sync_device_step()
+        self._seek(timestep)
         noise = None
         if eta > 0:
             if variance_noise is not None and generator is not None:
                 raise ValueError("Cannot pass both generator and variance_noise. Please make sure that either "
                                  "`generator` or `variance_noise` stays `None`.")
-            if variance_noise is None:
-                gdev = generator.device if generator is not None else model_output.device
-                variance_noise = torch.randn(model_output.shape, generator=generator, device=gdev,
-                                             dtype=model_output.dtype).to(model_output.device)
-            noise = variance_noise
-        prev = ops.x0_linear_step(model_output.contiguous(), sample.contiguous(), noise, self._table, self._step_dev,
-                                  cfg=False, guidance=0.0, pred_type=self._pred)
-        self._advance()
-        if not return_dict:
-            return (prev, None)
-        return SchedulerOutput(prev_sample=prev)
+            noise = variance_noise if variance_noise is not None else self._draw_like_reference(model_output, generator)
+        prev = self._run(model_output.contiguous(), sample.contiguous(), noise, 0, False, 0.0)
+        return self._result(prev, return_dict)
 
     def step_cfg(self, model_output_2b, sample, guidance_scale: float, eta: float = 0.0, out=None, cfg: bool = True,
                  noise_table=None):
         """Engine extension: CFG combine (``cfg=False``: plain model output) + DDIM update in one kernel, in place when
         ``out`` is the sample.  ``eta > 0`` needs ``noise_table`` [steps][numel]: every step's variance noise drawn up
         front (the kernel picks the row of the device step counter, so the step stays HIP-graph replayable)."""
-        self._ensure(eta, self.timesteps[0])
+        self.ensure_table(eta)
         if eta > 0 and noise_table is None:
             raise ValueError("DDIMScheduler.step_cfg: eta > 0 needs the pre-drawn `noise_table` [steps][numel]")
-        prev = ops.x0_linear_step(model_output_2b, sample, noise_table if eta > 0 else None, self._table, self._step_dev,
-                                  cfg=cfg, guidance=float(guidance_scale), out=out, pred_type=self._pred,
-                                  noise_step_stride=sample.numel() if eta > 0 else 0)
-        self._advance()
-        return prev
+        return self._run(model_output_2b, sample, noise_table if eta > 0 else None, sample.numel() if eta > 0 else 0, cfg,
+                         float(guidance_scale), out)
+
+    def _built(self):
+        """(a table nobody asked an eta for yet is eta 0's)"""
+        if self._table is None or self._eta is None:
+            self._rebuild(0.0)
+        return self
 
     @property
     def device_table(self):
-        if self._table is None or self._eta is None:
-            self._rebuild(0.0)
-        return self._table
+        return self._built()._table
 
     @property
     def device_step(self):
-        if self._table is None or self._eta is None:
-            self._rebuild(0.0)
-        return self._step_dev
+        return self._built()._step_dev
 
 
 # ----------------------------------------------------------------------------------------------------------------------
-class DDPMScheduler(_SchedulerBase):
+class DDPMScheduler(_AlphaBarBase):
     _defaults = dict(num_train_timesteps=1000, beta_start=0.0001, beta_end=0.02, beta_schedule="linear",
                      trained_betas=None, variance_type="fixed_small", clip_sample=True, prediction_type="epsilon",
                      thresholding=False, dynamic_thresholding_ratio=0.995, clip_sample_range=1.0,
@@ -723,44 +757,16 @@ class DDPMScheduler(_SchedulerBase):
         self._pred = L.PRED_TYPES[c.prediction_type]
         if c.variance_type not in ("fixed_small", "fixed_large"):
             raise NotImplementedError("DDPMScheduler: only fixed_small / fixed_large variance")
-        self.betas = _betas(c.beta_schedule, c.beta_start, c.beta_end, c.num_train_timesteps, c.trained_betas)
-        self.alphas = 1.0 - self.betas
-        self.alphas_cumprod = torch.cumprod(self.alphas, dim=0)
+        self._init_ladder()
         self.one = torch.tensor(1.0)
-        self.init_noise_sigma = 1.0
         self.custom_timesteps = False
-        self.timesteps = torch.from_numpy(np.arange(0, c.num_train_timesteps)[::-1].copy())
-        self._timesteps_host = self.timesteps.numpy()
         self.variance_type = c.variance_type
-
-    def _add_noise_coeffs(self, timesteps, dtype):
-        return _alpha_noise_coeffs(self.alphas_cumprod, timesteps, dtype)
 
     def set_timesteps(self, num_inference_steps: int = None, device=None, timesteps=None):
         c = self.config
         if timesteps is not None:
             raise NotImplementedError("custom timesteps are not supported by the HIP DDPMScheduler")
-        if num_inference_steps > c.num_train_timesteps:
-            raise ValueError(f"`num_inference_steps`: {num_inference_steps} cannot be larger than "
-                             f"`self.config.train_timesteps`: {c.num_train_timesteps}")
-        self.num_inference_steps = num_inference_steps
-        n_train = c.num_train_timesteps
-        if c.timestep_spacing == "linspace":
-            ts = np.linspace(0, n_train - 1, num_inference_steps).round()[::-1].copy().astype(np.int64)
-        elif c.timestep_spacing == "leading":
-            ratio = n_train // num_inference_steps
-            ts = (np.arange(0, num_inference_steps) * ratio).round()[::-1].copy().astype(np.int64)
-            ts += c.steps_offset
-        elif c.timestep_spacing == "trailing":
-            ratio = n_train / num_inference_steps
-            ts = np.round(np.arange(n_train, 0, -ratio)).astype(np.int64)
-            ts -= 1
-        else:
-            raise ValueError(f"{c.timestep_spacing} is not supported.")
-        self.timesteps = torch.from_numpy(ts).to(device)
-        self._timesteps_host = ts
-        self._step_index = None
-        self._begin_index = None
+        ts = self._spaced_timesteps(num_inference_steps)
         rows = np.zeros((len(ts), 8), dtype=np.float32)
         for i, t in enumerate(ts):
             t = int(t)
@@ -787,26 +793,16 @@ class DDPMScheduler(_SchedulerBase):
             rows[i, 5] = float(var ** 0.5) if t > 0 else 0.0
             rows[i, 6] = float(c.clip_sample_range) if c.clip_sample else 0.0
             rows[i, 7] = float(t)
-        self._upload(rows, device)
+        self._set_schedule(num_inference_steps, torch.from_numpy(ts).to(device), ts, rows, device)
 
     def step(self, model_output, timestep, sample, generator=None, return_dict: bool = True, noise=None):
         """scheduling_ddpm.py:461-567.  ``noise`` (engine extension): this step's variance noise instead of a draw from
         ``generator`` (which, like the reference's randn_tensor, draws in the dtype of ``model_output``)."""
-        idx = self.index_for_timestep(timestep)
-        if idx != self._step_index:
-            self._step_index = idx
-            self._sync_device_step()
-        t = int(self._timesteps_host[idx])
+        t = int(self._timesteps_host[self._seek(timestep)])
         if t > 0 and noise is None:
-            gdev = generator.device if generator is not None else model_output.device
-            noise = torch.randn(model_output.shape, generator=generator, device=gdev,
-                                dtype=model_output.dtype).to(model_output.device)
-        prev = ops.x0_linear_step(model_output.contiguous(), sample.contiguous(), noise if t > 0 else None, self._table,
-                                  self._step_dev, cfg=False, guidance=0.0, pred_type=self._pred)
-        self._advance()
-        if not return_dict:
-            return (prev, None)
-        return SchedulerOutput(prev_sample=prev)
+            noise = self._draw_like_reference(model_output, generator)
+        prev = self._run(model_output.contiguous(), sample.contiguous(), noise if t > 0 else None, 0, False, 0.0)
+        return self._result(prev, return_dict)
 
     def step_inplace(self, model_output, sample, noise_table):
         """Engine extension for HIP-graph replay: the update written over ``sample``; ``noise_table`` [steps][numel]
@@ -814,9 +810,7 @@ class DDPMScheduler(_SchedulerBase):
         if self._step_index is None:
             self._step_index = 0
             self._sync_device_step()
-        ops.x0_linear_step(model_output, sample, noise_table, self._table, self._step_dev, cfg=False, guidance=0.0,
-                           out=sample, noise_step_stride=sample.numel(), pred_type=self._pred)
-        self._advance()
+        self._run(model_output, sample, noise_table, sample.numel(), False, 0.0, out=sample)
         return sample
 
 
@@ -846,7 +840,6 @@ class FlowMatchEulerDiscreteScheduler(_SchedulerBase):
         self.sigmas = sig
         self.sigma_min = self.sigmas[-1].item()
         self.sigma_max = self.sigmas[0].item()
-        self.init_noise_sigma = 1.0
 
     @property
     def shift(self):
@@ -872,7 +865,6 @@ class FlowMatchEulerDiscreteScheduler(_SchedulerBase):
                              "`num_inference_steps` is provided")
         if num_inference_steps is None:
             num_inference_steps = len(sigmas)
-        self.num_inference_steps = num_inference_steps
         if sigmas is None:
             ts = np.linspace(self.sigma_max * c.num_train_timesteps, self.sigma_min * c.num_train_timesteps,
                              num_inference_steps)
@@ -886,11 +878,7 @@ class FlowMatchEulerDiscreteScheduler(_SchedulerBase):
         sig_t = torch.from_numpy(np.asarray(sig)).to(dtype=torch.float32)
         ts_t = sig_t * c.num_train_timesteps
         sig_t = torch.cat([sig_t, torch.zeros(1)])
-        self.timesteps = ts_t.to(device)
-        self._timesteps_host = ts_t.numpy()
-        self.sigmas = sig_t.to(device)
-        self._step_index = None
-        self._begin_index = None
+        self.sigmas = sig_t.to(device)          # on the device like the reference's (the other schedulers keep theirs on the CPU)
         rows = np.zeros((num_inference_steps, 8), dtype=np.float32)
         for i in range(num_inference_steps):
             s, s_next = sig_t[i], sig_t[i + 1]
@@ -898,20 +886,13 @@ class FlowMatchEulerDiscreteScheduler(_SchedulerBase):
             rows[i, 1] = float(s_next)
             rows[i, 2] = float(s_next - s)
             rows[i, 7] = float(ts_t[i])
-        self._upload(rows, device)
+        self._set_schedule(num_inference_steps, ts_t.to(device), ts_t.numpy(), rows, device)
 
     def _add_noise_coeffs(self, timesteps, dtype):
         """scale_noise (scheduling_flow_match_euler_discrete.py): ``sigma * noise + (1.0 - sigma) * sample`` with sigma cast to the
-        sample's dtype, so a = dtype(1 - dtype(sigma)) and b = dtype(sigma); sigma of the step at ``begin_index`` (img2img: before
-        the first step), at ``step_index`` (after it), or of each timestep's index when no begin index is set."""
+        sample's dtype, so a = dtype(1 - dtype(sigma)) and b = dtype(sigma); sigma of the entry ``_noise_index`` picks."""
         sig = self.sigmas.to(device="cpu", dtype=dtype)
-        ts = torch.as_tensor(timesteps).reshape(-1).cpu()
-        if self.begin_index is None:
-            idx = [self.index_for_timestep(t) for t in ts]
-        elif self.step_index is not None:
-            idx = [self.step_index] * ts.shape[0]
-        else:
-            idx = [self.begin_index] * ts.shape[0]
+        idx = self._noise_index(timesteps)
         return [float(1.0 - sig[i]) for i in idx], [float(sig[i]) for i in idx]
 
     def scale_noise(self, sample: torch.Tensor, timestep, noise: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -924,35 +905,27 @@ class FlowMatchEulerDiscreteScheduler(_SchedulerBase):
     def step(self, model_output, timestep, sample, s_churn: float = 0.0, s_tmin: float = 0.0,
              s_tmax: float = float("inf"), s_noise: float = 1.0, generator=None, per_token_timesteps=None,
              return_dict: bool = True):
-        if isinstance(timestep, int) or (torch.is_tensor(timestep) and timestep.dtype in (torch.int32, torch.int64)):
-            raise ValueError("Passing integer indices (e.g. from `enumerate(timesteps)`) as timesteps to "
-                             "`FlowMatchEulerDiscreteScheduler.step()` is not supported. Make sure to pass one of the "
-                             "`scheduler.timesteps` as a timestep.")
+        self._refuse_int_timestep(timestep)
         if per_token_timesteps is not None:
             raise NotImplementedError("per_token_timesteps is not on the hot path")
-        if self._step_index is None:
-            self._init_step_index(timestep)
-        prev = ops.flowmatch_step(model_output, sample, self._table, self._step_dev)
+        self._before_step(timestep)
+        return self._result(self._run(model_output, sample), return_dict)
+
+    def _run(self, model_output, sample, cfg=False, guidance=0.0, out=None):
+        """The one caller of this class's fused step (da_flowmatch_step)."""
+        prev = ops.flowmatch_step(model_output, sample, self._table, self._step_dev, cfg=cfg, guidance=guidance, out=out)
         self._advance()
-        if not return_dict:
-            return (prev,)
-        return SchedulerOutput(prev_sample=prev)
+        return prev
 
     def step_inplace(self, model_output, sample):
         """Engine extension: the update written over ``sample`` (same buffer every HIP-graph replay)."""
-        if self._step_index is None:
-            self._init_step_index(self.timesteps[0])
-        ops.flowmatch_step(model_output, sample, self._table, self._step_dev, out=sample)
-        self._advance()
+        self._before_step(self.timesteps[0])
+        self._run(model_output, sample, out=sample)
         return sample
 
     def step_cfg(self, model_output_2b, sample, guidance_scale: float, out=None):
-        if self._step_index is None:
-            self._init_step_index(self.timesteps[0])
-        prev = ops.flowmatch_step(model_output_2b, sample, self._table, self._step_dev, cfg=True,
-                                  guidance=float(guidance_scale), out=out)
-        self._advance()
-        return prev
+        self._before_step(self.timesteps[0])
+        return self._run(model_output_2b, sample, True, float(guidance_scale), out)
 
 
 # ----------------------------------------------------------------------------------------------------------------------
@@ -984,7 +957,6 @@ class UniPCMultistepScheduler(_SchedulerBase):
                 or c.use_beta_sigmas or c.use_dynamic_shifting or c.shift_terminal or not c.lower_order_final
                 or c.final_sigmas_type != "zero"):
             raise NotImplementedError("UniPCMultistepScheduler: unsupported option for the HIP step")
-        self.init_noise_sigma = 1.0
         ts = np.linspace(0, c.num_train_timesteps - 1, c.num_train_timesteps, dtype=np.float32)[::-1].copy()
         self.timesteps = torch.from_numpy(ts)
         self._timesteps_host = ts
@@ -1024,11 +996,8 @@ class UniPCMultistepScheduler(_SchedulerBase):
             sig[0] -= 1e-6
         ts = (sig * c.num_train_timesteps).copy()
         self.sigmas = torch.from_numpy(np.concatenate([sig, [0]]).astype(np.float32))
-        self.timesteps = torch.from_numpy(ts).to(device=device, dtype=torch.int64)
-        self._timesteps_host = self.timesteps.cpu().numpy()
-        self.num_inference_steps = n
-        self._step_index = None
-        self._begin_index = None
+        timesteps = torch.from_numpy(ts).to(device=device, dtype=torch.int64)
+        timesteps_host = timesteps.cpu().numpy()        # (what the device holds: the int64 cast truncates)
         S = self.sigmas
         coef = np.zeros((n, 16), dtype=np.float32)
         rows = np.zeros((n, 8), dtype=np.float32)
@@ -1048,16 +1017,12 @@ class UniPCMultistepScheduler(_SchedulerBase):
             c1, c2, c3, rks, _, _ = self._coeffs(S[i + 1], S[i], [S[i - k] for k in range(1, op)], op)
             coef[i, 9], coef[i, 10], coef[i, 11], coef[i, 12] = float(op), float(c1), float(c2), float(c3)
             coef[i, 13] = float(rks[0]) if op == 2 else 1.0
-            rows[i, 0], rows[i, 1], rows[i, 7] = float(S[i]), float(S[i + 1]), float(self._timesteps_host[i])
+            rows[i, 0], rows[i, 1], rows[i, 7] = float(S[i]), float(S[i + 1]), float(timesteps_host[i])
             prev_order = op
             if lower < c.solver_order:
                 lower += 1
-        self._upload(rows, device)
-        host = torch.from_numpy(coef)
-        if self._coef is not None and tuple(self._coef.shape) == tuple(host.shape) and self._coef.device == self._table.device:
-            self._coef.copy_(host)          # in place: captured graphs keep their addresses
-        else:
-            self._coef = host.to(self._table.device)
+        self._set_schedule(n, timesteps, timesteps_host, rows, device)
+        self._refresh_device("_coef", torch.from_numpy(coef), self._table.device)
         # the history tensors are kept (a captured graph holds their addresses); their stale content is never used:
         # step 0 runs without corrector at order 1, and every later read was written by an earlier step
 
@@ -1069,39 +1034,28 @@ class UniPCMultistepScheduler(_SchedulerBase):
     def graph_buffers(self, sample):
         return (self._coef.data_ptr(),) + tuple(h.data_ptr() for h in self._history(sample))
 
-    def step(self, model_output, timestep, sample, return_dict: bool = True):
-        if self.num_inference_steps is None:
-            raise ValueError("Number of inference steps is 'None', you need to run 'set_timesteps' after creating the "
-                             "scheduler")
-        if self._step_index is None:
-            self._init_step_index(timestep)
-        prev = sample.clone()
+    def _run(self, model_output, sample, cfg=False, guidance=0.0):
+        """The one caller of this class's fused step (da_unipc_flow_step): ``sample`` is updated in place."""
         last, m1, m2 = self._history(sample)
-        ops.unipc_flow_step_(model_output, prev, last, m1, m2, self._coef, self._step_dev)
+        ops.unipc_flow_step_(model_output, sample, last, m1, m2, self._coef, self._step_dev, cfg=cfg, guidance=guidance)
         self._advance()
-        if not return_dict:
-            return (prev,)
-        return SchedulerOutput(prev_sample=prev)
+        return sample
+
+    def step(self, model_output, timestep, sample, return_dict: bool = True):
+        self._require_schedule()
+        self._before_step(timestep)
+        return self._result(self._run(model_output, sample.clone()), return_dict)
 
     def step_cfg(self, model_output_2b, sample, guidance_scale: float, out=None):
         """Engine extension: CFG combine + UniPC step, written over ``sample`` (graph replay)."""
-        if self._step_index is None:
-            self._init_step_index(self.timesteps[0])
+        self._before_step(self.timesteps[0])
         if out is not None and out.data_ptr() != sample.data_ptr():
             raise ValueError("UniPC step_cfg updates `sample` in place")
-        last, m1, m2 = self._history(sample)
-        ops.unipc_flow_step_(model_output_2b, sample, last, m1, m2, self._coef, self._step_dev, cfg=True,
-                             guidance=float(guidance_scale))
-        self._advance()
-        return sample
+        return self._run(model_output_2b, sample, True, float(guidance_scale))
 
     def step_inplace(self, model_output, sample):
-        if self._step_index is None:
-            self._init_step_index(self.timesteps[0])
-        last, m1, m2 = self._history(sample)
-        ops.unipc_flow_step_(model_output, sample, last, m1, m2, self._coef, self._step_dev)
-        self._advance()
-        return sample
+        self._before_step(self.timesteps[0])
+        return self._run(model_output, sample)
 
 
 # ----------------------------------------------------------------------------------------------------------------------
@@ -1135,6 +1089,7 @@ class DPMSolverMultistepScheduler(_SchedulerBase):
                      use_lu_lambdas=False, use_flow_sigmas=False, flow_shift=1.0, final_sigmas_type="zero",
                      lambda_min_clipped=-float("inf"), variance_type=None, timestep_spacing="linspace", steps_offset=0,
                      rescale_betas_zero_snr=False, use_dynamic_shifting=False, time_shift_type="exponential")
+    _bounded_steps = True
 
     def __init__(self, **kwargs):
         super().__init__(**kwargs)
@@ -1179,7 +1134,6 @@ class DPMSolverMultistepScheduler(_SchedulerBase):
         self.alphas = 1.0 - self.betas
         # (the float64 product rounded once: not bit-equal to the fp32 cumprod the other schedulers hold for the same betas)
         self.alphas_cumprod = torch.from_numpy(ac).float()
-        self.init_noise_sigma = 1.0
         ts = np.arange(0, c.num_train_timesteps)[::-1].copy().astype(np.int64)
         self.timesteps = torch.from_numpy(ts)
         self._timesteps_host = ts
@@ -1216,11 +1170,7 @@ class DPMSolverMultistepScheduler(_SchedulerBase):
         last = 0.0 if c.final_sigmas_type == "zero" else float(sig_all[0])
         sig = np.concatenate([sig, [last]]).astype(np.float32)
         self.sigmas = torch.from_numpy(sig)                      # kept on the CPU like the reference
-        self.timesteps = torch.from_numpy(ts).to(device=device, dtype=torch.int64)
-        self._timesteps_host = ts
-        self.num_inference_steps = n
-        self._step_index = None
-        self._begin_index = None
+        self._set_schedule(n, torch.from_numpy(ts).to(device=device, dtype=torch.int64), ts, None, device)
         rows = self._rows(sig, ts)
         self.second_order_rows = [bool(r[6]) for r in rows]
         self._upload(rows, device)
@@ -1263,10 +1213,7 @@ class DPMSolverMultistepScheduler(_SchedulerBase):
 
     def _upload(self, rows, device):
         super()._upload(rows, device)
-        if self._begin_dev is None or self._begin_dev.device != self._table.device:
-            self._begin_dev = torch.zeros((), dtype=torch.int32, device=self._table.device)
-        else:
-            self._begin_dev.zero_()         # in place: captured graphs keep the address
+        self._refresh_device("_begin_dev", torch.zeros((), dtype=torch.int32), self._table.device)
 
     def _sync_device_step(self):
         """reset() and the first step() of a loop come through here: the loop starts at this row."""
@@ -1294,32 +1241,14 @@ class DPMSolverMultistepScheduler(_SchedulerBase):
         return (self._begin_dev.data_ptr(), self.history(sample).data_ptr())
 
     def _add_noise_coeffs(self, timesteps, dtype):
-        """scheduling_dpmsolver_multistep.py add_noise: alpha_t x + sigma_t n of the sigma at ``begin_index`` (img2img: before the
-        first step), at ``step_index`` (after it), or of each timestep's index when no begin index is set; ops in ``dtype``."""
-        sig = self.sigmas.to(dtype=dtype)
-        ts = torch.as_tensor(timesteps).reshape(-1).cpu()
-        if self.begin_index is None:
-            idx = [self.index_for_timestep(t) for t in ts]
-        elif self.step_index is not None:
-            idx = [self.step_index] * ts.shape[0]
-        else:
-            idx = [self.begin_index] * ts.shape[0]
-        s = sig[idx]
+        """scheduling_dpmsolver_multistep.py add_noise: alpha_t x + sigma_t n of the sigma ``_noise_index`` picks; ops in ``dtype``."""
+        s = self.sigmas.to(dtype=dtype)[self._noise_index(timesteps)]
         a = 1 / ((s ** 2 + 1) ** 0.5)
         b = s * a
         return [float(v) for v in a], [float(v) for v in b]
 
-    def _before_step(self, timestep):
-        if self.num_inference_steps is None:
-            raise ValueError("Number of inference steps is 'None', you need to run 'set_timesteps' after creating the "
-                             "scheduler")
-        if self._step_index is None:
-            self._init_step_index(timestep)
-        if not 0 <= self._step_index < self.num_inference_steps:
-            raise IndexError(f"DPMSolverMultistepScheduler: step {self._step_index} of a {self.num_inference_steps}-step "
-                             "schedule (call set_timesteps() or reset() before another loop)")
-
     def _run(self, model_output, sample, cfg, guidance_scale):
+        """The one caller of this class's fused step (da_dpmpp_2m_step): ``sample`` is updated in place."""
         ops.dpmpp_2m_step_(model_output, sample, self.history(sample), self._table, self._step_dev, self._begin_dev, cfg=cfg,
                            guidance=float(guidance_scale), pred_type=self._pred)
         self._advance()
@@ -1328,10 +1257,7 @@ class DPMSolverMultistepScheduler(_SchedulerBase):
     def step(self, model_output, timestep, sample, generator=None, variance_noise=None, return_dict: bool = True):
         """``generator`` / ``variance_noise`` belong to the SDE variants and are unused by dpmsolver++."""
         self._before_step(timestep)
-        prev = self._run(model_output.contiguous(), sample.contiguous().clone(), False, 0.0)
-        if not return_dict:
-            return (prev,)
-        return SchedulerOutput(prev_sample=prev)
+        return self._result(self._run(model_output.contiguous(), sample.contiguous().clone(), False, 0.0), return_dict)
 
     def step_cfg(self, model_output_2b, sample, guidance_scale: float, out=None, cfg: bool = True):
         """Engine extension: CFG combine (``cfg=False``: a plain model output) + the step, written over ``sample`` (graph replay)."""
