@@ -13,6 +13,7 @@ __version__ = "0.1.0"
 
 _EXPORTS = {
     "UNet2DConditionModel": "unet_2d_condition",
+    "ControlNetModel": "controlnet",
     "AutoencoderKL": "autoencoder_kl",
     "AutoencoderKLWan": "autoencoder_kl_wan",
     "FluxTransformer2DModel": "transformer_flux",
@@ -35,6 +36,8 @@ _EXPORTS = {
     "StableDiffusionImg2ImgPipeline": "pipelines",
     "StableDiffusionXLImg2ImgPipeline": "pipelines",
     "StableDiffusionInpaintPipeline": "pipelines",
+    "StableDiffusionControlNetPipeline": "pipelines",
+    "StableDiffusionXLControlNetPipeline": "pipelines",
     "StableDiffusionXLInpaintPipeline": "pipelines",
     "from_reference_config": "config_utils",
     "CLIPTextModel": "text_encoders",

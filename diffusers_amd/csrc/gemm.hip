@@ -83,6 +83,7 @@ int validate(da_gemm_params& p) {
   if (p.residual && (p.ldr & 3)) return DA_ERR_UNSUPPORTED;
   if (p.rowvec && (p.rows_per_batch <= 0 || (p.ld_rowvec & 3))) return DA_ERR_INVALID;
   if (p.gate && (p.rows_per_batch <= 0 || (p.ld_gate & 3))) return DA_ERR_INVALID;
+  if (p.gate_f32 < 0 || p.gate_f32 > 2) return DA_ERR_INVALID;
   if (p.alpha == 0.0f) p.alpha = 1.0f;
   if (p.out_scale == 0.0f) p.out_scale = 1.0f;
   if (p.conv) {
@@ -96,6 +97,7 @@ int validate(da_gemm_params& p) {
       ((p.N & 127) || p.out_f32 || p.residual || p.rowvec || p.gate || p.bias_rows))
     return DA_ERR_UNSUPPORTED;
   if (p.act < 0 || p.act > DA_ACT_GEGLU_TANH) return DA_ERR_INVALID;
+  if (p.gate && p.gate_f32 == 2 && p.conv == 3) return DA_ERR_UNSUPPORTED;   // the rounded fp32 gate: nn.Linear and 1x1 convs
   if (p.split_k < 0 || p.split_k > DA_SPLITK_MAX) return DA_ERR_INVALID;
   if (p.split_k > 1 && (p.stats_out || p.ln_stats)) return DA_ERR_UNSUPPORTED;   // no split-K build of the LayerNorm fold
   if (p.k_valid < 0 || (p.k_valid > 0 && (p.k_valid > (p.conv ? p.C1 : p.K) || (p.conv && p.C2 != 0)))) return DA_ERR_INVALID;
@@ -117,6 +119,9 @@ int stats_parts(const da_gemm_params& p, int tile) {   // one partial per column
 
 bool tile_ok(const da_gemm_params& p, int tile) {
   if (tile <= 0 || tile >= kNumTiles) return false;
+  // gate_f32 == 2 (fp32 gate, product rounded to bf16) lives in the first family's epilogue only: the K2 / K1 / K3 epilogues
+  // read any non-zero gate_f32 as the Wan mode
+  if (p.gate && p.gate_f32 == 2 && (is_k2(tile) || is_k3(tile))) return false;
   if (is_k3(tile)) {  // nn.Linear, plain or GEGLU epilogue, nothing that needs the other families' extra instantiations
     if (p.conv || p.split_k > 1 || p.stats_out || (p.ln_stats && tile != DA_TILE_K3_256x320) || p.vt || p.xa_k) return false;
     if (tile == DA_TILE_K3_256x320)   // the GEGLU projection's tile: whole tiles, aligned output rows (round 6: also as a LayerNorm-fold consumer)

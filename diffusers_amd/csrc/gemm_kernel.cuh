@@ -828,7 +828,12 @@ __global__ __launch_bounds__(64 * WM * WN) void igemm_bf16_kernel(const da_gemm_
             o[e] = xv * bf2f(f2bf(1.0f / (1.0f + __expf(-tv))));
           }
         }
-        if (gate && p.gate_f32) {
+        if (gate && p.gate_f32 == 2) {
+          // ControlNet hand-off: y = zero_conv(h) (bf16) ; y * scale (fp32 scalar, product rounded to bf16) ; out = residual + that
+          const float4 gv = *(const float4*)((const float*)p.gate + (size_t)bidx * p.ld_gate + n);
+          o[0] = bf2f(f2bf(bf2f(f2bf(o[0])) * gv.x)); o[1] = bf2f(f2bf(bf2f(f2bf(o[1])) * gv.y));
+          o[2] = bf2f(f2bf(bf2f(f2bf(o[2])) * gv.z)); o[3] = bf2f(f2bf(bf2f(f2bf(o[3])) * gv.w));
+        } else if (gate && p.gate_f32) {
           // WanTransformerBlock: hidden.float() + Linear(x) (bf16) * gate (fp32), rounded once at the store
           const float4 gv = *(const float4*)((const float*)p.gate + (size_t)bidx * p.ld_gate + n);
           o[0] = bf2f(f2bf(o[0])) * gv.x; o[1] = bf2f(f2bf(o[1])) * gv.y;

@@ -6,8 +6,10 @@ from typing import Optional
 from . import init as dinit
 from .autoencoder_kl import AutoencoderKL
 from .autoencoder_kl_wan import AutoencoderKLWan
-from .pipelines import (DDPMPipeline, FluxImg2ImgPipeline, FluxInpaintPipeline, FluxPipeline, StableDiffusionImg2ImgPipeline, StableDiffusionInpaintPipeline,
-                        StableDiffusionPipeline, StableDiffusionXLImg2ImgPipeline, StableDiffusionXLInpaintPipeline,
+from .controlnet import ControlNetModel
+from .pipelines import (DDPMPipeline, FluxImg2ImgPipeline, FluxInpaintPipeline, FluxPipeline, StableDiffusionControlNetPipeline,
+                        StableDiffusionImg2ImgPipeline, StableDiffusionInpaintPipeline, StableDiffusionPipeline,
+                        StableDiffusionXLControlNetPipeline, StableDiffusionXLImg2ImgPipeline, StableDiffusionXLInpaintPipeline,
                         StableDiffusionXLPipeline, WanPipeline)
 from .schedulers import DDPMScheduler
 from .unet_2d import UNet2DModel
@@ -42,6 +44,23 @@ def build_unet(cfg: dict, seed: int = 0, device="cuda", init_device: Optional[st
     return unet, state_dict
 
 
+def build_controlnet(unet_config: dict, seed: int = 3, device="cuda", init_device: Optional[str] = None, state_dict=None,
+                     zero_convs: bool = False, **config_overrides):
+    """The ControlNet that goes with ``unet_config`` (``ControlNetModel.from_unet``: the U-Net's encoder-side options; pass e.g.
+    ``conditioning_embedding_out_channels=`` to change the rest) with seeded random weights.  A trained-from-scratch ControlNet
+    starts with its zero convs (``controlnet_down_blocks.*``, ``controlnet_mid_block``, the embedding's ``conv_out``) at zero and
+    changes nothing; here they are random like every other weight, so that the model has an effect, unless ``zero_convs``."""
+    cn = ControlNetModel(**dinit.controlnet_config(dict(unet_config), **config_overrides))
+    if state_dict is None:
+        state_dict = dinit.random_state_dict(dinit.controlnet_param_shapes(cn.config), seed=seed, device=init_device or "cpu")
+        if zero_convs:
+            for k, v in state_dict.items():
+                if k.startswith(("controlnet_down_blocks.", "controlnet_mid_block.", "controlnet_cond_embedding.conv_out.")):
+                    v.zero_()
+    cn.load_state_dict(state_dict, device=device)
+    return cn, state_dict
+
+
 def build_vae(cfg: dict, seed: int = 1, device="cuda", init_device: Optional[str] = None, state_dict=None,
               with_encoder: bool = False):
     """``with_encoder``: the encoder half (+ quant_conv) as well, for ``encode`` (random_state_dict seeds per key: the decoder
@@ -71,12 +90,22 @@ def _inpaint_unet_config(ucfg: dict, unet_in_channels: int) -> dict:
     return ucfg if unet_in_channels == ucfg.get("in_channels", 4) else dict(ucfg, in_channels=unet_in_channels)
 
 
+def _controlnet_for(ucfg: dict, tiny: bool, seed: int, device, idev, controlnet):
+    """``controlnet=True``: a seeded ControlNet for the U-Net config; a ControlNetModel is taken as it is."""
+    if controlnet is not True:
+        return controlnet
+    over = {"conditioning_embedding_out_channels": dinit.TINY_SDXL_CONTROLNET["conditioning_embedding_out_channels"]} if tiny else {}
+    return build_controlnet(ucfg, seed=seed + 3, device=device, init_device=idev, **over)[0]
+
+
 def build_sdxl_pipeline(device="cuda", tiny: bool = False, seed: int = 0, init_device: Optional[str] = None,
-                        with_encoder: bool = False, img2img: bool = False, inpaint: bool = False, unet_in_channels: int = 4):
+                        with_encoder: bool = False, img2img: bool = False, inpaint: bool = False, unet_in_channels: int = 4,
+                        controlnet=False):
     """SDXL-base (BASELINE config 3) or its tiny sibling.  Full size: weights are generated on ``init_device``
     (default: the HIP device, ~2.6 B parameters in seconds) and freed after packing.  ``with_encoder``: the VAE's encoder as
     well; ``img2img``: the same components in a StableDiffusionXLImg2ImgPipeline, ``inpaint``: in a
-    StableDiffusionXLInpaintPipeline (both imply ``with_encoder``), whose U-Net takes ``unet_in_channels`` = 4 or 9 input channels."""
+    StableDiffusionXLInpaintPipeline (both imply ``with_encoder``), whose U-Net takes ``unet_in_channels`` = 4 or 9 input channels.
+    ``controlnet``: True (a seeded ControlNet, seed + 3) or a ControlNetModel -- a StableDiffusionXLControlNetPipeline (text-to-image)."""
     ucfg = dinit.TINY_SDXL_UNET if tiny else dinit.SDXL_UNET
     if inpaint:
         ucfg = _inpaint_unet_config(ucfg, unet_in_channels)
@@ -85,12 +114,18 @@ def build_sdxl_pipeline(device="cuda", tiny: bool = False, seed: int = 0, init_d
     unet, _ = build_unet(ucfg, seed=seed, device=device, init_device=idev)
     vae, _ = build_vae(vcfg, seed=seed + 1, device=device, init_device=idev, with_encoder=with_encoder or img2img or inpaint)
     sch = EulerDiscreteScheduler(**SDXL_SCHEDULER)
+    if controlnet:
+        if img2img or inpaint:
+            raise ValueError("controlnet= builds the text-to-image ControlNet pipeline (no ControlNet img2img / inpainting pipeline)")
+        return StableDiffusionXLControlNetPipeline(vae=vae, unet=unet, scheduler=sch,
+                                                   controlnet=_controlnet_for(ucfg, tiny, seed, device, idev, controlnet))
     cls = StableDiffusionXLInpaintPipeline if inpaint else StableDiffusionXLImg2ImgPipeline if img2img else StableDiffusionXLPipeline
     return cls(vae=vae, unet=unet, scheduler=sch)
 
 
 def build_sd15_pipeline(device="cuda", tiny: bool = False, seed: int = 0, init_device: Optional[str] = None,
-                        with_encoder: bool = False, img2img: bool = False, inpaint: bool = False, unet_in_channels: int = 4):
+                        with_encoder: bool = False, img2img: bool = False, inpaint: bool = False, unet_in_channels: int = 4,
+                        controlnet=False):
     ucfg = dinit.TINY_SD15_UNET if tiny else dinit.SD15_UNET
     if inpaint:
         ucfg = _inpaint_unet_config(ucfg, unet_in_channels)
@@ -98,6 +133,11 @@ def build_sd15_pipeline(device="cuda", tiny: bool = False, seed: int = 0, init_d
     idev = init_device or ("cpu" if tiny else str(device))
     unet, _ = build_unet(ucfg, seed=seed, device=device, init_device=idev)
     vae, _ = build_vae(vcfg, seed=seed + 1, device=device, init_device=idev, with_encoder=with_encoder or img2img or inpaint)
+    if controlnet:
+        if img2img or inpaint:
+            raise ValueError("controlnet= builds the text-to-image ControlNet pipeline (no ControlNet img2img / inpainting pipeline)")
+        return StableDiffusionControlNetPipeline(vae=vae, unet=unet, scheduler=DDIMScheduler(**SD15_SCHEDULER),
+                                                 controlnet=_controlnet_for(ucfg, tiny, seed, device, idev, controlnet))
     cls = StableDiffusionInpaintPipeline if inpaint else StableDiffusionImg2ImgPipeline if img2img else StableDiffusionPipeline
     return cls(vae=vae, unet=unet, scheduler=DDIMScheduler(**SD15_SCHEDULER))
 

@@ -59,9 +59,9 @@ def _transformer(sh, p, c, cross, layers, linear_proj):
     sh[f"{p}.proj_out.bias"] = (c,)
 
 
-def unet_param_shapes(cfg) -> "OrderedDict[str, Tuple[int, ...]]":
-    """state_dict inventory of UNet2DConditionModel for the supported configs (SD1.5 / SDXL families)."""
-    sh: "OrderedDict[str, Tuple[int, ...]]" = OrderedDict()
+def _unet_encoder_shapes(sh, cfg) -> None:
+    """conv_in, the time / text_time embeddings, the down blocks and the mid block: the part of the inventory that
+    UNet2DConditionModel and ControlNetModel share, under the same names."""
     boc = tuple(cfg["block_out_channels"])
     n = len(boc)
     temb = boc[0] * 4
@@ -94,6 +94,50 @@ def unet_param_shapes(cfg) -> "OrderedDict[str, Tuple[int, ...]]":
     _resnet(sh, "mid_block.resnets.0", mid, mid, temb)
     _transformer(sh, "mid_block.attentions.0", mid, cross[-1], tlpb[-1], lin)
     _resnet(sh, "mid_block.resnets.1", mid, mid, temb)
+
+
+def controlnet_param_shapes(cfg) -> "OrderedDict[str, Tuple[int, ...]]":
+    """state_dict inventory of ControlNetModel (models/controlnets/controlnet.py): the U-Net's encoder half, the conditioning
+    embedding of the control image (conv_in, pairs of 3x3 convs -- the second of each pair with stride 2 -- and conv_out) and the
+    1x1 "zero convs": one per skip connection, one for the mid block."""
+    sh: "OrderedDict[str, Tuple[int, ...]]" = OrderedDict()
+    _unet_encoder_shapes(sh, cfg)
+    boc = tuple(cfg["block_out_channels"])
+    n = len(boc)
+    lpb = _tup(cfg["layers_per_block"], n)
+    emb = tuple(cfg["conditioning_embedding_out_channels"])
+    e = "controlnet_cond_embedding"
+    sh[f"{e}.conv_in.weight"] = (emb[0], cfg["conditioning_channels"], 3, 3)
+    sh[f"{e}.conv_in.bias"] = (emb[0],)
+    for i in range(len(emb) - 1):
+        sh[f"{e}.blocks.{2 * i}.weight"] = (emb[i], emb[i], 3, 3)
+        sh[f"{e}.blocks.{2 * i}.bias"] = (emb[i],)
+        sh[f"{e}.blocks.{2 * i + 1}.weight"] = (emb[i + 1], emb[i], 3, 3)
+        sh[f"{e}.blocks.{2 * i + 1}.bias"] = (emb[i + 1],)
+    sh[f"{e}.conv_out.weight"] = (boc[0], emb[-1], 3, 3)
+    sh[f"{e}.conv_out.bias"] = (boc[0],)
+    chans = [boc[0]]
+    for i in range(n):
+        chans += [boc[i]] * (lpb[i] + (1 if i != n - 1 else 0))
+    for k, ch in enumerate(chans):
+        sh[f"controlnet_down_blocks.{k}.weight"] = (ch, ch, 1, 1)
+        sh[f"controlnet_down_blocks.{k}.bias"] = (ch,)
+    sh["controlnet_mid_block.weight"] = (boc[-1], boc[-1], 1, 1)
+    sh["controlnet_mid_block.bias"] = (boc[-1],)
+    return sh
+
+
+def unet_param_shapes(cfg) -> "OrderedDict[str, Tuple[int, ...]]":
+    """state_dict inventory of UNet2DConditionModel for the supported configs (SD1.5 / SDXL families)."""
+    sh: "OrderedDict[str, Tuple[int, ...]]" = OrderedDict()
+    _unet_encoder_shapes(sh, cfg)
+    boc = tuple(cfg["block_out_channels"])
+    n = len(boc)
+    temb = boc[0] * 4
+    lpb = _tup(cfg["layers_per_block"], n)
+    tlpb = _tup(cfg["transformer_layers_per_block"], n)
+    cross = _tup(cfg["cross_attention_dim"], n)
+    lin = cfg["use_linear_projection"]
     rboc = tuple(reversed(boc))
     rlpb = tuple(reversed(lpb))
     rcross = tuple(reversed(cross))
@@ -446,10 +490,27 @@ TINY_SDXL_UNET = dict(sample_size=16, in_channels=4, out_channels=4, block_out_c
                       up_block_types=("CrossAttnUpBlock2D", "UpBlock2D"), transformer_layers_per_block=(1, 2),
                       use_linear_projection=True, addition_embed_type="text_time", addition_time_embed_dim=32,
                       projection_class_embeddings_input_dim=256)
+def controlnet_config(unet_cfg: dict, **overrides) -> dict:
+    """The ControlNet config that goes with a U-Net config (``ControlNetModel.from_unet``, controlnet.py:444-497): the U-Net's
+    encoder-side options, the reference's own defaults for the rest."""
+    keys = ("in_channels", "block_out_channels", "layers_per_block", "cross_attention_dim", "attention_head_dim", "down_block_types",
+            "transformer_layers_per_block", "use_linear_projection", "addition_embed_type", "addition_time_embed_dim",
+            "projection_class_embeddings_input_dim", "num_attention_heads", "norm_num_groups", "norm_eps", "flip_sin_to_cos",
+            "freq_shift", "downsample_padding", "mid_block_scale_factor")
+    cfg = {k: unet_cfg[k] for k in keys if k in unet_cfg}
+    cfg.update(overrides)
+    return cfg
+
+
 TINY_SD15_UNET = dict(sample_size=16, in_channels=4, out_channels=4, block_out_channels=(64, 128),
                       layers_per_block=1, cross_attention_dim=64, attention_head_dim=(1, 2),
                       down_block_types=("CrossAttnDownBlock2D", "DownBlock2D"),
                       up_block_types=("UpBlock2D", "CrossAttnUpBlock2D"))
+SDXL_CONTROLNET = controlnet_config(SDXL_UNET)
+SD15_CONTROLNET = controlnet_config(SD15_UNET)
+# the tiny VAE has scale factor 2: one stride-2 stage in the conditioning embedding (32 x 32 control image, 16 x 16 latents)
+TINY_SDXL_CONTROLNET = controlnet_config(TINY_SDXL_UNET, conditioning_embedding_out_channels=(16, 32))
+TINY_SD15_CONTROLNET = controlnet_config(TINY_SD15_UNET, conditioning_embedding_out_channels=(16, 32))
 DDPM_CAT = dict(sample_size=256, in_channels=3, out_channels=3, block_out_channels=(128, 128, 256, 256, 512, 512),
                 layers_per_block=2, down_block_types=("DownBlock2D",) * 4 + ("AttnDownBlock2D", "DownBlock2D"),
                 up_block_types=("UpBlock2D", "AttnUpBlock2D") + ("UpBlock2D",) * 4, attention_head_dim=None,

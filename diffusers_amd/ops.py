@@ -364,6 +364,20 @@ def linear_qkv(x: torch.Tensor, wqkv: torch.Tensor, col0: int, bias: Optional[to
     return qk, vt
 
 
+# an fp32 gate whose product is rounded to bf16 (gate_f32 == 2) exists in the first kernel family only: such a launch leaves the
+# per-shape table alone (its entries may name a K2 / K1 / K3 tile) and lets the library choose among the first family's tiles
+_ROUNDED_GATE_VARIANT = (L.TILE_AUTO, L.STAGE_LDS_DIRECT, 1)
+
+
+def _gate_mode(gate: torch.Tensor, gate_round: bool, what: str) -> int:
+    """da_gemm_params.gate_f32 of a ``gate`` tensor: 0 bf16, 1 fp32 (product kept in fp32), 2 fp32 with ``gate_round``."""
+    if gate.dtype not in (bf16, torch.float32):
+        raise TypeError(f"{what}: gate must be bf16 (Flux rounding) or float32 (Wan rounding; ControlNet rounding with gate_round)")
+    if gate_round and gate.dtype != torch.float32:
+        raise TypeError(f"{what}: gate_round is an option of a float32 gate (a bf16 gate's product is always rounded)")
+    return 2 if gate_round else int(gate.dtype == torch.float32)
+
+
 def linear(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None, *, act: int = L.ACT_NONE,
            residual: Optional[torch.Tensor] = None, rowvec: Optional[torch.Tensor] = None, rows_per_batch: int = 0,
            alpha: float = 1.0, out_scale: float = 1.0, out: Optional[torch.Tensor] = None, out_f32: bool = False,
@@ -371,7 +385,7 @@ def linear(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None
            tile: Optional[int] = None, staging: Optional[int] = None, split_k: Optional[int] = None,
            stats_out: Optional[RowStats] = None, ln: Optional[tuple] = None, k_valid: int = 0,
            prefetch: Optional[torch.Tensor] = None, vt_out: Optional[tuple] = None,
-           xattn: Optional[dict] = None) -> torch.Tensor:
+           xattn: Optional[dict] = None, gate_round: bool = False) -> torch.Tensor:
     """out[M][N] = epilogue(alpha * x[M][K] @ w[N][K]^T).  For act == GEGLU, w/bias are in the packed layout of
     :func:`pack_geglu` and the output has N/2 columns.  ``k_valid`` > 0: columns k >= k_valid of BOTH operands are
     zero padding (da_gemm_params.k_valid): the kernel skips the MFMA steps that would multiply them.
@@ -382,11 +396,16 @@ def linear(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None
 
     ``xattn=dict(k=, vt=, skv=, skv_alloc=, seq=, scale=)`` (da_gemm_params.xa_*): this launch is a cross-attention layer's to_q
     AND its attention -- the result is softmax(scale * q k^T) v for K / V^T of the text embeddings (layers.CrossKV), see
-    :func:`xattn_eligible`."""
+    :func:`xattn_eligible`.
+
+    ``gate`` [M / rows_per_batch][N]: bf16 (the product with the projection is rounded to bf16, Flux) or fp32 (the product stays
+    fp32 until the store, Wan).  ``gate_round=True`` with an fp32 gate (da_gemm_params.gate_f32 == 2) rounds that product to bf16
+    before the residual add -- a bf16 tensor times a Python float, then a bf16 add: the ControlNet hand-off.  First-family tiles
+    only: without a pinned ``tile`` the library picks one of them."""
     p, st = _linear_params(x, w, bias, act=act, residual=residual, rowvec=rowvec, rows_per_batch=rows_per_batch,
                            alpha=alpha, out_scale=out_scale, out=out, out_f32=out_f32, bias_rows=bias_rows, gate=gate,
                            tile=tile, staging=staging, split_k=split_k, stats_out=stats_out, ln=ln, k_valid=k_valid,
-                           prefetch=prefetch, vt_out=vt_out, xattn=xattn)
+                           prefetch=prefetch, vt_out=vt_out, xattn=xattn, gate_round=gate_round)
     if p is None:
         return st     # the skinny-M path ran
     _launch_gemm(p, st, "da_gemm_bf16(linear)")
@@ -430,7 +449,7 @@ def _linear_params(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor
                    gate: Optional[torch.Tensor] = None, tile: Optional[int] = None, staging: Optional[int] = None,
                    split_k: Optional[int] = None, stats_out: Optional[RowStats] = None, ln: Optional[tuple] = None,
                    k_valid: int = 0, prefetch: Optional[torch.Tensor] = None, vt_out: Optional[tuple] = None,
-                   xattn: Optional[dict] = None):
+                   xattn: Optional[dict] = None, gate_round: bool = False):
     """Checks + da_gemm_params of one nn.Linear problem; returns (params, stream), or (None, result) when the skinny-M
     kernel handled it."""
     _req(x, "x"), _req(w, "w")
@@ -465,9 +484,11 @@ def _linear_params(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor
     if prefetch is not None:      # the caller knows better what is met cold next (cross-attention: the layer's K / V^T)
         p.prefetch, p.prefetch_bytes = prefetch.data_ptr(), (prefetch.numel() * prefetch.element_size()) & ~15
     if gate is not None:
-        if gate.dtype not in (bf16, torch.float32):
-            raise TypeError("linear: gate must be bf16 (Flux rounding) or float32 (Wan rounding)")
-        p.gate_f32 = int(gate.dtype == torch.float32)
+        p.gate_f32 = _gate_mode(gate, gate_round, "linear")
+        if p.gate_f32 == 2 and tile is None:
+            tile, staging, split_k = _ROUNDED_GATE_VARIANT
+    elif gate_round:
+        raise ValueError("linear: gate_round needs a gate")
     # out may BE the residual (accumulating launch: one lane reads and writes each element); variant tuning then
     # times its repeated launches on a scratch output
     inplace = residual is not None and out.data_ptr() == residual.data_ptr()
@@ -554,14 +575,17 @@ def conv2d_nhwc(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] =
                 rowvec: Optional[torch.Tensor] = None, residual: Optional[torch.Tensor] = None,
                 out_scale: float = 1.0, act: int = L.ACT_NONE, tile: Optional[int] = None,
                 staging: Optional[int] = None, pad_after: int = 0, out: Optional[torch.Tensor] = None,
-                split_k: Optional[int] = None, k_valid: int = 0) -> torch.Tensor:
+                split_k: Optional[int] = None, k_valid: int = 0, gate: Optional[torch.Tensor] = None,
+                gate_round: bool = False) -> torch.Tensor:
     """Implicit-GEMM Conv2d on channels-last tensors.  x: [B][H][W][C1] (x2: [B][H][W][C2] = fused channel concat),
     w: [Cout][k][k][C1+C2] flattened to [Cout][k*k*(C1+C2)].  up=True fuses a nearest 2x upsample of the input.
     rowvec [B][Cout] is added per batch (time embedding); residual is [B][Hout][Wout][Cout].  ``out`` (contiguous
     [B][Hout][Wout][Cout]) may be the SAME tensor as ``residual``: every output element is read and written by one
     lane, which is how the temporal taps of a causal Conv3d accumulate in place (autoencoder_kl_wan.py).
     ``k_valid`` > 0 (single source only): channels >= k_valid of x AND of every tap of w are zero padding up to the 64-wide
-    K granule; the kernel skips the MFMA steps that would multiply them (da_gemm_params.k_valid)."""
+    K granule; the kernel skips the MFMA steps that would multiply them (da_gemm_params.k_valid).
+    ``gate`` [B][Cout] (bf16 or fp32) multiplies the bf16-rounded conv output per batch before the residual add, with the rounding
+    modes of :func:`linear` (``gate_round``: 1x1 convs only)."""
     _req(x, "x"), _req(w, "w")
     if x2 is not None:
         _req(x2, "x2")
@@ -585,6 +609,19 @@ def conv2d_nhwc(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] =
         _req(rowvec, "rowvec")
         p.ld_rowvec = _rows2d(rowvec, "rowvec")
         p.rows_per_batch = Hout * Wout
+    if gate is not None:
+        _req(gate, "gate", None)
+        if gate.dim() != 2 or tuple(gate.shape) != (B, Cout):
+            raise ValueError(f"conv2d_nhwc: gate must be [B][Cout] = {(B, Cout)}, got {tuple(gate.shape)}")
+        p.gate, p.ld_gate, p.rows_per_batch = gate.data_ptr(), _rows2d(gate, "gate"), Hout * Wout
+        p.gate_f32 = _gate_mode(gate, gate_round, "conv2d_nhwc")
+        if p.gate_f32 == 2:
+            if ksize != 1:
+                raise ValueError("conv2d_nhwc: gate_round is built for 1x1 convs")
+            if tile is None:
+                tile, staging, split_k = _ROUNDED_GATE_VARIANT
+    elif gate_round:
+        raise ValueError("conv2d_nhwc: gate_round needs a gate")
     p.alpha, p.out_scale, p.act, p.out_f32 = 1.0, out_scale, act, 0
     C1, C2 = p.C1, p.C2
     if not 0 <= k_valid <= C1 or (k_valid and C2):

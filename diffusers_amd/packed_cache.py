@@ -28,6 +28,7 @@ FORMAT = "diffusers_amd.packed/1"
 # class name -> parameter inventory of its reference state_dict (what the meta skeleton is built from)
 _SHAPES: Dict[str, Callable] = {
     "UNet2DConditionModel": dinit.unet_param_shapes,
+    "ControlNetModel": dinit.controlnet_param_shapes,
     "AutoencoderKL": dinit.vae_decoder_param_shapes,
     "AutoencoderKLWan": dinit.wan_vae_decoder_param_shapes,
     "FluxTransformer2DModel": dinit.flux_param_shapes,

@@ -37,6 +37,10 @@ def _engine_class(name: str):
 
 
 class PipelineLoadingMixin:
+    # other pipeline classes whose directories this class loads as well: a ControlNet pipeline is put together from a base
+    # checkpoint's directory and a ``controlnet=`` handed in (the reference's own recipe)
+    _accepts_directory_of = ()
+
     @classmethod
     def from_pretrained(cls, pretrained_model_name_or_path, torch_dtype=None, variant: Optional[str] = None, device="cuda",
                         text_encoders: str = "transformers", cache_packed: bool = True, **passed):
@@ -53,7 +57,7 @@ class PipelineLoadingMixin:
             raise FileNotFoundError(f"{root}: no {MODEL_INDEX} (a local pipeline directory is needed; there is no hub access here)")
         index = json.loads((root / MODEL_INDEX).read_text())
         want = index.get("_class_name")
-        if want and want != cls.__name__:
+        if want and want != cls.__name__ and want not in getattr(cls, "_accepts_directory_of", ()):
             raise ValueError(f"{root} holds a {want}; load it with diffusers_amd.{want}" if _engine_class(want) is not None else
                              f"{root} holds a {want}, which this engine does not implement")
         params = inspect.signature(cls.__init__).parameters

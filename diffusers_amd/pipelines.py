@@ -211,7 +211,7 @@ def _pf(pipe) -> "ops.WeightPrefetch":
     """The pipeline's weight-prefetch trace (ops.weight_prefetch): recorded by one eager step, applied to every later one."""
     pf = getattr(pipe, "_weight_prefetch", None)
     if pf is None:
-        pf = pipe._weight_prefetch = ops.WeightPrefetch(owner=pipe, slots=("unet", "transformer"))
+        pf = pipe._weight_prefetch = ops.WeightPrefetch(owner=pipe, slots=("unet", "transformer", "controlnet"))
     return pf
 
 
@@ -368,15 +368,18 @@ class _LatentDiffusionBase(_StepCallbacks, _CapturedStepLoop, PipelineLoadingMix
         pass
 
     # ---- the captured step -------------------------------------------------------------------------------------
-    def _predict_noise(self, latents, cond, do_cfg):
-        """scale_model_input + CFG batch doubling + the U-Net forward of one step."""
+    def _model_input(self, latents, do_cfg):
+        """scale_model_input + CFG batch doubling: what the denoiser (and a ControlNet next to it) reads in one step."""
         sch = self.scheduler
         rep = 2 if do_cfg else 1
         if sch.scales_model_input:
-            x_in = sch.scale_model_input(latents, sch.timesteps[0], rep=rep)
-        else:
-            x_in = ops.mul_scalar(latents, 1.0, rep=rep) if rep > 1 else latents  # DDIM, DPM-Solver++: scale_model_input = identity
-        return self.unet(x_in, None, None, conditioning=cond, sampler_table=sch.device_table,
+            return sch.scale_model_input(latents, sch.timesteps[0], rep=rep)
+        return ops.mul_scalar(latents, 1.0, rep=rep) if rep > 1 else latents  # DDIM, DPM-Solver++: scale_model_input = identity
+
+    def _predict_noise(self, latents, cond, do_cfg):
+        """scale_model_input + CFG batch doubling + the U-Net forward of one step."""
+        sch = self.scheduler
+        return self.unet(self._model_input(latents, do_cfg), None, None, conditioning=cond, sampler_table=sch.device_table,
                          step_idx=sch.device_step, return_dict=False)[0]
 
     def _step(self, latents, cond, guidance_scale, do_cfg):
@@ -567,10 +570,13 @@ class StableDiffusionXLPipeline(_LatentDiffusionBase):
                              "`negative_pooled_prompt_embeds`")
         return pe, npe, te, nte
 
-    def _conditioning(self, prompt_embeds, negative_prompt_embeds, pooled_prompt_embeds, negative_pooled_prompt_embeds, ids, neg_ids,
-                      do_cfg):
-        """The step's conditioning: embeddings and added time ids (one row each: txt2img passes the same ``ids`` twice) on the
-        device, per sample, the negative half in front with CFG."""
+    def _conditioning(self, *inputs):
+        return self.unet.precompute_conditioning(*self._conditioning_inputs(*inputs))
+
+    def _conditioning_inputs(self, prompt_embeds, negative_prompt_embeds, pooled_prompt_embeds, negative_pooled_prompt_embeds, ids,
+                             neg_ids, do_cfg):
+        """The step's conditioning as ``precompute_conditioning`` takes it: embeddings and added time ids (one row each: txt2img
+        passes the same ``ids`` twice) on the device, per sample, the negative half in front with CFG."""
         dev = self.device
         pe = prompt_embeds.to(device=dev, dtype=bf16)
         te = pooled_prompt_embeds.to(device=dev, dtype=bf16)
@@ -580,7 +586,7 @@ class StableDiffusionXLPipeline(_LatentDiffusionBase):
             pe = torch.cat([negative_prompt_embeds.to(device=dev, dtype=bf16), pe], dim=0)
             te = torch.cat([negative_pooled_prompt_embeds.to(device=dev, dtype=bf16), te], dim=0)
             ids = torch.cat([neg_ids.to(dev).repeat(batch, 1), ids], dim=0)
-        return self.unet.precompute_conditioning(pe.contiguous(), {"text_embeds": te, "time_ids": ids})
+        return pe.contiguous(), {"text_embeds": te, "time_ids": ids}
 
     def _takes_custom_schedule(self) -> bool:
         """(whatever else the scheduler is, its own ``set_timesteps`` answers)"""
@@ -650,11 +656,14 @@ class StableDiffusionPipeline(_LatentDiffusionBase):
             raise ValueError("classifier-free guidance needs `negative_prompt_embeds`")
         return pe, npe
 
-    def _conditioning(self, prompt_embeds, negative_prompt_embeds, do_cfg):
+    def _conditioning(self, *inputs):
+        return self.unet.precompute_conditioning(*self._conditioning_inputs(*inputs))
+
+    def _conditioning_inputs(self, prompt_embeds, negative_prompt_embeds, do_cfg):
         pe = prompt_embeds.to(device=self.device, dtype=bf16)
         if do_cfg:
             pe = torch.cat([negative_prompt_embeds.to(device=self.device, dtype=bf16), pe], dim=0)
-        return self.unet.precompute_conditioning(pe.contiguous(), None)
+        return pe.contiguous(), None
 
     @torch.no_grad()
     def __call__(self, prompt=None, height: Optional[int] = None, width: Optional[int] = None,
@@ -1236,6 +1245,194 @@ class StableDiffusionXLInpaintPipeline(_InpaintMixin, StableDiffusionXLImg2ImgPi
                                 guidance_rescale, original_size, crops_coords_top_left, target_size, negative_original_size,
                                 negative_crops_coords_top_left, negative_target_size, aesthetic_score, negative_aesthetic_score,
                                 clip_skip, callback_on_step_end, callback_on_step_end_tensor_inputs, use_graph)
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# ControlNet (pipelines/controlnet/pipeline_controlnet.py, pipeline_controlnet_sd_xl.py)
+# ----------------------------------------------------------------------------------------------------------------------
+def prepare_control_image(image, vae_scale_factor: int, device):
+    """The control image as ``ControlNetModel.precompute_conditioning`` reads it: ``(tensor, nchw)``.  VaeImageProcessor.preprocess
+    with ``do_normalize=False`` (pipeline_controlnet.py:232-234): pixels stay in [0, 1].  A torch tensor is NCHW (or CHW) in [0, 1];
+    a numpy array is NHWC / HWC (float in [0, 1], or uint8 read as x / 255 like a PIL image); a PIL image is taken via numpy.  The
+    engine does not resize: sides that are not a multiple of the VAE's scale factor are refused.  One image or one batch -- a list
+    (of images, or of images per ControlNet) is refused."""
+    if isinstance(image, (list, tuple)):
+        raise NotImplementedError("`image` as a list (several control images, or one per ControlNet of a MultiControlNetModel) is not "
+                                  "supported: pass one image, or a batch as one tensor / array")
+    if image is None:
+        raise ValueError("`image` (the control image) is required")
+    if not torch.is_tensor(image) and not isinstance(image, np.ndarray):
+        if hasattr(image, "convert"):                       # PIL.Image
+            image = np.asarray(_pil_rgb(image))
+        else:
+            raise ValueError(f"`image` has to be of type `torch.Tensor`, `np.ndarray` or `PIL.Image.Image`, but is {type(image)}")
+    if torch.is_tensor(image):
+        t = image if image.dim() == 4 else image.unsqueeze(0)
+        if t.dim() != 4 or t.shape[1] != 3:
+            raise ValueError(f"`image` tensor must be NCHW or CHW with 3 channels, got shape {tuple(image.shape)}")
+        H, W_, nchw = t.shape[2], t.shape[3], True
+        t = t.to(device=device, dtype=torch.float32).contiguous()
+    else:
+        a = image if image.ndim == 4 else image[None]
+        if a.ndim != 4 or a.shape[-1] != 3:
+            raise ValueError(f"`image` array must be NHWC / HWC with 3 channels, got shape {tuple(image.shape)}")
+        if a.dtype != np.uint8:
+            a = a.astype(np.float32)
+        H, W_, nchw = a.shape[1], a.shape[2], False
+        t = torch.from_numpy(np.ascontiguousarray(a)).to(device)
+    if H % vae_scale_factor or W_ % vae_scale_factor:
+        raise ValueError(f"`image` is {H} x {W_}: height and width must be multiples of the VAE scale factor {vae_scale_factor} "
+                         "(the engine does not resize images)")
+    return t, nchw
+
+
+def control_image_batch(image: torch.Tensor, batch: int, num_images_per_prompt: int, do_cfg: bool) -> torch.Tensor:
+    """prepare_image's batching (pipeline_controlnet.py:820-850): one image serves every sample, else each image is repeated
+    ``num_images_per_prompt`` times in place (``repeat_interleave``); with CFG the whole batch is then doubled."""
+    n = image.shape[0]
+    if n == 1:
+        image = image.repeat_interleave(batch, dim=0)
+    elif n * num_images_per_prompt == batch:
+        image = image.repeat_interleave(num_images_per_prompt, dim=0)
+    else:
+        raise ValueError(f"`image` holds {n} control images for {batch} samples (prompts x num_images_per_prompt "
+                         f"{num_images_per_prompt}): pass one image, or one per prompt")
+    return torch.cat([image] * 2, 0).contiguous() if do_cfg else image.contiguous()
+
+
+class _ControlNetMixin:
+    """The ControlNet pipelines on top of the text-to-image ones: every step runs ``controlnet.features`` on the U-Net's own
+    (scaled, CFG-doubled) input, and the U-Net forward takes the zero convs as its ``controlnet_handoff`` -- launches of the
+    engine only, so the step captures into a HIP graph or a strict launch plan like the base pipelines' steps.  Once per call:
+    the ControlNet's own cross-attention K / V^T and text_time embedding, and the conditioning embedding of the control image.
+    Not built (refused by name): several ControlNets, ``guess_mode``, a ``control_guidance_start`` / ``control_guidance_end``
+    window, image resizing."""
+
+    _cn_call = None      # (image, nchw, scale, num_images_per_prompt) of the call in progress
+    _cn_static = None    # static inputs of the captured step that outlive a call: the image embedding, the scale vector
+
+    def _set_controlnet(self, controlnet):
+        if isinstance(controlnet, (list, tuple)) or type(controlnet).__name__ == "MultiControlNetModel":
+            raise NotImplementedError("several ControlNets (MultiControlNetModel) are not supported: pass one ControlNetModel")
+        if controlnet is None:
+            raise ValueError(f"{type(self).__name__} needs its `controlnet` component")
+        self.controlnet = controlnet
+        cc, uc = controlnet.config, self.unet.config
+        for k in ("block_out_channels", "down_block_types", "layers_per_block", "in_channels"):
+            a, b = cc[k], uc[k]
+            if (tuple(a) if isinstance(a, (list, tuple)) else a) != (tuple(b) if isinstance(b, (list, tuple)) else b):
+                raise ValueError(f"the ControlNet's `{k}` = {a} does not match the U-Net's {b}: its residuals would not fit")
+        if self.vae is not None and controlnet.conditioning_scale_factor != self.vae_scale_factor:
+            raise ValueError(f"the ControlNet's conditioning embedding downsamples {controlnet.conditioning_scale_factor} x, the VAE "
+                             f"{self.vae_scale_factor} x: control image and latents would not line up")
+
+    def _arm_controlnet(self, image, height, width, controlnet_conditioning_scale, guess_mode, control_guidance_start,
+                        control_guidance_end, num_images_per_prompt):
+        """Checks and stores the ControlNet arguments of a call; returns the call's ``(height, width)`` -- the control image's,
+        which is not resized."""
+        if guess_mode:
+            raise NotImplementedError("`guess_mode=True` is not supported")
+        if isinstance(control_guidance_start, (list, tuple)) or isinstance(control_guidance_end, (list, tuple)) \
+                or float(control_guidance_start) != 0.0 or float(control_guidance_end) != 1.0:
+            raise NotImplementedError("`control_guidance_start` / `control_guidance_end` other than 0.0 / 1.0 are not supported (the "
+                                      "ControlNet runs in every step)")
+        if isinstance(controlnet_conditioning_scale, (list, tuple)) or torch.is_tensor(controlnet_conditioning_scale):
+            raise NotImplementedError("`controlnet_conditioning_scale` is one float (several ControlNets are not supported)")
+        t, nchw = prepare_control_image(image, self.vae_scale_factor, self.device)
+        H, W_ = (t.shape[2], t.shape[3]) if nchw else (t.shape[1], t.shape[2])
+        if (height is not None and height != H) or (width is not None and width != W_):
+            raise ValueError(f"`image` is {H} x {W_} but height x width = {height} x {width} was asked for (the engine does not "
+                             "resize images)")
+        self._cn_call = (t, nchw, float(controlnet_conditioning_scale), int(num_images_per_prompt))
+        return H, W_
+
+    def _conditioning(self, *inputs):
+        pe, added = self._conditioning_inputs(*inputs)
+        cond = self.unet.precompute_conditioning(pe, added)
+        image, nchw, scale, nipp = self._cn_call
+        do_cfg = bool(inputs[-1])
+        image = control_image_batch(image, pe.shape[0] // (2 if do_cfg else 1), nipp, do_cfg)
+        cn = self.controlnet.precompute_conditioning(pe, added, image=image, image_nchw=nchw, conditioning_scale=scale)
+        # what the captured step reads by address and the key names: kept over calls, refreshed in place while the shapes hold
+        st = self._cn_static = _adopt_or_refresh(self._cn_static, {"embed": cn["embed"], "gate": cn["gate"]})
+        cn["embed"], cn["gate"], cn["scale"] = st["embed"], st["gate"], scale
+        cond["controlnet"] = cn
+        return cond
+
+    def _predict_noise(self, latents, cond, do_cfg):
+        sch, cn = self.scheduler, cond["controlnet"]
+        x_in = self._model_input(latents, do_cfg)
+        feats = self.controlnet.features(x_in, cn, sampler_table=sch.device_table, step_idx=sch.device_step)
+        return self.unet(x_in, None, None, conditioning=cond, sampler_table=sch.device_table, step_idx=sch.device_step,
+                         controlnet_handoff=self.controlnet.handoff(feats, cn["gate"]), return_dict=False)[0]
+
+    def _make_graph_key(self, latents, cond, guidance_scale, do_cfg):
+        cn = cond["controlnet"]
+        return super()._make_graph_key(latents, cond, guidance_scale, do_cfg) + (
+            "controlnet", _weights_token(self.controlnet), cn["embed"].data_ptr(), tuple(cn["embed"].shape), cn["gate"].data_ptr(),
+            tuple(cn["gate"].shape), float(cn["scale"]))
+
+    def _refresh_static(self, captured, new):
+        super()._refresh_static(captured, new)
+        old, cn = captured[0]["controlnet"], new[0]["controlnet"]
+        for kv_old, kv_new in zip(old["kvs"], cn["kvs"]):
+            for a, b in zip(kv_old, kv_new):
+                a.k.copy_(b.k)
+                a.vt.copy_(b.vt)
+        if old["aug_emb"] is not None:
+            old["aug_emb"].copy_(cn["aug_emb"])
+        # (embed / gate are the pipeline's own static buffers: `_conditioning` refreshed them in place already)
+        for k in ("embed", "gate"):
+            if old[k].data_ptr() != cn[k].data_ptr():
+                old[k].copy_(cn[k])
+
+
+class StableDiffusionControlNetPipeline(_ControlNetMixin, StableDiffusionPipeline):
+    """pipeline_controlnet.py: SD1.5 text-to-image guided by one ControlNet (see _ControlNetMixin).  ``image`` is the control
+    image, pixels in [0, 1]; the result has its size."""
+
+    _accepts_directory_of = ("StableDiffusionPipeline",)
+
+    def __init__(self, vae, unet, scheduler, controlnet=None, text_encoder=None, tokenizer=None, safety_checker=None,
+                 feature_extractor=None, requires_safety_checker: bool = False):
+        super().__init__(vae, unet, scheduler, text_encoder, tokenizer, safety_checker, feature_extractor, requires_safety_checker)
+        self._set_controlnet(controlnet)
+
+    @torch.no_grad()
+    def __call__(self, prompt=None, image=None, height: Optional[int] = None, width: Optional[int] = None,
+                 controlnet_conditioning_scale: float = 1.0, guess_mode: bool = False, control_guidance_start: float = 0.0,
+                 control_guidance_end: float = 1.0, num_images_per_prompt: int = 1, **kwargs):
+        """``StableDiffusionPipeline.__call__`` plus the control image and its scale; every other argument passes through."""
+        height, width = self._arm_controlnet(image, height, width, controlnet_conditioning_scale, guess_mode, control_guidance_start,
+                                             control_guidance_end, num_images_per_prompt)
+        try:
+            return super().__call__(prompt, height=height, width=width, num_images_per_prompt=num_images_per_prompt, **kwargs)
+        finally:
+            self._cn_call = None
+
+
+class StableDiffusionXLControlNetPipeline(_ControlNetMixin, StableDiffusionXLPipeline):
+    """pipeline_controlnet_sd_xl.py: SDXL text-to-image guided by one ControlNet (see _ControlNetMixin)."""
+
+    _accepts_directory_of = ("StableDiffusionXLPipeline",)
+
+    def __init__(self, vae, unet, scheduler, controlnet=None, text_encoder=None, text_encoder_2=None, tokenizer=None,
+                 tokenizer_2=None, force_zeros_for_empty_prompt: bool = True):
+        super().__init__(vae, unet, scheduler, text_encoder, text_encoder_2, tokenizer, tokenizer_2, force_zeros_for_empty_prompt)
+        self._set_controlnet(controlnet)
+
+    @torch.no_grad()
+    def __call__(self, prompt=None, prompt_2=None, image=None, height: Optional[int] = None, width: Optional[int] = None,
+                 controlnet_conditioning_scale: float = 1.0, guess_mode: bool = False, control_guidance_start: float = 0.0,
+                 control_guidance_end: float = 1.0, num_images_per_prompt: int = 1, **kwargs):
+        """``StableDiffusionXLPipeline.__call__`` plus the control image and its scale; every other argument passes through."""
+        height, width = self._arm_controlnet(image, height, width, controlnet_conditioning_scale, guess_mode, control_guidance_start,
+                                             control_guidance_end, num_images_per_prompt)
+        try:
+            return super().__call__(prompt, height=height, width=width, prompt_2=prompt_2, num_images_per_prompt=num_images_per_prompt,
+                                    **kwargs)
+        finally:
+            self._cn_call = None
 
 
 def calculate_shift(image_seq_len, base_seq_len: int = 256, max_seq_len: int = 4096, base_shift: float = 0.5,

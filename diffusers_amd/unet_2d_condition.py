@@ -15,8 +15,9 @@ import torch
 from . import ops
 from .config_utils import check_to
 from .loading import PretrainedMixin
-from .layers import (Downsample2D, GroupNorm, ResnetBlock2D, TimeProjections, TimestepEmbedding, Transformer2DModel,
-                     Upsample2D, Weights, encoder_mask_bias, pad_encoder_states)
+from .layers import (GroupNorm, ResnetBlock2D, TimeProjections, TimestepEmbedding, Transformer2DModel, Upsample2D, Weights,
+                     encoder_mask_bias, pad_encoder_states)
+from .unet_blocks import build_down_blocks, build_mid_block, walk_down, walk_mid
 
 bf16 = torch.bfloat16
 
@@ -126,23 +127,8 @@ class UNet2DConditionModel(PretrainedMixin):
         self.time_embedding = TimestepEmbedding(w, "time_embedding")
         self.add_embedding = TimestepEmbedding(w, "add_embedding") if c.addition_embed_type == "text_time" else None
 
-        self.down = []
-        for i, btype in enumerate(c.down_block_types):
-            pre = f"down_blocks.{i}"
-            stage = {"resnets": [], "attns": [], "down": None}
-            for j in range(lpb[i]):
-                stage["resnets"].append(ResnetBlock2D(w, f"{pre}.resnets.{j}", groups, eps))
-                if btype == "CrossAttnDownBlock2D":
-                    stage["attns"].append(Transformer2DModel(w, f"{pre}.attentions.{j}", heads[i], tlpb[i], groups))
-            if i != n - 1:
-                stage["down"] = Downsample2D(w, f"{pre}.downsamplers.0", padding=c.downsample_padding)
-            self.down.append(stage)
-
-        self.mid = {
-            "resnets": [ResnetBlock2D(w, "mid_block.resnets.0", groups, eps, c.mid_block_scale_factor),
-                        ResnetBlock2D(w, "mid_block.resnets.1", groups, eps, c.mid_block_scale_factor)],
-            "attns": [Transformer2DModel(w, "mid_block.attentions.0", heads[-1], tlpb[-1], groups)],
-        }
+        self.down = build_down_blocks(w, c)
+        self.mid = build_mid_block(w, c)
 
         rheads = tuple(reversed(heads))
         rlpb = tuple(reversed(lpb))
@@ -276,7 +262,7 @@ class UNet2DConditionModel(PretrainedMixin):
                 down_block_additional_residuals=None, mid_block_additional_residual=None,
                 down_intrablock_additional_residuals=None, encoder_attention_mask=None, return_dict: bool = True,
                 conditioning: Optional[Dict[str, Any]] = None, sampler_table=None, step_idx=None, inpaint_cond=None,
-                scale_model_input: bool = False):
+                scale_model_input: bool = False, controlnet_handoff=None):
         """Same signature as the reference forward (unet_2d_condition.py:979-994) plus engine extensions:
         ``conditioning`` (result of :meth:`precompute_conditioning`), ``sampler_table``/``step_idx`` (read the
         timestep from the device-resident sampler table so the call is HIP-graph replayable) and, for a 9-channel inpainting
@@ -284,7 +270,10 @@ class UNet2DConditionModel(PretrainedMixin):
         its nine input channels from the three tensors (ops.conv_in_inpaint; the CFG halves are stored from one computation, their
         count taken from the conditioning batch).  ``scale_model_input`` (with ``inpaint_cond`` and ``sampler_table``) applies the
         Euler scheduler's ``scale_model_input`` to the latents inside that conv.  Without ``inpaint_cond`` a 9-channel ``sample``
-        goes through the ordinary conv_in.
+        goes through the ordinary conv_in.  ``controlnet_handoff``: a callable ``f(skips, mid)`` that adds a ControlNet's residuals
+        with the engine's own launches (``ControlNetModel.handoff_``): called once, after the mid block, with the channels-last skip
+        list of the down blocks and the mid block's output, it updates those tensors IN PLACE -- no torch op, so the step stays
+        recordable as a strict launch plan.  Not together with the two reference residual arguments.
 
         Handled like the reference: ``encoder_attention_mask`` (key-padding mask of the text tokens, :1071-1073, through the
         masked flash kernel), ``down_block_additional_residuals`` / ``mid_block_additional_residual`` (ControlNet, :1178-1222:
@@ -307,6 +296,9 @@ class UNet2DConditionModel(PretrainedMixin):
         if (down_block_additional_residuals is None) != (mid_block_additional_residual is None):
             raise ValueError("ControlNet residuals: pass both down_block_additional_residuals and "
                              "mid_block_additional_residual (unet_2d_condition.py:1104)")
+        if controlnet_handoff is not None and down_block_additional_residuals is not None:
+            raise ValueError("`controlnet_handoff` and down_block_additional_residuals / mid_block_additional_residual are two "
+                             "ways to add the same residuals: pass one")
         ops.require_hip(sample, "sample")
         c = self.config
         B, Cin, H, W_ = sample.shape
@@ -357,18 +349,7 @@ class UNet2DConditionModel(PretrainedMixin):
             x = ops.conv_thin_in(sample.contiguous(), self.conv_in_w, self.conv_in_b, ksize=3, in_nchw=True)
 
         # 3. down
-        ki = 0
-        skips = [x]
-        for st in self.down:
-            for j, rn in enumerate(st["resnets"]):
-                x = rn(x, emb)
-                if st["attns"]:
-                    x = st["attns"][j](x, kvs[ki])
-                    ki += 1
-                skips.append(x)
-            if st["down"] is not None:
-                x = st["down"](x)
-                skips.append(x)
+        x, skips, ki = walk_down(self.down, x, emb, kvs)
 
         if down_block_additional_residuals is not None:
             # ControlNet (:1191-1200): one residual per skip connection, NCHW like every reference activation; the sum is a
@@ -379,12 +360,13 @@ class UNet2DConditionModel(PretrainedMixin):
             skips = [s_ + self._nhwc(r, s_) for s_, r in zip(skips, down_block_additional_residuals)]
 
         # 4. mid
-        x = self.mid["resnets"][0](x, emb)
-        x = self.mid["attns"][0](x, kvs[ki])
-        ki += 1
-        x = self.mid["resnets"][1](x, emb)
+        x, ki = walk_mid(self.mid, x, emb, kvs, ki)
         if mid_block_additional_residual is not None:
             x = x + self._nhwc(mid_block_additional_residual, x)             # :1220-1222
+        if controlnet_handoff is not None:
+            # after the mid block, not in front of it: the last skip IS the mid block's input, which the reference leaves without
+            # a residual (:1191-1200 build new tensors for the skip list only)
+            controlnet_handoff(skips, x)
 
         # 5. up (skip concat fused into the resnets)
         for st in self.up:

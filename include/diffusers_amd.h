@@ -169,7 +169,12 @@ typedef struct da_gemm_params {
   int tile;    /* DA_TILE_* */
   int staging; /* DA_STAGE_* */
   int gate_f32; /* 1: gate is float and out = residual + bf16(xW+b) * gate in fp32, rounded once
-                   (WanTransformerBlock, transformer_wan.py:491,:502); 0: Flux rounding (gate product rounded to bf16) */
+                   (WanTransformerBlock, transformer_wan.py:491,:502); 0: Flux rounding (gate product rounded to bf16);
+                   2: gate is float and the PRODUCT is rounded to bf16 before the residual add,
+                   out = residual + bf16(bf16(xW+b) * gate) -- a bf16 tensor times a Python float, then a bf16 add (the ControlNet
+                   hand-off, controlnet.py: `sample * conditioning_scale`, then unet_2d_condition.py:1191-1222).  conv == 0 / 1 on
+                   the first-family tiles (DA_TILE_128x128 .. DA_TILE_128x128_W8) only: DA_TILE_AUTO picks one of them, an
+                   explicit K2 / K1 / K3 tile or conv == 3 returns DA_ERR_UNSUPPORTED.  Any other value: DA_ERR_INVALID */
   int split_k;  /* 0 / 1: every tile is computed by one block.  2..DA_SPLITK_MAX (24): the K range of each tile is dealt to
                    split_k co-resident blocks that hand fp32 partial tiles over through `workspace` (in-launch reduction,
                    fixed summation order: deterministic, but the last fp32 bit of a sum differs from split_k = 1).  For
