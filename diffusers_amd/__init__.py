@@ -31,6 +31,7 @@ _EXPORTS = {
     "UniPCMultistepScheduler": "schedulers",
     "DPMSolverMultistepScheduler": "schedulers",
     "EulerAncestralDiscreteScheduler": "schedulers",
+    "LCMScheduler": "schedulers",
     "StableDiffusionPipeline": "pipelines",
     "StableDiffusionXLPipeline": "pipelines",
     "StableDiffusionImg2ImgPipeline": "pipelines",

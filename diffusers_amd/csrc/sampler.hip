@@ -177,6 +177,40 @@ __global__ void x0_linear_step_kernel(const T* __restrict__ eps, const T* __rest
   }
 }
 
+// Latent-consistency (LCM) step, schedulers/scheduling_lcm.py step():
+//   row = [sqrt(1 - abar_t), sqrt(abar_t), c_out, c_skip, sqrt(abar_prev), sqrt(1 - abar_prev), clip_range(0=off), timestep]
+//   x0       as x0_linear_step_kernel (epsilon / v_prediction / sample), clamped when clip > 0
+//   denoised = c_out * x0 + c_skip * x
+//   prev     = sqrt(abar_prev) * denoised + sqrt(1 - abar_prev) * noise       each product / sum rounded in the tensor dtype
+// The last step of a schedule has slots 4, 5 = 1, 0: prev = denoised, and the noise row is not read.
+template <typename T, bool CFG, int PRED>
+__global__ void lcm_step_kernel(const T* __restrict__ eps, const T* __restrict__ x, const T* __restrict__ noise,
+                                T* __restrict__ out, const float* __restrict__ table, const int* __restrict__ step_idx,
+                                float g, size_t n, size_t noise_step_stride) {
+  const float* row = table + (size_t)(*step_idx) * 8;
+  noise += (size_t)(*step_idx) * noise_step_stride;
+  const float cb = row[0], ca = row[1], c_out = row[2], c_skip = row[3], pa = row[4], pb = row[5], clip = row[6];
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+    const float e = load_eps<T, CFG>(eps, i, n, g);
+    const float s = IO<T>::ld(x, i);
+    float x0;
+    if (PRED == 0) {
+      x0 = IO<T>::rnd(__fmul_rn(cb, e));
+      x0 = IO<T>::rnd(__fsub_rn(s, x0));
+      x0 = IO<T>::rnd(__fdiv_rn(x0, ca));
+    } else if (PRED == 1) {
+      x0 = IO<T>::rnd(__fsub_rn(IO<T>::rnd(__fmul_rn(ca, s)), IO<T>::rnd(__fmul_rn(cb, e))));
+    } else {
+      x0 = e;
+    }
+    if (clip > 0.f) x0 = fminf(fmaxf(x0, -clip), clip);
+    float acc = IO<T>::rnd(__fadd_rn(IO<T>::rnd(__fmul_rn(c_out, x0)), IO<T>::rnd(__fmul_rn(c_skip, s))));
+    if (pb != 0.f)
+      acc = IO<T>::rnd(__fadd_rn(IO<T>::rnd(__fmul_rn(pa, acc)), IO<T>::rnd(__fmul_rn(pb, IO<T>::ld(noise, i)))));
+    IO<T>::st(out, i, acc);
+  }
+}
+
 // FlowMatch Euler: row = [sigma, sigma_next, dt, -, -, -, -, timestep]; prev = float(x) + (dt * v in model dtype), stored in
 // the MODEL OUTPUT's dtype (scheduling_flow_match_euler_discrete.py:484,:517: sample.to(float32) ... .to(model_output.dtype)).
 // TX = dtype of the sample, TV = dtype of the model output and of `out` (TX = float, TV = bf16 is what the reference's
@@ -535,14 +569,20 @@ extern "C" int da_x0_linear_step(const void* eps, const void* x, const void* noi
                                  void* out, const float* table, const int* step_idx, int cfg, float guidance,
                                  long long n_, int dtype, int pred_type, void* stream) {
   if (!eps || !x || !out || !table || !step_idx || n_ <= 0 || noise_step_stride < 0) return DA_ERR_INVALID;
-  if (pred_type < 0 || pred_type > 2) return DA_ERR_INVALID;
+  // bit 2 (DA_PRED_LCM) selects the consistency update; the low bits stay the prediction type
+  const bool lcm = (pred_type & 4) != 0;
+  const int pred = pred_type & 3;
+  if (pred_type < 0 || pred_type > 6 || pred > 2) return DA_ERR_INVALID;
+  if (lcm && !noise) return DA_ERR_INVALID;
   const size_t n = (size_t)n_;
   hipStream_t s = (hipStream_t)stream;
-#define DA_XL(T, C, P)                                                                                              \
-  DA_LAUNCH((x0_linear_step_kernel<T, C, P>), ew_grid(n), dim3(256), 0, s, (const T*)eps, (const T*)x, (const T*)noise, \
-            (T*)out, table, step_idx, guidance, n, (size_t)noise_step_stride)
+#define DA_XL_K(K, T, C, P)                                                                                         \
+  DA_LAUNCH((K<T, C, P>), ew_grid(n), dim3(256), 0, s, (const T*)eps, (const T*)x, (const T*)noise, (T*)out, table, \
+            step_idx, guidance, n, (size_t)noise_step_stride)
+#define DA_XL(T, C, P) \
+  do { if (lcm) DA_XL_K(lcm_step_kernel, T, C, P); else DA_XL_K(x0_linear_step_kernel, T, C, P); } while (0)
 #define DA_XL_P(T, C) \
-  do { if (pred_type == 0) DA_XL(T, C, 0); else if (pred_type == 1) DA_XL(T, C, 1); else DA_XL(T, C, 2); } while (0)
+  do { if (pred == 0) DA_XL(T, C, 0); else if (pred == 1) DA_XL(T, C, 1); else DA_XL(T, C, 2); } while (0)
   if (dtype == DA_DTYPE_BF16) {
     if (cfg) DA_XL_P(uint16_t, true); else DA_XL_P(uint16_t, false);
   } else if (dtype == DA_DTYPE_F32) {
@@ -552,6 +592,7 @@ extern "C" int da_x0_linear_step(const void* eps, const void* x, const void* noi
   }
 #undef DA_XL_P
 #undef DA_XL
+#undef DA_XL_K
   DA_CHECK_LAUNCH();
   return DA_OK;
 }

@@ -14,7 +14,7 @@ from .pipelines import (DDPMPipeline, FluxImg2ImgPipeline, FluxInpaintPipeline, 
 from .schedulers import DDPMScheduler
 from .unet_2d import UNet2DModel
 from .transformer_wan import WanTransformer3DModel
-from .schedulers import DDIMScheduler, EulerDiscreteScheduler, FlowMatchEulerDiscreteScheduler
+from .schedulers import DDIMScheduler, EulerDiscreteScheduler, FlowMatchEulerDiscreteScheduler, LCMScheduler
 from .transformer_flux import FluxTransformer2DModel
 from .unet_2d_condition import UNet2DConditionModel
 
@@ -33,6 +33,19 @@ SDXL_EULER_A_SCHEDULER = dict(beta_start=0.00085, beta_end=0.012, beta_schedule=
                               timestep_spacing="leading")
 SD15_EULER_A_SCHEDULER = dict(beta_start=0.00085, beta_end=0.012, beta_schedule="scaled_linear", steps_offset=1,
                               timestep_spacing="leading")
+# latent-consistency sampling (LCM-LoRA fused into the checkpoint, or a distilled LCM U-Net) on the same betas:
+# LCMScheduler(**LCM_SCHEDULER), 2-8 steps
+LCM_SCHEDULER = dict(beta_start=0.00085, beta_end=0.012, beta_schedule="scaled_linear", original_inference_steps=50,
+                     timestep_scaling=10.0)
+
+
+def _scheduler_for(scheduler: Optional[str], default):
+    """``scheduler=None``: the pipeline's usual one (``default()``); ``"lcm"``: LCMScheduler."""
+    if scheduler is None:
+        return default()
+    if scheduler == "lcm":
+        return LCMScheduler(**LCM_SCHEDULER)
+    raise ValueError("scheduler must be None (the pipeline's default) or 'lcm'")
 
 
 def build_unet(cfg: dict, seed: int = 0, device="cuda", init_device: Optional[str] = None, state_dict=None):
@@ -100,20 +113,24 @@ def _controlnet_for(ucfg: dict, tiny: bool, seed: int, device, idev, controlnet)
 
 def build_sdxl_pipeline(device="cuda", tiny: bool = False, seed: int = 0, init_device: Optional[str] = None,
                         with_encoder: bool = False, img2img: bool = False, inpaint: bool = False, unet_in_channels: int = 4,
-                        controlnet=False):
+                        controlnet=False, scheduler: Optional[str] = None, time_cond_proj_dim: Optional[int] = None):
     """SDXL-base (BASELINE config 3) or its tiny sibling.  Full size: weights are generated on ``init_device``
     (default: the HIP device, ~2.6 B parameters in seconds) and freed after packing.  ``with_encoder``: the VAE's encoder as
     well; ``img2img``: the same components in a StableDiffusionXLImg2ImgPipeline, ``inpaint``: in a
     StableDiffusionXLInpaintPipeline (both imply ``with_encoder``), whose U-Net takes ``unet_in_channels`` = 4 or 9 input channels.
-    ``controlnet``: True (a seeded ControlNet, seed + 3) or a ControlNetModel -- a StableDiffusionXLControlNetPipeline (text-to-image)."""
+    ``controlnet``: True (a seeded ControlNet, seed + 3) or a ControlNetModel -- a StableDiffusionXLControlNetPipeline (text-to-image).
+    ``scheduler="lcm"``: LCMScheduler instead of Euler; ``time_cond_proj_dim``: a U-Net with the guidance-scale embedding input of the
+    distilled LCM checkpoints (``time_embedding.cond_proj``)."""
     ucfg = dinit.TINY_SDXL_UNET if tiny else dinit.SDXL_UNET
+    if time_cond_proj_dim is not None:
+        ucfg = dict(ucfg, time_cond_proj_dim=int(time_cond_proj_dim))
     if inpaint:
         ucfg = _inpaint_unet_config(ucfg, unet_in_channels)
     vcfg = dinit.TINY_VAE if tiny else dinit.SDXL_VAE
     idev = init_device or ("cpu" if tiny else str(device))
     unet, _ = build_unet(ucfg, seed=seed, device=device, init_device=idev)
     vae, _ = build_vae(vcfg, seed=seed + 1, device=device, init_device=idev, with_encoder=with_encoder or img2img or inpaint)
-    sch = EulerDiscreteScheduler(**SDXL_SCHEDULER)
+    sch = _scheduler_for(scheduler, lambda: EulerDiscreteScheduler(**SDXL_SCHEDULER))
     if controlnet:
         if img2img or inpaint:
             raise ValueError("controlnet= builds the text-to-image ControlNet pipeline (no ControlNet img2img / inpainting pipeline)")
@@ -125,21 +142,25 @@ def build_sdxl_pipeline(device="cuda", tiny: bool = False, seed: int = 0, init_d
 
 def build_sd15_pipeline(device="cuda", tiny: bool = False, seed: int = 0, init_device: Optional[str] = None,
                         with_encoder: bool = False, img2img: bool = False, inpaint: bool = False, unet_in_channels: int = 4,
-                        controlnet=False):
+                        controlnet=False, scheduler: Optional[str] = None, time_cond_proj_dim: Optional[int] = None):
+    """SD1.5 or its tiny sibling, as ``build_sdxl_pipeline`` (DDIM by default)."""
     ucfg = dinit.TINY_SD15_UNET if tiny else dinit.SD15_UNET
+    if time_cond_proj_dim is not None:
+        ucfg = dict(ucfg, time_cond_proj_dim=int(time_cond_proj_dim))
     if inpaint:
         ucfg = _inpaint_unet_config(ucfg, unet_in_channels)
     vcfg = dinit.TINY_VAE if tiny else dinit.SD_VAE
     idev = init_device or ("cpu" if tiny else str(device))
     unet, _ = build_unet(ucfg, seed=seed, device=device, init_device=idev)
     vae, _ = build_vae(vcfg, seed=seed + 1, device=device, init_device=idev, with_encoder=with_encoder or img2img or inpaint)
+    sch = _scheduler_for(scheduler, lambda: DDIMScheduler(**SD15_SCHEDULER))
     if controlnet:
         if img2img or inpaint:
             raise ValueError("controlnet= builds the text-to-image ControlNet pipeline (no ControlNet img2img / inpainting pipeline)")
-        return StableDiffusionControlNetPipeline(vae=vae, unet=unet, scheduler=DDIMScheduler(**SD15_SCHEDULER),
+        return StableDiffusionControlNetPipeline(vae=vae, unet=unet, scheduler=sch,
                                                  controlnet=_controlnet_for(ucfg, tiny, seed, device, idev, controlnet))
     cls = StableDiffusionInpaintPipeline if inpaint else StableDiffusionImg2ImgPipeline if img2img else StableDiffusionPipeline
-    return cls(vae=vae, unet=unet, scheduler=DDIMScheduler(**SD15_SCHEDULER))
+    return cls(vae=vae, unet=unet, scheduler=sch)
 
 
 def build_flux_transformer(cfg: dict, seed: int = 5, device="cuda", init_device: Optional[str] = None, state_dict=None):

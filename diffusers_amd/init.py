@@ -132,6 +132,8 @@ def unet_param_shapes(cfg) -> "OrderedDict[str, Tuple[int, ...]]":
     sh: "OrderedDict[str, Tuple[int, ...]]" = OrderedDict()
     _unet_encoder_shapes(sh, cfg)
     boc = tuple(cfg["block_out_channels"])
+    if cfg.get("time_cond_proj_dim") is not None:      # the distilled LCM checkpoints' guidance-scale embedding input (bias-free)
+        sh["time_embedding.cond_proj.weight"] = (boc[0], cfg["time_cond_proj_dim"])
     n = len(boc)
     temb = boc[0] * 4
     lpb = _tup(cfg["layers_per_block"], n)

@@ -998,7 +998,14 @@ def x0_linear_step(eps: torch.Tensor, x: torch.Tensor, noise: Optional[torch.Ten
                    step_idx: torch.Tensor, *, cfg: bool, guidance: float,
                    out: Optional[torch.Tensor] = None, noise_step_stride: int = 0,
                    pred_type: int = L.PRED_EPSILON) -> torch.Tensor:
+    """DDIM / DDPM update, or -- ``pred_type = L.PRED_LCM + L.PRED_*`` -- the latent-consistency update (see da_x0_linear_step),
+    + the CFG combine when ``cfg``.  The consistency update needs ``noise``; ``out`` may be the sample (in place)."""
     _check_sampler("x0_linear_step", x, eps, out, cfg)
+    pred_type = int(pred_type)
+    if pred_type not in (0, 1, 2, L.PRED_LCM, L.PRED_LCM + 1, L.PRED_LCM + 2):
+        raise ValueError(f"x0_linear_step: pred_type {pred_type} is none of 0-2 (DDIM / DDPM) and 4-6 (consistency update)")
+    if pred_type & L.PRED_LCM and noise is None:
+        raise ValueError("x0_linear_step: the consistency update (pred_type 4-6) needs `noise`")
     if out is None:
         out = torch.empty_like(x)
     elif out.dtype != x.dtype:

@@ -25,7 +25,7 @@ from . import ops
 from .autoencoder_kl import AutoencoderKL
 from .pipeline_loading import PipelineLoadingMixin
 from .schedulers import (DDPMScheduler, DPMSolverMultistepScheduler, EulerAncestralDiscreteScheduler,
-                         EulerDiscreteScheduler, FlowMatchEulerDiscreteScheduler, UniPCMultistepScheduler)
+                         EulerDiscreteScheduler, FlowMatchEulerDiscreteScheduler, LCMScheduler, UniPCMultistepScheduler)
 from .transformer_flux import FluxTransformer2DModel
 from .transformer_wan import WanTransformer3DModel
 from .unet_2d import UNet2DModel
@@ -151,6 +151,29 @@ def _check_latents_batch(latents, batch: int):
     a captured step of another size)"""
     if latents.shape[0] != batch:
         raise ValueError(f"`latents` holds {latents.shape[0]} samples, the prompt embeddings (x num_images_per_prompt) {batch}")
+
+
+def get_guidance_scale_embedding(w: torch.Tensor, embedding_dim: int = 512, dtype: torch.dtype = torch.float32) -> torch.Tensor:
+    """The guidance-scale embedding a U-Net with ``time_cond_proj_dim`` takes as ``timestep_cond`` (the pipelines'
+    ``get_guidance_scale_embedding``, pipeline_stable_diffusion_xl.py:789-816; from the VDM sinusoidal embedding): ``w`` [n] ->
+    [n][embedding_dim], sines then cosines of ``1000 w`` at ``embedding_dim // 2`` log-spaced frequencies, zero-padded when odd."""
+    if w.dim() != 1:
+        raise ValueError("get_guidance_scale_embedding: `w` must be one-dimensional")
+    w = w * 1000.0
+    half_dim = embedding_dim // 2
+    emb = torch.log(torch.tensor(10000.0)) / (half_dim - 1)
+    emb = torch.exp(torch.arange(half_dim, dtype=dtype) * -emb)
+    emb = w.to(dtype)[:, None] * emb[None, :]
+    emb = torch.cat([torch.sin(emb), torch.cos(emb)], dim=1)
+    if embedding_dim % 2 == 1:
+        emb = torch.nn.functional.pad(emb, (0, 1))
+    return emb
+
+
+def _time_cond_dim(unet) -> Optional[int]:
+    """``unet.config.time_cond_proj_dim``: set for the distilled LCM U-Nets, which take the guidance scale as an embedding."""
+    cfg = getattr(unet, "config", None)
+    return cfg.get("time_cond_proj_dim") if hasattr(cfg, "get") else getattr(cfg, "time_cond_proj_dim", None)
 
 
 def _capture_step(pipe, step, mode):
@@ -359,6 +382,7 @@ class _LatentDiffusionBase(_StepCallbacks, _CapturedStepLoop, PipelineLoadingMix
         self._noise_table = None   # [num_inference_steps, *latents.shape]: DDIM eta > 0, or a stochastic sampler (_draw_step_noise)
         self._noise_buffer = None  # the table's storage, kept over the calls that need none (_fill_noise_table)
         self._guidance_rescale = 0.0   # > 0: rescale_noise_cfg after the CFG combine (pipeline_stable_diffusion.py:69-92)
+        self._guidance_scale = 1.0     # the call's: a U-Net with time_cond_proj_dim reads its embedding (_timestep_cond)
 
     @property
     def device(self):
@@ -406,8 +430,12 @@ class _LatentDiffusionBase(_StepCallbacks, _CapturedStepLoop, PipelineLoadingMix
         which is where the reference's loop would start consuming the generator -- into rows ``begin ... begin + n_steps - 1``
         of a ``[num_inference_steps, *latents.shape]`` table in the latents' dtype (= the model output's); the fused step picks its
         row with the device step counter, so it stays graph-replayable (``_fill_noise_table``)."""
-        if getattr(self.scheduler, "needs_step_noise", False):
-            self._fill_noise_table(latents, generator, num_inference_steps, n_steps, begin)
+        sch = self.scheduler
+        if getattr(sch, "needs_step_noise", False):
+            # (a scheduler may say how many of the steps draw: LCM's last step of a schedule adds no noise, and the reference's loop
+            # leaves the generator there)
+            draws = sch.step_noise_draws(begin, n_steps) if hasattr(sch, "step_noise_draws") else n_steps
+            self._fill_noise_table(latents, generator, num_inference_steps, draws, begin)
         elif self._eta == 0.0:
             self._noise_table = None
 
@@ -431,7 +459,10 @@ class _LatentDiffusionBase(_StepCallbacks, _CapturedStepLoop, PipelineLoadingMix
         # address (reading `device_table` first would rebuild it in place for eta = 0, and a replayed graph would then run
         # deterministic DDIM whatever eta the caller passed).  A no-op for every other scheduler.
         sch.ensure_table(self._eta)
-        return (tuple(latents.shape), float(guidance_scale), bool(do_cfg), cond["kvs"][0][0].skv if cond["kvs"] else 0,
+        # (a U-Net with time_cond_proj_dim never combines: the guidance scale reaches the step through the static `timestep_cond`
+        # buffer, which `_refresh_static` rewrites, not by value)
+        by_value = float(guidance_scale) if cond.get("timestep_cond") is None else 0.0
+        return (tuple(latents.shape), by_value, bool(do_cfg), cond["kvs"][0][0].skv if cond["kvs"] else 0,
                 self._noise_table.data_ptr() if self._noise_table is not None else 0, float(self._eta),
                 float(self._guidance_rescale)) + _key_tail(sch, self.unet, latents)
 
@@ -443,6 +474,8 @@ class _LatentDiffusionBase(_StepCallbacks, _CapturedStepLoop, PipelineLoadingMix
                 a.vt.copy_(b.vt)
         if old["aug_emb"] is not None:
             old["aug_emb"].copy_(cond["aug_emb"])
+        if old.get("timestep_cond") is not None:
+            old["timestep_cond"].copy_(cond["timestep_cond"])
 
     def _decode(self, latents, output_type):
         if output_type == "latent":
@@ -460,15 +493,43 @@ class _LatentDiffusionBase(_StepCallbacks, _CapturedStepLoop, PipelineLoadingMix
         """What every call sets before anything reads it; returns ``do_cfg``."""
         self._guidance_rescale = float(guidance_rescale)    # pipeline_stable_diffusion_xl.py:849, :1227-1229
         self._arm_callback(callback_on_step_end, callback_on_step_end_tensor_inputs)
-        return guidance_scale > 1.0
+        self._guidance_scale = float(guidance_scale)
+        # pipeline_stable_diffusion_xl.py:831-832: a U-Net that takes the guidance scale as an embedding runs without the CFG batch
+        return guidance_scale > 1.0 and _time_cond_dim(self.unet) is None
+
+    def _timestep_cond(self, batch: int) -> Optional[torch.Tensor]:
+        """pipeline_stable_diffusion_xl.py:1188-1193: the embedding of ``guidance_scale - 1``, one row per sample, bf16 -- for a
+        U-Net with ``time_cond_proj_dim``; None otherwise."""
+        dim = _time_cond_dim(self.unet)
+        if dim is None:
+            return None
+        w = torch.tensor(self._guidance_scale - 1).repeat(batch)
+        return get_guidance_scale_embedding(w, embedding_dim=dim).to(device=self.device, dtype=bf16)
+
+    def _unet_conditioning(self, pe, added):
+        tc = self._timestep_cond(pe.shape[0])
+        return self.unet.precompute_conditioning(pe, added, **({} if tc is None else {"timestep_cond": tc}))
 
     def _takes_custom_schedule(self) -> bool:
-        return isinstance(self.scheduler, EulerDiscreteScheduler)
+        return isinstance(self.scheduler, (EulerDiscreteScheduler, LCMScheduler))
+
+    _original_inference_steps = None   # a call's ``original_inference_steps=``: LCMScheduler.set_timesteps takes it
 
     def _set_schedule(self, num_inference_steps, timesteps, sigmas):
         """retrieve_timesteps (pipeline_stable_diffusion_xl.py:144-167): a custom timestep / sigma schedule replaces the step count,
         for a scheduler whose ``set_timesteps`` takes one."""
         custom = {k: v for k, v in (("timesteps", timesteps), ("sigmas", sigmas)) if v is not None}
+        orig, self._original_inference_steps = self._original_inference_steps, None
+        if orig is not None:
+            if not isinstance(self.scheduler, LCMScheduler):
+                raise ValueError(f"`original_inference_steps` is an LCMScheduler option; the current scheduler is "
+                                 f"{type(self.scheduler)}")
+            custom["original_inference_steps"] = orig
+            if timesteps is None:
+                custom["num_inference_steps"] = num_inference_steps
+        if sigmas is not None and isinstance(self.scheduler, LCMScheduler):
+            raise ValueError(f"The current scheduler class {type(self.scheduler)}'s `set_timesteps` does not support custom sigmas "
+                             "schedules. Please check whether you are using the correct scheduler.")
         if not custom:
             self.scheduler.set_timesteps(num_inference_steps, device=self.device)
         elif not self._takes_custom_schedule():
@@ -571,7 +632,7 @@ class StableDiffusionXLPipeline(_LatentDiffusionBase):
         return pe, npe, te, nte
 
     def _conditioning(self, *inputs):
-        return self.unet.precompute_conditioning(*self._conditioning_inputs(*inputs))
+        return self._unet_conditioning(*self._conditioning_inputs(*inputs))
 
     def _conditioning_inputs(self, prompt_embeds, negative_prompt_embeds, pooled_prompt_embeds, negative_pooled_prompt_embeds, ids,
                              neg_ids, do_cfg):
@@ -606,7 +667,9 @@ class StableDiffusionXLPipeline(_LatentDiffusionBase):
                  target_size: Optional[Tuple[int, int]] = None, generator=None, use_graph: bool = True,
                  prompt_2=None, negative_prompt=None, negative_prompt_2=None, num_images_per_prompt: int = 1,
                  clip_skip=None, guidance_rescale: float = 0.0, callback_on_step_end=None,
-                 callback_on_step_end_tensor_inputs=None, timesteps=None, sigmas=None, denoising_end: Optional[float] = None):
+                 callback_on_step_end_tensor_inputs=None, timesteps=None, sigmas=None, denoising_end: Optional[float] = None,
+                 original_inference_steps: Optional[int] = None):
+        self._original_inference_steps = original_inference_steps
         do_cfg = self._arm(guidance_scale, guidance_rescale, callback_on_step_end, callback_on_step_end_tensor_inputs)
         embeds = self._prompt_inputs(prompt, prompt_2, negative_prompt, negative_prompt_2, num_images_per_prompt, prompt_embeds,
                                      negative_prompt_embeds, pooled_prompt_embeds, negative_pooled_prompt_embeds, clip_skip, do_cfg)
@@ -657,7 +720,7 @@ class StableDiffusionPipeline(_LatentDiffusionBase):
         return pe, npe
 
     def _conditioning(self, *inputs):
-        return self.unet.precompute_conditioning(*self._conditioning_inputs(*inputs))
+        return self._unet_conditioning(*self._conditioning_inputs(*inputs))
 
     def _conditioning_inputs(self, prompt_embeds, negative_prompt_embeds, do_cfg):
         pe = prompt_embeds.to(device=self.device, dtype=bf16)
@@ -942,7 +1005,9 @@ class StableDiffusionXLImg2ImgPipeline(_Img2ImgMixin, StableDiffusionXLPipeline)
                  target_size: Optional[Tuple[int, int]] = None, negative_original_size: Optional[Tuple[int, int]] = None,
                  negative_crops_coords_top_left: Tuple[int, int] = (0, 0), negative_target_size: Optional[Tuple[int, int]] = None,
                  aesthetic_score: float = 6.0, negative_aesthetic_score: float = 2.5, clip_skip=None,
-                 callback_on_step_end=None, callback_on_step_end_tensor_inputs=None, use_graph: bool = True):
+                 callback_on_step_end=None, callback_on_step_end_tensor_inputs=None, use_graph: bool = True,
+                 original_inference_steps: Optional[int] = None):
+        self._original_inference_steps = original_inference_steps
         return self._image_call(prompt, prompt_2, image, None, None, None, None, None, strength, num_inference_steps, timesteps,
                                 sigmas, denoising_start, denoising_end, guidance_scale, negative_prompt, negative_prompt_2,
                                 num_images_per_prompt, eta, generator, latents, prompt_embeds, negative_prompt_embeds,
@@ -978,7 +1043,8 @@ class StableDiffusionImg2ImgPipeline(_Img2ImgMixin, StableDiffusionPipeline):
                  sigmas=None, guidance_scale: float = 7.5, negative_prompt=None, num_images_per_prompt: int = 1,
                  eta: float = 0.0, generator=None, prompt_embeds=None, negative_prompt_embeds=None, output_type: str = "pt",
                  return_dict: bool = True, clip_skip=None, guidance_rescale: float = 0.0, callback_on_step_end=None,
-                 callback_on_step_end_tensor_inputs=None, use_graph: bool = True):
+                 callback_on_step_end_tensor_inputs=None, use_graph: bool = True, original_inference_steps: Optional[int] = None):
+        self._original_inference_steps = original_inference_steps
         return self._image_call(prompt, image, None, None, None, None, None, strength, num_inference_steps, timesteps, sigmas,
                                 guidance_scale, negative_prompt, num_images_per_prompt, eta, generator, None, prompt_embeds,
                                 negative_prompt_embeds, output_type, return_dict, clip_skip, guidance_rescale, callback_on_step_end,
@@ -1209,8 +1275,9 @@ class StableDiffusionInpaintPipeline(_InpaintMixin, StableDiffusionImg2ImgPipeli
                  eta: float = 0.0, generator=None, latents: Optional[torch.Tensor] = None, prompt_embeds=None,
                  negative_prompt_embeds=None, ip_adapter_image=None, ip_adapter_image_embeds=None, output_type: str = "pt",
                  return_dict: bool = True, clip_skip=None, guidance_rescale: float = 0.0, callback_on_step_end=None,
-                 callback_on_step_end_tensor_inputs=None, use_graph: bool = True):
+                 callback_on_step_end_tensor_inputs=None, use_graph: bool = True, original_inference_steps: Optional[int] = None):
         self._check_inpaint_inputs(image, ip_adapter_image, ip_adapter_image_embeds)
+        self._original_inference_steps = original_inference_steps
         return self._image_call(prompt, image, mask_image, masked_image_latents, height, width, padding_mask_crop, strength,
                                 num_inference_steps, timesteps, sigmas, guidance_scale, negative_prompt, num_images_per_prompt, eta,
                                 generator, latents, prompt_embeds, negative_prompt_embeds, output_type, return_dict, clip_skip,
@@ -1236,8 +1303,9 @@ class StableDiffusionXLInpaintPipeline(_InpaintMixin, StableDiffusionXLImg2ImgPi
                  negative_original_size: Optional[Tuple[int, int]] = None, negative_crops_coords_top_left: Tuple[int, int] = (0, 0),
                  negative_target_size: Optional[Tuple[int, int]] = None, aesthetic_score: float = 6.0,
                  negative_aesthetic_score: float = 2.5, clip_skip=None, callback_on_step_end=None,
-                 callback_on_step_end_tensor_inputs=None, use_graph: bool = True):
+                 callback_on_step_end_tensor_inputs=None, use_graph: bool = True, original_inference_steps: Optional[int] = None):
         self._check_inpaint_inputs(image, ip_adapter_image, ip_adapter_image_embeds)
+        self._original_inference_steps = original_inference_steps
         return self._image_call(prompt, prompt_2, image, mask_image, masked_image_latents, height, width, padding_mask_crop, strength,
                                 num_inference_steps, timesteps, sigmas, denoising_start, denoising_end, guidance_scale,
                                 negative_prompt, negative_prompt_2, num_images_per_prompt, eta, generator, latents, prompt_embeds,
@@ -1348,7 +1416,7 @@ class _ControlNetMixin:
 
     def _conditioning(self, *inputs):
         pe, added = self._conditioning_inputs(*inputs)
-        cond = self.unet.precompute_conditioning(pe, added)
+        cond = self._unet_conditioning(pe, added)
         image, nchw, scale, nipp = self._cn_call
         do_cfg = bool(inputs[-1])
         image = control_image_batch(image, pe.shape[0] // (2 if do_cfg else 1), nipp, do_cfg)

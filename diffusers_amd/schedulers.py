@@ -8,6 +8,7 @@ Host side (schedule construction) is numpy / torch-CPU scalar math written to fo
   DDPMScheduler                   schedulers/scheduling_ddpm.py:348-416, :461-567
   FlowMatchEulerDiscreteScheduler schedulers/scheduling_flow_match_euler_discrete.py:283-382, :423-523
   DPMSolverMultistepScheduler     schedulers/scheduling_dpmsolver_multistep.py (dpmsolver++, order <= 2; float64 host scalars)
+  LCMScheduler                    schedulers/scheduling_lcm.py (latent-consistency sampling; per-step noise, pre-drawn)
 Per-step scalars are evaluated once with fp32 torch scalar ops (same ops, same order as the reference evaluates them
 every step) and stored in a device table of 8 floats per step; a device-resident step counter selects the row, so a
 denoising step is HIP-graph replayable.  ``step_cfg`` additionally fuses the classifier-free-guidance combine.
@@ -812,6 +813,157 @@ class DDPMScheduler(_AlphaBarBase):
             self._sync_device_step()
         self._run(model_output, sample, noise_table, sample.numel(), False, 0.0, out=sample)
         return sample
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+@dataclass
+class LCMSchedulerOutput:
+    prev_sample: torch.Tensor
+    denoised: Optional[torch.Tensor] = None
+
+
+def _lcm_rows(alphas_cumprod: torch.Tensor, ts, timestep_scaling: float, clip: float) -> np.ndarray:
+    """[sqrt(1 - abar_t), sqrt(abar_t), c_out, c_skip, sqrt(abar_prev), sqrt(1 - abar_prev), clip_range, timestep] per step, every
+    scalar a 0-d fp32 torch tensor formed in the order ``LCMScheduler.step`` and ``get_scalings_for_boundary_condition_discrete``
+    form it (sigma_data = 0.5).  The last step returns ``denoised``: slots 4, 5 = 1, 0."""
+    n = len(ts)
+    rows = np.zeros((n, 8), dtype=np.float32)
+    for i in range(n):
+        t = int(ts[i])
+        a_t = alphas_cumprod[t]
+        b_t = 1 - a_t
+        scaled = torch.tensor(t) * timestep_scaling          # int64 0-d tensor x Python float -> fp32
+        c_skip = 0.5 ** 2 / (scaled ** 2 + 0.5 ** 2)
+        c_out = scaled / (scaled ** 2 + 0.5 ** 2) ** 0.5
+        rows[i, 0] = float(b_t ** 0.5)
+        rows[i, 1] = float(a_t ** 0.5)
+        rows[i, 2] = float(c_out)
+        rows[i, 3] = float(c_skip)
+        if i + 1 < n:
+            a_prev = alphas_cumprod[int(ts[i + 1])]
+            rows[i, 4] = float(a_prev ** 0.5)
+            rows[i, 5] = float((1 - a_prev) ** 0.5)
+        else:
+            rows[i, 4], rows[i, 5] = 1.0, 0.0
+        rows[i, 6] = clip
+        rows[i, 7] = float(t)
+    return rows
+
+
+class LCMScheduler(_AlphaBarBase):
+    """schedulers/scheduling_lcm.py: multistep latent-consistency sampling (Luo et al., "Latent Consistency Models"), 1-8 steps.
+    A step predicts x0, applies the consistency boundary condition ``denoised = c_out x0 + c_skip x`` and, on every step but the
+    schedule's last, re-noises ``denoised`` to the next timestep with fresh noise.  ONE kernel per step (da_x0_linear_step with
+    ``pred_type = PRED_LCM + prediction type``) does the CFG combine and the update with the reference's rounding points.
+    ``step()`` draws its noise as the reference does; ``step_cfg`` (the pipelines' captured step) reads row ``device_step`` of a
+    pre-drawn ``noise_table`` [steps][numel].  The device table holds the ``n`` step rows and, behind them, the same ``n`` rows with
+    slots 4, 5 = 1, 0: the eager ``step()`` reads ``denoised`` for its output from those with a second launch."""
+
+    _defaults = dict(num_train_timesteps=1000, beta_start=0.00085, beta_end=0.012, beta_schedule="scaled_linear",
+                     trained_betas=None, original_inference_steps=50, clip_sample=False, clip_sample_range=1.0,
+                     set_alpha_to_one=True, steps_offset=0, prediction_type="epsilon", thresholding=False,
+                     dynamic_thresholding_ratio=0.995, sample_max_value=1.0, timestep_spacing="leading",
+                     timestep_scaling=10.0, rescale_betas_zero_snr=False)
+    needs_step_noise = True
+    _bounded_steps = True
+
+    def __init__(self, **kwargs):
+        super().__init__(**kwargs)
+        c = self.config
+        if c.thresholding or c.rescale_betas_zero_snr:
+            raise NotImplementedError("LCMScheduler: dynamic thresholding / zero-SNR rescaling are not on the hot path")
+        if c.prediction_type not in L.PRED_TYPES:
+            raise ValueError(f"prediction_type given as {c.prediction_type} must be one of `epsilon`, `sample` or "
+                             "`v_prediction` for `LCMScheduler`.")
+        self._pred = L.PRED_LCM + L.PRED_TYPES[c.prediction_type]
+        self._init_ladder()
+        self.final_alpha_cumprod = torch.tensor(1.0) if c.set_alpha_to_one else self.alphas_cumprod[0]
+        self.custom_timesteps = False
+        self._den_step = None        # device int32: the row the eager step()'s second launch reads (n + step)
+
+    def set_timesteps(self, num_inference_steps: Optional[int] = None, device=None, original_inference_steps: Optional[int] = None,
+                      timesteps: Optional[List[int]] = None, strength: float = 1.0):
+        c = self.config
+        n_train = c.num_train_timesteps
+        if num_inference_steps is None and timesteps is None:
+            raise ValueError("Must pass exactly one of `num_inference_steps` or `custom_timesteps`.")
+        if num_inference_steps is not None and timesteps is not None:
+            raise ValueError("Can only pass one of `num_inference_steps` or `custom_timesteps`.")
+        orig = original_inference_steps if original_inference_steps is not None else c.original_inference_steps
+        if orig > n_train:
+            raise ValueError(f"`original_steps`: {orig} cannot be larger than `self.config.train_timesteps`: {n_train} as the unet "
+                             f"model trained with this scheduler can only handle maximal {n_train} timesteps.")
+        # the schedule the model was distilled on: every k-th training timestep, cut to `strength`
+        k = n_train // orig
+        origin = np.asarray(list(range(1, int(orig * strength) + 1)), dtype=np.int64) * k - 1
+        if timesteps is not None:
+            ts = np.array(timesteps, dtype=np.int64)
+            if len(ts) == 0 or (np.diff(ts) >= 0).any():
+                raise ValueError("`custom_timesteps` must be in descending order.")
+            if ts[0] >= n_train:
+                raise ValueError(f"`timesteps` must start before `self.config.train_timesteps`: {n_train}.")
+            n = len(ts)
+            self.custom_timesteps = True
+            # img2img: the tail that `strength` leaves, as the reference cuts a custom schedule
+            ts = ts[max(n - min(int(n * strength), n), 0):].copy()
+        else:
+            n = int(num_inference_steps)
+            if n > n_train:
+                raise ValueError(f"`num_inference_steps`: {n} cannot be larger than `self.config.train_timesteps`: {n_train} as "
+                                 f"the unet model trained with this scheduler can only handle maximal {n_train} timesteps.")
+            if len(origin) // n < 1:
+                raise ValueError(f"The combination of `original_steps x strength`: {orig} x {strength} is smaller than "
+                                 f"`num_inference_steps`: {n}. Make sure to either reduce `num_inference_steps` to a value smaller "
+                                 f"than {int(orig * strength)} or increase `strength` to a value higher than {float(n / orig)}.")
+            if n > orig:
+                raise ValueError(f"`num_inference_steps`: {n} cannot be larger than `original_inference_steps`: {orig} because the "
+                                 "final timestep schedule will be a subset of the `original_inference_steps`-sized initial "
+                                 "timestep schedule.")
+            self.custom_timesteps = False
+            origin = origin[::-1].copy()
+            ts = origin[np.floor(np.linspace(0, len(origin), num=n, endpoint=False)).astype(np.int64)]
+        rows = _lcm_rows(self.alphas_cumprod, ts, c.timestep_scaling, float(c.clip_sample_range) if c.clip_sample else 0.0)
+        den = rows.copy()
+        den[:, 4], den[:, 5] = 1.0, 0.0
+        self._set_schedule(len(ts), torch.from_numpy(ts).to(device), ts, np.concatenate([rows, den]), device)
+        if self._den_step is None or self._den_step.device != self._step_dev.device:
+            self._den_step = torch.zeros_like(self._step_dev)
+
+    def step_noise_draws(self, begin: int, n_steps: int) -> int:
+        """Engine extension: how many of the ``n_steps`` steps from schedule entry ``begin`` draw noise -- every step but the
+        schedule's last (scheduling_lcm.py step: ``if self.step_index != self.num_inference_steps - 1``)."""
+        return max(min(begin + n_steps, self.num_inference_steps - 1) - begin, 0)
+
+    def step(self, model_output, timestep, sample, generator=None, return_dict: bool = True):
+        self._before_step(timestep)
+        i, n = self._step_index, self.num_inference_steps
+        model_output, sample = model_output.contiguous(), sample.contiguous()
+        # `denoised` first, from row n + i (its slots 4, 5 = 1, 0: no noise read; the pointer only has to be there)
+        self._den_step.fill_(n + i)
+        denoised = ops.x0_linear_step(model_output, sample, sample, self._table, self._den_step, cfg=False, guidance=0.0,
+                                      pred_type=self._pred)
+        if i == n - 1:
+            self._advance()
+            prev = denoised
+        else:
+            noise = self._draw_like_reference(model_output, generator).contiguous()
+            prev = self._run(model_output, sample, noise, 0, False, 0.0)
+        if not return_dict:
+            return (prev, denoised)
+        return LCMSchedulerOutput(prev_sample=prev, denoised=denoised)
+
+    def step_cfg(self, model_output_2b, sample, guidance_scale: float, out=None, cfg: bool = True, noise_table=None):
+        """Engine extension: CFG combine (``cfg=False``: a plain model output) + the consistency step in one kernel, in place when
+        ``out`` is the sample.  ``noise_table`` [steps][numel of the sample], in the sample's dtype, holds every step's noise drawn
+        up front (the last step's row is not read); the kernel picks the row of the device step counter."""
+        if noise_table is None:
+            raise ValueError("LCMScheduler.step_cfg needs the pre-drawn `noise_table` [steps][numel]: the sampler adds fresh "
+                             "noise on every step but the last")
+        self._before_step(self.timesteps[0])
+        if noise_table.shape[0] != self.num_inference_steps:
+            raise ValueError(f"LCMScheduler.step_cfg: `noise_table` has {noise_table.shape[0]} rows for a "
+                             f"{self.num_inference_steps}-step schedule")
+        return self._run(model_output_2b, sample, noise_table, sample.numel(), cfg, float(guidance_scale), out)
 
 
 # ----------------------------------------------------------------------------------------------------------------------

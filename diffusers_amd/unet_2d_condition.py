@@ -78,8 +78,12 @@ class UNet2DConditionModel(PretrainedMixin):
             raise ValueError(f"addition_embed_type={c.addition_embed_type!r} is not supported")
         if c.dual_cross_attention or c.only_cross_attention or c.attention_type != "default" or c.upcast_attention:
             raise ValueError("unsupported attention variant")
-        if c.conv_in_kernel != 3 or c.conv_out_kernel != 3 or c.time_cond_proj_dim is not None:
-            raise ValueError("unsupported conv_in/out kernel or time_cond_proj_dim")
+        if c.conv_in_kernel != 3 or c.conv_out_kernel != 3:
+            raise ValueError("unsupported conv_in/out kernel")
+        tcd = c.time_cond_proj_dim
+        if tcd is not None and (isinstance(tcd, bool) or not isinstance(tcd, int) or tcd <= 0 or tcd % 8):
+            # (the skinny linear reads its K in 16-byte chunks; the distilled LCM checkpoints use 256)
+            raise ValueError(f"time_cond_proj_dim={tcd!r}: None or a positive multiple of 8")
         # options the engine has no code for must sit at their reference defaults: a non-default value would change the
         # reference's arithmetic, so it is refused rather than ignored
         for k in ("center_input_sample", "dropout", "resnet_skip_time_act", "resnet_out_scale_factor",
@@ -125,6 +129,14 @@ class UNet2DConditionModel(PretrainedMixin):
         self.conv_in_w = ops.pack_conv_weight(w.get("conv_in.weight"))
         self.conv_in_b = w.get("conv_in.bias")
         self.time_embedding = TimestepEmbedding(w, "time_embedding")
+        # TimestepEmbedding.cond_proj (models/embeddings.py:1276-1279, bias-free): the guidance-scale embedding of the distilled LCM
+        # checkpoints, projected onto the sinusoidal timestep embedding in front of linear_1
+        self.time_cond_proj = None
+        if c.time_cond_proj_dim is not None:
+            self.time_cond_proj = w.get("time_embedding.cond_proj.weight")
+            if tuple(self.time_cond_proj.shape) != (boc[0], c.time_cond_proj_dim):
+                raise ValueError(f"time_embedding.cond_proj.weight has shape {tuple(self.time_cond_proj.shape)}, the config asks for "
+                                 f"{(boc[0], c.time_cond_proj_dim)}")
         self.add_embedding = TimestepEmbedding(w, "add_embedding") if c.addition_embed_type == "text_time" else None
 
         self.down = build_down_blocks(w, c)
@@ -178,10 +190,13 @@ class UNet2DConditionModel(PretrainedMixin):
 
     def precompute_conditioning(self, encoder_hidden_states: torch.Tensor,
                                 added_cond_kwargs: Optional[Dict[str, torch.Tensor]] = None,
-                                encoder_attention_mask: Optional[torch.Tensor] = None) -> Dict[str, Any]:
-        """Everything in forward() that does not depend on the timestep or the latents."""
+                                encoder_attention_mask: Optional[torch.Tensor] = None,
+                                timestep_cond: Optional[torch.Tensor] = None) -> Dict[str, Any]:
+        """Everything in forward() that does not depend on the timestep or the latents.  ``timestep_cond`` (a U-Net with
+        ``time_cond_proj_dim``): kept as a static bf16 buffer the step reads by address."""
         ops.require_hip(encoder_hidden_states, "encoder_hidden_states")
         B = encoder_hidden_states.shape[0]
+        tc = self._check_timestep_cond(timestep_cond, B)
         ehs_pad, skv, skv_alloc = pad_encoder_states(encoder_hidden_states.contiguous())
         bias = None
         if encoder_attention_mask is not None:
@@ -190,9 +205,28 @@ class UNet2DConditionModel(PretrainedMixin):
         aug = None
         if self.config.addition_embed_type == "text_time":
             aug = self._text_time_embedding(added_cond_kwargs, B)
-        return {"kvs": kvs, "aug_emb": aug, "batch": B, "ehs_ptr": encoder_hidden_states.data_ptr()}
+        cond = {"kvs": kvs, "aug_emb": aug, "batch": B, "ehs_ptr": encoder_hidden_states.data_ptr()}
+        if tc is not None:
+            cond["timestep_cond"] = tc
+        return cond
 
-    def _cached_conditioning(self, encoder_hidden_states, added_cond_kwargs, encoder_attention_mask=None):
+    def _check_timestep_cond(self, timestep_cond, B: int):
+        """``timestep_cond`` as the step reads it: None for a U-Net without ``time_cond_proj_dim`` (which refuses the argument),
+        else a fresh contiguous bf16 [B][time_cond_proj_dim] tensor on the device."""
+        dim = self.config.time_cond_proj_dim
+        if dim is None:
+            if timestep_cond is not None:
+                raise ValueError("diffusers_amd UNet2DConditionModel.forward: `timestep_cond` is not supported on the HIP path "
+                                 "(this U-Net's config has no `time_cond_proj_dim`)")
+            return None
+        if timestep_cond is None:
+            raise ValueError(f"this U-Net has time_cond_proj_dim={dim}: `timestep_cond` [batch][{dim}] is required")
+        if not torch.is_tensor(timestep_cond) or timestep_cond.dim() != 2 or tuple(timestep_cond.shape) != (B, dim):
+            got = tuple(timestep_cond.shape) if torch.is_tensor(timestep_cond) else type(timestep_cond).__name__
+            raise ValueError(f"`timestep_cond` must be [{B}][{dim}] (batch, time_cond_proj_dim), got {got}")
+        return timestep_cond.to(device=self.device, dtype=bf16).contiguous().clone()
+
+    def _cached_conditioning(self, encoder_hidden_states, added_cond_kwargs, encoder_attention_mask=None, timestep_cond=None):
         """The drop-in path: an unchanged reference pipeline calls forward(sample, t, encoder_hidden_states=prompt_embeds,
         added_cond_kwargs=...) with the SAME tensors on every step (pipeline_stable_diffusion_xl.py:1208-1217), so the
         step-invariant work (140 K / V^T GEMMs + the text_time MLP for SDXL) is computed for the first call and reused
@@ -207,7 +241,7 @@ class UNet2DConditionModel(PretrainedMixin):
             return (t.data_ptr(), t._version, tuple(t.shape), t.dtype)
         added = added_cond_kwargs or {}
         key = (ident(encoder_hidden_states), ident(added.get("text_embeds")), ident(added.get("time_ids")),
-               ident(encoder_attention_mask))
+               ident(encoder_attention_mask), ident(timestep_cond))
         cacheable = not any(k is False for k in key)
         hit = getattr(self, "_cond_cache", None)
         if cacheable and hit is not None and hit[0] == key:
@@ -215,13 +249,13 @@ class UNet2DConditionModel(PretrainedMixin):
         ehs = encoder_hidden_states
         if ehs is not None and (ehs.dtype != bf16 or not ehs.is_cuda):
             ehs = ehs.to(device=self.device, dtype=bf16)
-        cond = self.precompute_conditioning(ehs, added_cond_kwargs, encoder_attention_mask)
+        cond = self.precompute_conditioning(ehs, added_cond_kwargs, encoder_attention_mask, timestep_cond)
         if not cacheable:
             self._cond_cache = None
             return cond
         # the cache holds references to the keyed tensors, so their storage (and data_ptr) cannot be recycled under it
         self._cond_cache = (key, cond, (encoder_hidden_states, added.get("text_embeds"), added.get("time_ids"),
-                                        encoder_attention_mask))
+                                        encoder_attention_mask, timestep_cond))
         return cond
 
     @staticmethod
@@ -279,15 +313,16 @@ class UNet2DConditionModel(PretrainedMixin):
         masked flash kernel), ``down_block_additional_residuals`` / ``mid_block_additional_residual`` (ControlNet, :1178-1222:
         added to the skip connections / the mid-block output), ``cross_attention_kwargs`` that change nothing
         (``None``, ``{}``, ``{"scale": 1.0}``).  Refused loudly: what has no engine path (self-attention ``attention_mask``,
-        ``class_labels``, ``timestep_cond``, T2I-Adapter intra-block residuals, GLIGEN, a LoRA ``scale`` != 1 -- fuse the
+        ``class_labels``, T2I-Adapter intra-block residuals, GLIGEN, a LoRA ``scale`` != 1 -- fuse the
         adapter with ``fuse_lora(scale)`` instead)."""
         if not self._built:
             raise RuntimeError("UNet2DConditionModel: call load_state_dict() first")
-        for name, v in (("class_labels", class_labels), ("timestep_cond", timestep_cond),
-                        ("attention_mask", attention_mask),
+        for name, v in (("class_labels", class_labels), ("attention_mask", attention_mask),
                         ("down_intrablock_additional_residuals", down_intrablock_additional_residuals)):
             if v is not None:
                 raise ValueError(f"diffusers_amd UNet2DConditionModel.forward: `{name}` is not supported on the HIP path")
+        if timestep_cond is not None and self.config.time_cond_proj_dim is None:
+            self._check_timestep_cond(timestep_cond, 0)      # refused by name
         if cross_attention_kwargs:
             extra = {k: v for k, v in cross_attention_kwargs.items() if not (k == "scale" and float(v) == 1.0)}
             if extra:
@@ -306,9 +341,14 @@ class UNet2DConditionModel(PretrainedMixin):
         if H % (2 ** n_up) or W_ % (2 ** n_up):
             raise ValueError("sample height/width must be divisible by 2**(num_upsamplers)")
         if conditioning is None:
-            conditioning = self._cached_conditioning(encoder_hidden_states, added_cond_kwargs, encoder_attention_mask)
+            conditioning = self._cached_conditioning(encoder_hidden_states, added_cond_kwargs, encoder_attention_mask, timestep_cond)
         elif encoder_attention_mask is not None:
             raise ValueError("pass encoder_attention_mask to precompute_conditioning() when `conditioning` is given")
+        elif timestep_cond is not None:
+            raise ValueError("pass timestep_cond to precompute_conditioning() when `conditioning` is given")
+        if c.time_cond_proj_dim is not None and conditioning.get("timestep_cond") is None:
+            raise ValueError(f"this U-Net has time_cond_proj_dim={c.time_cond_proj_dim}: `timestep_cond` is required "
+                             "(forward(timestep_cond=) or precompute_conditioning(timestep_cond=))")
         if inpaint_cond is not None:
             if c.in_channels != 9 or Cin != 4:
                 raise ValueError(f"`inpaint_cond` is for a U-Net with 9 input channels fed 4-channel latents (this one has "
@@ -337,6 +377,9 @@ class UNet2DConditionModel(PretrainedMixin):
                 t = t.expand(B)
             t_emb = ops.timestep_embedding(t.contiguous(), c.block_out_channels[0], batch=B,
                                            flip_sin_to_cos=c.flip_sin_to_cos, shift=float(c.freq_shift))
+        if self.time_cond_proj is not None:
+            # embeddings.py:1296-1297: sample + cond_proj(condition) = bf16(t_emb + bf16(cond_proj(c))), the skinny linear's epilogue
+            t_emb = ops.linear_small_m(conditioning["timestep_cond"], self.time_cond_proj, None, residual=t_emb)
         emb = self.time_embedding(t_emb, residual=conditioning["aug_emb"])  # emb + aug_emb fused as residual
         emb = self.time_proj(emb)                    # the resnets below take their columns of this
 

@@ -427,6 +427,14 @@ int da_rmsnorm_channels_bf16(const void* x, const void* gamma, void* y, long lon
  *                               row = [sqrt(beta_t), sqrt(alpha_t), k0, ke, kx, kn, clip_range, timestep]
  *                               noise (may be NULL) + step * noise_step_stride elements = this step's variance noise
  *                               (stride 0: one buffer refilled by the host per step; > 0: all steps pre-drawn)
+ *                               pred_type 4 + DA_PRED_* (4 epsilon, 5 v_prediction, 6 sample): the latent-consistency
+ *                               update of scheduling_lcm.py step() instead, same x0 forms, noise REQUIRED:
+ *                               row = [sqrt(1-abar_t), sqrt(abar_t), c_out, c_skip, sqrt(abar_prev), sqrt(1-abar_prev),
+ *                                      clip_range, timestep]
+ *                               denoised = c_out x0 + c_skip x; out = sqrt(abar_prev) denoised + sqrt(1-abar_prev) noise,
+ *                               every product / sum rounded in the tensor dtype.  A row with slot 5 == 0 (the last step
+ *                               of a schedule: slots 4, 5 = 1, 0) writes denoised and does not read the noise.  out may
+ *                               alias x.  3, 7 and anything else: DA_ERR_INVALID
  *   da_flowmatch_step           scheduling_flow_match_euler_discrete.py:423-523 ; row = [sigma, sigma_next, dt, ...]
  *   da_advance_step             the reference's `self._step_index += 1`
  * ------------------------------------------------------------------------------------------------------------------ */
