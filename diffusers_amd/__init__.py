@@ -16,6 +16,7 @@ _EXPORTS = {
     "ControlNetModel": "controlnet",
     "AutoencoderKL": "autoencoder_kl",
     "AutoencoderKLWan": "autoencoder_kl_wan",
+    "AutoencoderTiny": "autoencoder_tiny",
     "FluxTransformer2DModel": "transformer_flux",
     "FluxPipeline": "pipelines",
     "FluxImg2ImgPipeline": "pipelines",

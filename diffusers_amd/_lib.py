@@ -15,6 +15,7 @@ LIB_PATH = _PKG / "_C" / "libdiffusers_amd.so"
 DA_OK = 0
 ERRORS = {1: "DA_ERR_INVALID", 2: "DA_ERR_LAUNCH", 3: "DA_ERR_UNSUPPORTED"}
 ACT_NONE, ACT_GEGLU, ACT_GELU_TANH, ACT_SILU, ACT_GELU_ERF, ACT_QUICK_GELU, ACT_GEGLU_TANH = 0, 1, 2, 3, 4, 5, 6
+ACT_RELU = 7                 # DA_ACT_RELU: AutoencoderTiny's 64 -> 64 3x3 conv only (csrc/conv_c64.hip), bias + residual + ReLU
 (TILE_AUTO, TILE_128x128, TILE_64x128, TILE_128x64, TILE_64x64, TILE_256x128, TILE_128x256, TILE_256x256,
  TILE_128x128_W8, TILE_K2_128x128, TILE_K2_128x80, TILE_K2_128x160, TILE_K2_80x128, TILE_K2_128x64,
  TILE_K1_128x320, TILE_K1_256x128, TILE_K1_128x256, TILE_K1_256x160, TILE_K1_256x256, TILE_K1_256x320,
@@ -100,6 +101,7 @@ PASS_THROUGH = {
     "da_gemm_tune": "times trial launches of a problem; its result is a table entry, its outputs are overwritten by the real launch",
     "da_mfma_probe": "register-only clock probe of the benchmark; writes no memory",
     "da_plan_launch": "replays an existing plan from inside the library; plans do not nest, the recorder never sees its launches",
+    "da_tiny_vae_latents_in": "runs once per decode, outside any recorded step; ops.tiny_vae_latents_in refuses under a recording",
 }
 
 
@@ -164,6 +166,7 @@ SIGNATURES = {
     "da_vae_conv_in_image": (_i, [_vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "da_vae_posterior_latents": (_i, [_vp, _ll, _ll, _ll, _vp, _vp, _vp, _vp, _vp, _i, _ll, _i, _i, _i, _f, _f, _f, _f, _vp]),
     "da_flux_prepare_latents": (_i, [_vp, _ll, _ll, _ll, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _f, _f, _f, _f, _vp]),
+    "da_tiny_vae_latents_in": (_i, [_vp, _vp, _i, _i, _i, _i, _f, _f, _f, _vp]),
     "da_plan_create": (_i, [C.POINTER(PlanOp), _i, C.POINTER(C.c_void_p)]),
     "da_plan_launch": (_i, [_vp, _vp, C.POINTER(C.c_int)]),
     "da_plan_relocate": (_i, [_vp, _i, C.POINTER(C.c_void_p), C.POINTER(C.c_ulonglong), C.POINTER(C.c_void_p),

@@ -31,6 +31,9 @@ int dispatch_conv(const da_gemm_params& p, int tile, int staging, hipStream_t s)
 namespace da_gemm3 {   // the eight-phase 256 x 256 tile (gemm3.hip), nn.Linear only
 int dispatch_lin(const da_gemm_params& p, int tile, int staging, hipStream_t s);
 }
+namespace da_c64 {     // DA_ACT_RELU: the 64 -> 64 channel 3x3 conv of AutoencoderTiny (conv_c64.hip); checks its own params
+int launch(const da_gemm_params& p, hipStream_t s);
+}
 
 namespace {
 
@@ -96,7 +99,7 @@ int validate(da_gemm_params& p) {
   if ((p.act == DA_ACT_GEGLU || p.act == DA_ACT_GEGLU_TANH) &&
       ((p.N & 127) || p.out_f32 || p.residual || p.rowvec || p.gate || p.bias_rows))
     return DA_ERR_UNSUPPORTED;
-  if (p.act < 0 || p.act > DA_ACT_GEGLU_TANH) return DA_ERR_INVALID;
+  if (p.act < 0 || p.act > DA_ACT_RELU) return DA_ERR_INVALID;
   if (p.gate && p.gate_f32 == 2 && p.conv == 3) return DA_ERR_UNSUPPORTED;   // the rounded fp32 gate: nn.Linear and 1x1 convs
   if (p.split_k < 0 || p.split_k > DA_SPLITK_MAX) return DA_ERR_INVALID;
   if (p.split_k > 1 && (p.stats_out || p.ln_stats)) return DA_ERR_UNSUPPORTED;   // no split-K build of the LayerNorm fold
@@ -119,6 +122,7 @@ int stats_parts(const da_gemm_params& p, int tile) {   // one partial per column
 
 bool tile_ok(const da_gemm_params& p, int tile) {
   if (tile <= 0 || tile >= kNumTiles) return false;
+  if (p.act == DA_ACT_RELU) return false;   // no tile has that epilogue: da_gemm_bf16 hands it to conv_c64.hip before it gets here
   // gate_f32 == 2 (fp32 gate, product rounded to bf16) lives in the first family's epilogue only: the K2 / K1 / K3 epilogues
   // read any non-zero gate_f32 as the Wan mode
   if (p.gate && p.gate_f32 == 2 && (is_k2(tile) || is_k3(tile))) return false;
@@ -180,6 +184,7 @@ int run(const da_gemm_params& p, int tile, int staging, hipStream_t s, const da_
 
 extern "C" int da_gemm_bf16(const da_gemm_params* pp, void* stream) {
   if (!pp) return DA_ERR_INVALID;
+  if (pp->act == DA_ACT_RELU) return da_c64::launch(*pp, (hipStream_t)stream);   // one shape, its own kernel, no tile and no table
   da_gemm_params p = *pp;
   const int v = validate(p);
   if (v != DA_OK) return v;

@@ -6,6 +6,7 @@ from typing import Optional
 from . import init as dinit
 from .autoencoder_kl import AutoencoderKL
 from .autoencoder_kl_wan import AutoencoderKLWan
+from .autoencoder_tiny import AutoencoderTiny
 from .controlnet import ControlNetModel
 from .pipelines import (DDPMPipeline, FluxImg2ImgPipeline, FluxInpaintPipeline, FluxPipeline, StableDiffusionControlNetPipeline,
                         StableDiffusionImg2ImgPipeline, StableDiffusionInpaintPipeline, StableDiffusionPipeline,
@@ -88,6 +89,27 @@ def build_vae(cfg: dict, seed: int = 1, device="cuda", init_device: Optional[str
     return vae, state_dict
 
 
+def build_tiny_vae(cfg: dict, seed: int = 1, device="cuda", init_device: Optional[str] = None, state_dict=None,
+                   with_encoder: bool = True):
+    """AutoencoderTiny (``init.TAESD`` / ``TAESDXL`` / ``TAEF1`` or a sibling) with seeded random weights; ``with_encoder=False``
+    packs the decoder half only (random_state_dict seeds per key: the decoder weights are the same either way)."""
+    vae = AutoencoderTiny(**cfg)
+    if state_dict is None:
+        shapes = dinit.tiny_vae_param_shapes(vae.config, halves=("encoder", "decoder") if with_encoder else ("decoder",))
+        state_dict = dinit.random_state_dict(shapes, seed=seed, device=init_device or "cpu")
+    vae.load_state_dict(state_dict, device=device)
+    return vae, state_dict
+
+
+def _vae_for(tiny_vae: bool, tiny: bool, full_cfg: dict, tiny_cfg: dict, kl_cfg: dict, seed: int, device, idev, with_encoder: bool):
+    """The pipeline's ``vae``: AutoencoderKL, or -- ``tiny_vae`` -- AutoencoderTiny (text-to-image only)."""
+    if not tiny_vae:
+        return build_vae(kl_cfg, seed=seed, device=device, init_device=idev, with_encoder=with_encoder)[0]
+    if with_encoder:
+        raise ValueError("tiny_vae=True builds a text-to-image pipeline: AutoencoderTiny has no posterior for img2img / inpainting")
+    return build_tiny_vae(tiny_cfg if tiny else full_cfg, seed=seed, device=device, init_device=idev, with_encoder=False)[0]
+
+
 def build_wan_vae(cfg: dict, seed: int = 21, device="cuda", init_device: Optional[str] = None, state_dict=None):
     vae = AutoencoderKLWan(**cfg)
     if state_dict is None:
@@ -113,14 +135,16 @@ def _controlnet_for(ucfg: dict, tiny: bool, seed: int, device, idev, controlnet)
 
 def build_sdxl_pipeline(device="cuda", tiny: bool = False, seed: int = 0, init_device: Optional[str] = None,
                         with_encoder: bool = False, img2img: bool = False, inpaint: bool = False, unet_in_channels: int = 4,
-                        controlnet=False, scheduler: Optional[str] = None, time_cond_proj_dim: Optional[int] = None):
+                        controlnet=False, scheduler: Optional[str] = None, time_cond_proj_dim: Optional[int] = None,
+                        tiny_vae: bool = False):
     """SDXL-base (BASELINE config 3) or its tiny sibling.  Full size: weights are generated on ``init_device``
     (default: the HIP device, ~2.6 B parameters in seconds) and freed after packing.  ``with_encoder``: the VAE's encoder as
     well; ``img2img``: the same components in a StableDiffusionXLImg2ImgPipeline, ``inpaint``: in a
     StableDiffusionXLInpaintPipeline (both imply ``with_encoder``), whose U-Net takes ``unet_in_channels`` = 4 or 9 input channels.
     ``controlnet``: True (a seeded ControlNet, seed + 3) or a ControlNetModel -- a StableDiffusionXLControlNetPipeline (text-to-image).
     ``scheduler="lcm"``: LCMScheduler instead of Euler; ``time_cond_proj_dim``: a U-Net with the guidance-scale embedding input of the
-    distilled LCM checkpoints (``time_embedding.cond_proj``)."""
+    distilled LCM checkpoints (``time_embedding.cond_proj``).  ``tiny_vae``: AutoencoderTiny (TAESDXL, or its two-stage sibling with
+    ``tiny``) in the ``vae`` slot instead of AutoencoderKL -- text-to-image and ControlNet only."""
     ucfg = dinit.TINY_SDXL_UNET if tiny else dinit.SDXL_UNET
     if time_cond_proj_dim is not None:
         ucfg = dict(ucfg, time_cond_proj_dim=int(time_cond_proj_dim))
@@ -129,7 +153,7 @@ def build_sdxl_pipeline(device="cuda", tiny: bool = False, seed: int = 0, init_d
     vcfg = dinit.TINY_VAE if tiny else dinit.SDXL_VAE
     idev = init_device or ("cpu" if tiny else str(device))
     unet, _ = build_unet(ucfg, seed=seed, device=device, init_device=idev)
-    vae, _ = build_vae(vcfg, seed=seed + 1, device=device, init_device=idev, with_encoder=with_encoder or img2img or inpaint)
+    vae = _vae_for(tiny_vae, tiny, dinit.TAESDXL, dinit.TINY_TAESD, vcfg, seed + 1, device, idev, with_encoder or img2img or inpaint)
     sch = _scheduler_for(scheduler, lambda: EulerDiscreteScheduler(**SDXL_SCHEDULER))
     if controlnet:
         if img2img or inpaint:
@@ -142,8 +166,9 @@ def build_sdxl_pipeline(device="cuda", tiny: bool = False, seed: int = 0, init_d
 
 def build_sd15_pipeline(device="cuda", tiny: bool = False, seed: int = 0, init_device: Optional[str] = None,
                         with_encoder: bool = False, img2img: bool = False, inpaint: bool = False, unet_in_channels: int = 4,
-                        controlnet=False, scheduler: Optional[str] = None, time_cond_proj_dim: Optional[int] = None):
-    """SD1.5 or its tiny sibling, as ``build_sdxl_pipeline`` (DDIM by default)."""
+                        controlnet=False, scheduler: Optional[str] = None, time_cond_proj_dim: Optional[int] = None,
+                        tiny_vae: bool = False):
+    """SD1.5 or its tiny sibling, as ``build_sdxl_pipeline`` (DDIM by default; ``tiny_vae``: TAESD)."""
     ucfg = dinit.TINY_SD15_UNET if tiny else dinit.SD15_UNET
     if time_cond_proj_dim is not None:
         ucfg = dict(ucfg, time_cond_proj_dim=int(time_cond_proj_dim))
@@ -152,7 +177,7 @@ def build_sd15_pipeline(device="cuda", tiny: bool = False, seed: int = 0, init_d
     vcfg = dinit.TINY_VAE if tiny else dinit.SD_VAE
     idev = init_device or ("cpu" if tiny else str(device))
     unet, _ = build_unet(ucfg, seed=seed, device=device, init_device=idev)
-    vae, _ = build_vae(vcfg, seed=seed + 1, device=device, init_device=idev, with_encoder=with_encoder or img2img or inpaint)
+    vae = _vae_for(tiny_vae, tiny, dinit.TAESD, dinit.TINY_TAESD, vcfg, seed + 1, device, idev, with_encoder or img2img or inpaint)
     sch = _scheduler_for(scheduler, lambda: DDIMScheduler(**SD15_SCHEDULER))
     if controlnet:
         if img2img or inpaint:
@@ -172,15 +197,15 @@ def build_flux_transformer(cfg: dict, seed: int = 5, device="cuda", init_device:
 
 
 def build_flux_pipeline(device="cuda", tiny: bool = False, seed: int = 5, init_device: Optional[str] = None,
-                        with_encoder: bool = False, img2img: bool = False, inpaint: bool = False):
+                        with_encoder: bool = False, img2img: bool = False, inpaint: bool = False, tiny_vae: bool = False):
     """FLUX.1-schnell (BASELINE config 4) or its tiny sibling: transformer + 16-channel VAE + FlowMatch-Euler (shift 1).
     ``with_encoder``: the VAE's encoder as well; ``img2img``: the same components in a FluxImg2ImgPipeline, ``inpaint``: in a
-    FluxInpaintPipeline (both imply ``with_encoder``)."""
+    FluxInpaintPipeline (both imply ``with_encoder``).  ``tiny_vae``: AutoencoderTiny (TAEF1) as the ``vae`` (text-to-image only)."""
     tcfg = dinit.TINY_FLUX if tiny else dinit.FLUX_SCHNELL
     vcfg = dinit.TINY_FLUX_VAE if tiny else dinit.FLUX_VAE
     idev = init_device or ("cpu" if tiny else str(device))
     tr, _ = build_flux_transformer(tcfg, seed=seed, device=device, init_device=idev)
-    vae, _ = build_vae(vcfg, seed=seed + 1, device=device, init_device=idev, with_encoder=with_encoder or img2img or inpaint)
+    vae = _vae_for(tiny_vae, tiny, dinit.TAEF1, dinit.TINY_TAEF1, vcfg, seed + 1, device, idev, with_encoder or img2img or inpaint)
     sch = FlowMatchEulerDiscreteScheduler(shift=1.0, use_dynamic_shifting=False)
     cls = FluxInpaintPipeline if inpaint else FluxImg2ImgPipeline if img2img else FluxPipeline
     return cls(scheduler=sch, vae=vae, transformer=tr)

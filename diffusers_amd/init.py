@@ -546,3 +546,62 @@ SMALL_SD15_UNET = dict(sample_size=8, in_channels=4, out_channels=4, block_out_c
 TINY_VAE = dict(in_channels=3, out_channels=3, block_out_channels=(64, 128), layers_per_block=1,
                 down_block_types=("DownEncoderBlock2D",) * 2, up_block_types=("UpDecoderBlock2D",) * 2,
                 latent_channels=4, sample_size=32, scaling_factor=0.13025)
+# AutoencoderTiny (TAESD): the 64-channel, ReLU-only codec of models/autoencoders/autoencoder_tiny.py.  TAESD decodes SD1.x / SD2.x
+# latents, TAESDXL SDXL latents (same architecture, other weights), TAEF1 FLUX.1's 16-channel latents (its config carries FLUX's
+# scaling / shift factors, so the pipeline's `latents / scaling_factor + shift_factor` hands it the raw latents).
+TAESD = dict(in_channels=3, out_channels=3, encoder_block_out_channels=(64, 64, 64, 64), decoder_block_out_channels=(64, 64, 64, 64),
+             act_fn="relu", upsample_fn="nearest", latent_channels=4, upsampling_scaling_factor=2, num_encoder_blocks=(1, 3, 3, 3),
+             num_decoder_blocks=(3, 3, 3, 1), latent_magnitude=3, latent_shift=0.5, force_upcast=False, scaling_factor=1.0,
+             shift_factor=0.0)
+TAESDXL = dict(TAESD)
+TAEF1 = dict(TAESD, latent_channels=16, scaling_factor=0.3611, shift_factor=0.1159)
+# two stages (2x, like TINY_VAE / TINY_FLUX_VAE) with one block each: the siblings the tiny pipelines and the tests use
+TINY_TAESD = dict(TAESD, encoder_block_out_channels=(64, 64), decoder_block_out_channels=(64, 64), num_encoder_blocks=(1, 1),
+                  num_decoder_blocks=(1, 1))
+TINY_TAEF1 = dict(TINY_TAESD, latent_channels=16, scaling_factor=0.3611, shift_factor=0.1159)
+
+
+def _tiny_block(sh, p, c):
+    for i in (0, 2, 4):                       # Sequential(conv, ReLU, conv, ReLU, conv): the ReLUs take an index, no parameters
+        sh[f"{p}.conv.{i}.weight"] = (c, c, 3, 3)
+        sh[f"{p}.conv.{i}.bias"] = (c,)
+
+
+def tiny_vae_layer_plan(cfg, half: str):
+    """The ``layers`` Sequential of EncoderTiny / DecoderTiny (vae.py) as ``(index, kind, ...)`` entries: ``("conv", cin, cout,
+    stride, bias)``, ``("relu",)``, ``("block", c)``, ``("up",)``.  One walk serves the parameter inventory and the engine class."""
+    lat = cfg["latent_channels"]
+    plan = []
+    if half == "encoder":
+        boc, nb = tuple(cfg["encoder_block_out_channels"]), tuple(cfg["num_encoder_blocks"])
+        for i, n in enumerate(nb):
+            plan.append(("conv", cfg["in_channels"], boc[i], 1, True) if i == 0 else ("conv", boc[i], boc[i], 2, False))
+            plan.extend(("block", boc[i]) for _ in range(n))
+        plan.append(("conv", boc[-1], lat, 1, True))
+    elif half == "decoder":
+        boc, nb = tuple(cfg["decoder_block_out_channels"]), tuple(cfg["num_decoder_blocks"])
+        plan += [("conv", lat, boc[0], 1, True), ("relu",)]
+        for i, n in enumerate(nb):
+            last = i == len(nb) - 1
+            plan.extend(("block", boc[i]) for _ in range(n))
+            if not last:
+                plan.append(("up",))
+            plan.append(("conv", boc[i], cfg["out_channels"] if last else boc[i], 1, last))
+    else:
+        raise ValueError("half must be 'encoder' or 'decoder'")
+    return [(i,) + e for i, e in enumerate(plan)]
+
+
+def tiny_vae_param_shapes(cfg, halves=("encoder", "decoder")) -> "OrderedDict[str, Tuple[int, ...]]":
+    """AutoencoderTiny's state_dict: ``encoder.layers.N...`` / ``decoder.layers.N...`` with N the Sequential index."""
+    sh: "OrderedDict[str, Tuple[int, ...]]" = OrderedDict()
+    for half in halves:
+        for e in tiny_vae_layer_plan(cfg, half):
+            p = f"{half}.layers.{e[0]}"
+            if e[1] == "conv":
+                sh[f"{p}.weight"] = (e[3], e[2], 3, 3)
+                if e[5]:
+                    sh[f"{p}.bias"] = (e[3],)
+            elif e[1] == "block":
+                _tiny_block(sh, p, e[2])
+    return sh

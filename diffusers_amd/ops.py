@@ -585,7 +585,9 @@ def conv2d_nhwc(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] =
     ``k_valid`` > 0 (single source only): channels >= k_valid of x AND of every tap of w are zero padding up to the 64-wide
     K granule; the kernel skips the MFMA steps that would multiply them (da_gemm_params.k_valid).
     ``gate`` [B][Cout] (bf16 or fp32) multiplies the bf16-rounded conv output per batch before the residual add, with the rounding
-    modes of :func:`linear` (``gate_round``: 1x1 convs only)."""
+    modes of :func:`linear` (``gate_round``: 1x1 convs only).
+    ``act=ACT_RELU`` is AutoencoderTiny's conv on its own kernel (csrc/conv_c64.hip): 3x3, stride 1, 64 -> 64 channels, bias and
+    residual optional, ``out = max(bf16(conv + bias + residual), 0)`` with ONE rounding and the ReLU last; nothing else is admitted."""
     _req(x, "x"), _req(w, "w")
     if x2 is not None:
         _req(x2, "x2")
@@ -627,6 +629,16 @@ def conv2d_nhwc(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] =
     if not 0 <= k_valid <= C1 or (k_valid and C2):
         raise ValueError(f"conv2d_nhwc: k_valid {k_valid} outside [0, C1 = {C1}] (or given with a second source)")
     p.k_valid = 0 if k_valid == C1 else k_valid
+    if act == L.ACT_RELU:
+        # AutoencoderTiny's conv (csrc/conv_c64.hip): one shape, one kernel -- DA_TILE_AUTO, no tuning-table lookup or entry, no
+        # split-K workspace; the library refuses every launch that is not that shape
+        if tile is not None or staging is not None or split_k not in (None, 1):
+            raise ValueError("conv2d_nhwc: act=ACT_RELU takes no tile / staging / split_k (it has one kernel)")
+        if inplace:
+            raise ValueError("conv2d_nhwc: act=ACT_RELU does not run in place: `out` must not be `residual`")
+        p.tile, p.staging, p.split_k = L.TILE_AUTO, L.STAGE_REGISTER, 1
+        L.check(L.load().da_gemm_bf16(C.byref(p), _stream()), "da_gemm_bf16(conv, relu)")
+        return out
     _prefetch_hook(p, x, w)
     st = _stream()
     _select_variant(p, tile, staging, st, inplace=inplace, split_k=split_k, device=x.device)
@@ -1423,6 +1435,24 @@ def vae_conv_in_image(img: torch.Tensor, w: torch.Tensor, bias: Optional[torch.T
     y = torch.empty((B, H, W_, Cout), device=img.device, dtype=bf16)
     L.check(L.load().da_vae_conv_in_image(img.data_ptr(), src, w.data_ptr(), _ptr(bias), y.data_ptr(), B, H, W_, Cout,
                                           int(bool(normalize)), _stream()), "da_vae_conv_in_image")
+    return y
+
+
+def tiny_vae_latents_in(z: torch.Tensor, *, in_div: float = 1.0, in_add: float = 0.0, magnitude: float = 3.0) -> torch.Tensor:
+    """The head of AutoencoderTiny's decoder (da_tiny_vae_latents_in, csrc/conv_c64.hip): NCHW bf16 latents [B][L][H][W], L <= 16 ->
+    NHWC bf16 [B][H][W][64] holding ``tanh((z / in_div + in_add) / magnitude) * magnitude`` (every torch op of the reference
+    rounded to bf16) in channels < L and zeros above.  Runs once per decode and has no plan number: refused while a launch plan is
+    being recorded, so that a plan can never silently miss it."""
+    if getattr(L._tls, "recorder", None) is not None:
+        raise RuntimeError("tiny_vae_latents_in: not replayable by a launch plan (da_tiny_vae_latents_in has no DA_FN_* number); "
+                           "decode outside the recording")
+    _req(z, "z")
+    if z.dim() != 4 or not z.is_contiguous() or not 1 <= z.shape[1] <= 16:
+        raise ValueError(f"tiny_vae_latents_in: contiguous NCHW latents with 1 .. 16 channels expected, got {tuple(z.shape)}")
+    B, Lc, H, W_ = z.shape
+    y = torch.empty((B, H, W_, 64), device=z.device, dtype=bf16)
+    L.check(L.load().da_tiny_vae_latents_in(z.data_ptr(), y.data_ptr(), B, Lc, H, W_, float(in_div), float(in_add), float(magnitude),
+                                            _stream()), "da_tiny_vae_latents_in")
     return y
 
 

@@ -31,6 +31,7 @@ _SHAPES: Dict[str, Callable] = {
     "ControlNetModel": dinit.controlnet_param_shapes,
     "AutoencoderKL": dinit.vae_decoder_param_shapes,
     "AutoencoderKLWan": dinit.wan_vae_decoder_param_shapes,
+    "AutoencoderTiny": lambda cfg: dinit.tiny_vae_param_shapes(cfg, halves=("decoder",)),
     "FluxTransformer2DModel": dinit.flux_param_shapes,
     "WanTransformer3DModel": dinit.wan_param_shapes,
     "UNet2DModel": dinit.unet2d_param_shapes,
@@ -38,6 +39,7 @@ _SHAPES: Dict[str, Callable] = {
 # optional halves a checkpoint may or may not hold: (packed-path prefix, inventory) -- in the skeleton when the file has them
 _OPTIONAL_SHAPES: Dict[str, Tuple[str, Callable]] = {
     "AutoencoderKL": ("encoder.", dinit.vae_encoder_param_shapes),
+    "AutoencoderTiny": ("encoder.", lambda cfg: dinit.tiny_vae_param_shapes(cfg, halves=("encoder",))),
 }
 
 

@@ -116,6 +116,15 @@ def _decode_postprocessed(vae, latents: torch.Tensor, output_type: str, **decode
     return [Image.fromarray(a.squeeze(-1), mode="L") if a.shape[-1] == 1 else Image.fromarray(a) for a in arr]
 
 
+def _refuse_tiny_vae(vae, who: str) -> None:
+    """The image-conditioned pipelines sample / scale a posterior in their latent-prep kernels (ops.vae_posterior_latents,
+    ops.flux_prepare_latents); AutoencoderTiny's encoder returns latents and has none."""
+    if type(vae).__name__ == "AutoencoderTiny":
+        raise NotImplementedError(f"{who}: AutoencoderTiny has no posterior (its encoder returns latents, not a distribution), which "
+                                  "the img2img / inpainting latent preparation reads; use an AutoencoderKL here (AutoencoderTiny "
+                                  "serves the text-to-image pipelines)")
+
+
 def _per_prompt(t: Optional[torch.Tensor], n: int) -> Optional[torch.Tensor]:
     """``num_images_per_prompt`` copies of each row of caller-supplied embeddings, the copies of one prompt adjacent -- what the
     reference's SD / SDXL ``encode_prompt`` does to ``prompt_embeds`` it is handed (pipeline_stable_diffusion_xl.py:488-516:
@@ -963,6 +972,7 @@ class StableDiffusionXLImg2ImgPipeline(_Img2ImgMixin, StableDiffusionXLPipeline)
                     aesthetic_score, negative_aesthetic_score, clip_skip, callback_on_step_end, callback_on_step_end_tensor_inputs,
                     use_graph):
         """The call of the SDXL img2img and inpainting pipelines; ``_start_latents`` is what differs."""
+        _refuse_tiny_vae(self.vae, type(self).__name__)
         if image is None and latents is None:
             raise ValueError("`image` input cannot be undefined.")
         if eta != 0.0:
@@ -1025,6 +1035,7 @@ class StableDiffusionImg2ImgPipeline(_Img2ImgMixin, StableDiffusionPipeline):
                     latents, prompt_embeds, negative_prompt_embeds, output_type, return_dict, clip_skip, guidance_rescale,
                     callback_on_step_end, callback_on_step_end_tensor_inputs, use_graph):
         """The call of the SD img2img and inpainting pipelines; ``_start_latents`` is what differs."""
+        _refuse_tiny_vae(self.vae, type(self).__name__)
         if image is None:
             raise ValueError("`image` input cannot be undefined.")
         do_cfg = self._arm(guidance_scale, guidance_rescale, callback_on_step_end, callback_on_step_end_tensor_inputs)
@@ -1705,6 +1716,7 @@ class FluxImg2ImgPipeline(FluxPipeline):
                     num_images_per_prompt, generator, latents, prompt_embeds, pooled_prompt_embeds, negative_prompt,
                     negative_prompt_embeds, negative_pooled_prompt_embeds, output_type, return_dict, max_sequence_length, use_graph,
                     callback_on_step_end, callback_on_step_end_tensor_inputs):
+        _refuse_tiny_vae(self.vae, type(self).__name__)
         _check_strength(strength)
         if image is None:
             raise ValueError("`image` input cannot be undefined.")

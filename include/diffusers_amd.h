@@ -36,6 +36,13 @@ extern "C" {
 #define DA_ACT_QUICK_GELU 5  /* x * sigmoid(1.702 x): transformers ACT2FN["quick_gelu"], the CLIP-L text encoder's MLP */
 #define DA_ACT_GEGLU_TANH 6  /* DA_ACT_GEGLU with the tanh GELU on the gate rows: T5 / UMT5 "gated-gelu" feed-forward
                                 (gelu_new(wi_0 x) * (wi_1 x), modeling_t5.py T5DenseGatedActDense); rows packed [32 wi_1 | 32 wi_0] */
+#define DA_ACT_RELU 7        /* AutoencoderTiny's conv (csrc/conv_c64.hip): out = max(bf16(acc + bias + residual), 0) -- bias and
+                                residual join the fp32 accumulator, ONE rounding, ReLU last (relu(conv(x) + x), vae.py
+                                AutoencoderTinyBlock).  One shape only: conv == 3, stride 1, up 0, pad 1, C1 == N == 64, C2 == 0,
+                                K == 576, tile == DA_TILE_AUTO, k_valid 0 or 1 .. 64, bf16 output, bias / residual optional
+                                (residual must not alias C), none of rowvec, gate, bias_rows, split_k > 1, stats_out, ln_stats, vt,
+                                xa_*, out_f32, alpha / out_scale other than 1.  Anything else with this code: DA_ERR_UNSUPPORTED and
+                                no launch.  The tuning table is never consulted for it. */
 
 #define DA_TILE_AUTO 0
 #define DA_TILE_128x128 1
@@ -624,6 +631,19 @@ int da_vae_posterior_latents(const void* in, long long sB, long long sC, long lo
 int da_flux_prepare_latents(const void* in, long long sB, long long sC, long long sP, const void* eps1, const void* noise,
                             void* latents_packed, void* image_latents_packed, void* noise_packed, int B, int H, int W, int L,
                             int mode, int flags, float shift, float scale, float a, float b, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------------
+ * AutoencoderTiny (TAESD; models/autoencoders/autoencoder_tiny.py, vae.py DecoderTiny): the head of its decoder.
+ *   da_tiny_vae_latents_in   x: NCHW bf16 latents [B][L][H][W], 1 <= L <= 16 -> y: NHWC bf16 [B][H][W][64] (16-byte aligned), the
+ *                            input of the 64-channel conv (DA_ACT_RELU, k_valid = L); channels >= L are written as zeros.
+ *                            y = bf16(bf16(tanh(bf16(bf16(bf16(x / in_div) + in_add) / magnitude))) * magnitude): the pipeline's
+ *                            latents / scaling_factor (+ shift_factor), then DecoderTiny's tanh(x / 3) * 3, each torch op rounded.
+ *                            in_div == 1 skips the first rounding, in_add == 0 the second.  DA_ERR_INVALID and no launch for a null
+ *                            pointer, L < 1, L > 16, a non-positive size, in_div or magnitude == 0, a misaligned y.
+ *                            Runs once per decode, outside any recorded step: no DA_FN_* plan number (DA_ABI_VERSION stays 9).
+ * ------------------------------------------------------------------------------------------------------------------ */
+int da_tiny_vae_latents_in(const void* x, void* y, int B, int L, int H, int W, float in_div, float in_add, float magnitude,
+                           void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------------
  * Launch plans: a recorded sequence of the launch entry points above, owned by the library and replayed by ONE call --
