@@ -38,9 +38,11 @@ _EXPORTS = {
     "StableDiffusionImg2ImgPipeline": "pipelines",
     "StableDiffusionXLImg2ImgPipeline": "pipelines",
     "StableDiffusionInpaintPipeline": "pipelines",
+    "StableDiffusionInstructPix2PixPipeline": "pipelines",
     "StableDiffusionControlNetPipeline": "pipelines",
     "StableDiffusionXLControlNetPipeline": "pipelines",
     "StableDiffusionXLInpaintPipeline": "pipelines",
+    "StableDiffusionXLInstructPix2PixPipeline": "pipelines",
     "from_reference_config": "config_utils",
     "CLIPTextModel": "text_encoders",
     "CLIPTextModelWithProjection": "text_encoders",

@@ -29,6 +29,7 @@ STAGE_REGISTER, STAGE_LDS_DIRECT, STAGE_LDS_DIRECT3, STAGE_LDS_DIRECT4, STAGE_LD
 STAGE_PINGPONG, STAGE_PINGPONG3 = 6, 7   # K2 tiles: 2- / 3-pair ring with the two K-groups half an iteration apart
 RING_SLOTS = (2, 2, 3, 4, 6, 8)  # LDS ring depth per staging code
 DTYPE_BF16, DTYPE_F32 = 0, 1
+CFG_IMAGE_GUIDANCE = 0x100   # da_cfg_rescale only: OR-ed into `dtype`, selects InstructPix2Pix's (text, image, uncond) guidance
 SPLITK_FLAGS = 4096          # DA_SPLITK_FLAGS
 SPLITK_ERR_SLOT = SPLITK_FLAGS - 1
 SPLITK_MAX = 24              # DA_SPLITK_MAX

@@ -307,13 +307,24 @@ __global__ __launch_bounds__(256) void conv_thin_in4_kernel(const void* __restri
 // The structure is conv_thin_in4_kernel's: weights in LDS k-major, four output pixels of a row per thread, a kernel row's six input columns
 // loaded once -- unconditionally, from clamped addresses, zeroed by a select -- for the four pixels that share them; per output element
 // bias, then the taps in (kh, kw, c) order, padded taps skipped: bit-identical to da_conv_thin_in_bf16 on the concatenated tensor.
+// CIN = 8 (mask unused) is the conv_in of an InstructPix2Pix U-Net: channels 0-3 from x, channels 4-7 from `masked`, which holds the
+// image latents.  The reference feeds cat([cat([s(x)] * 3), cat([img, img, zeros_like(img)])], dim=1): the (text, image) rows have
+// identical inputs and are stored from one computation (UNCOND = false: `rep` copies), the unconditional row is the same convolution
+// with channels 4-7 equal to zero.  UNCOND = true forms it in the same pass in a second accumulator set: same bias, same taps in
+// the same order, the image channels' values replaced by +0.0f (multiplied and added, as da_conv_thin_in_bf16 does with the zeros
+// it reads: x + 0 * w is not always x in the sign of a zero), stored as copy 2.  The loads, the LDS weight reads and the latent
+// channels' conversions are shared; 64 accumulators per thread (one wave per SIMD per block at 256 threads and <= 64 KiB of LDS
+// leaves 512 VGPRs a lane, of which this takes under 200).
+template <int CIN, bool UNCOND>
 __global__ __launch_bounds__(256) void conv_in_inpaint_kernel(const uint16_t* __restrict__ x, const uint16_t* __restrict__ mask,
                                                               const uint16_t* __restrict__ masked, const uint16_t* __restrict__ w,
                                                               const uint16_t* __restrict__ bias, uint16_t* __restrict__ y,
                                                               const float* __restrict__ table, const int* __restrict__ step_idx, int B,
                                                               int H, int W, int Cout, int rep, int cond_per_sample, int coc) {
-  extern __shared__ __attribute__((aligned(16))) float wsm[];  // [81][coc]
-  constexpr int CIN = 9, kk = 9 * CIN;
+  extern __shared__ __attribute__((aligned(16))) float wsm[];  // [9 * CIN][coc]
+  static_assert(CIN == 9 || CIN == 8, "9: latents | mask | masked image latents; 8: latents | image latents");
+  static_assert(CIN == 8 || !UNCOND, "the zero-image row belongs to the 8-channel form");
+  constexpr int kk = 9 * CIN, IMG0 = CIN - 4;                   // first channel read from `masked`
   const int co0 = blockIdx.y * coc;
   const int ncoc = min(coc, Cout - co0);
   for (int i = threadIdx.x; i < ncoc * kk; i += blockDim.x) {
@@ -335,6 +346,7 @@ __global__ __launch_bounds__(256) void conv_in_inpaint_kernel(const uint16_t* __
     const int b = (int)(quad / ((size_t)wq * H));
     const int bm = cond_per_sample ? b : 0;
     float acc[4][8];
+    float acu[UNCOND ? 4 : 1][8];                            // the zero-image row's accumulators
     {
       float bvs[8];
       if (bias) {                                            // (16-byte aligned: checked by the entry point)
@@ -346,7 +358,10 @@ __global__ __launch_bounds__(256) void conv_in_inpaint_kernel(const uint16_t* __
 #pragma unroll
       for (int e = 0; e < 8; ++e)
 #pragma unroll
-        for (int px = 0; px < 4; ++px) acc[px][e] = bvs[e];
+        for (int px = 0; px < 4; ++px) {
+          acc[px][e] = bvs[e];
+          if (UNCOND) acu[px][e] = bvs[e];
+        }
     }
 #pragma unroll
     for (int kh = 0; kh < 3; ++kh) {
@@ -354,7 +369,7 @@ __global__ __launch_bounds__(256) void conv_in_inpaint_kernel(const uint16_t* __
       const bool row_ok = (unsigned)iy < (unsigned)H;
       const int iyc = min(max(iy, 0), H - 1);
       const uint16_t* xrow = x + (size_t)b * 4 * plane + (size_t)iyc * W;
-      const uint16_t* mrow = mask + (size_t)bm * plane + (size_t)iyc * W;
+      const uint16_t* mrow = CIN == 9 ? mask + (size_t)bm * plane + (size_t)iyc * W : nullptr;
       const uint16_t* irow = masked + (size_t)bm * 4 * plane + (size_t)iyc * W;
       uint16_t raw[6][CIN];
 #pragma unroll
@@ -362,9 +377,9 @@ __global__ __launch_bounds__(256) void conv_in_inpaint_kernel(const uint16_t* __
         const int ixc = min(max(x0 + j - 1, 0), W - 1);
 #pragma unroll
         for (int c = 0; c < 4; ++c) raw[j][c] = xrow[(size_t)c * plane + ixc];
-        raw[j][4] = mrow[ixc];
+        if (CIN == 9) raw[j][4] = mrow[ixc];
 #pragma unroll
-        for (int c = 0; c < 4; ++c) raw[j][5 + c] = irow[(size_t)c * plane + ixc];
+        for (int c = 0; c < 4; ++c) raw[j][IMG0 + c] = irow[(size_t)c * plane + ixc];
       }
       float xin[6][CIN];
 #pragma unroll
@@ -391,6 +406,11 @@ __global__ __launch_bounds__(256) void conv_in_inpaint_kernel(const uint16_t* __
             const float xv = xin[px + kw][c];
             acc[px][0] += xv * w0.x; acc[px][1] += xv * w0.y; acc[px][2] += xv * w0.z; acc[px][3] += xv * w0.w;
             acc[px][4] += xv * w1.x; acc[px][5] += xv * w1.y; acc[px][6] += xv * w1.z; acc[px][7] += xv * w1.w;
+            if (UNCOND) {
+              const float xu = c < IMG0 ? xv : 0.f;
+              acu[px][0] += xu * w0.x; acu[px][1] += xu * w0.y; acu[px][2] += xu * w0.z; acu[px][3] += xu * w0.w;
+              acu[px][4] += xu * w1.x; acu[px][5] += xu * w1.y; acu[px][6] += xu * w1.z; acu[px][7] += xu * w1.w;
+            }
           }
         }
     }
@@ -400,7 +420,8 @@ __global__ __launch_bounds__(256) void conv_in_inpaint_kernel(const uint16_t* __
       const uint4 o = pack8(acc[px]);
       const size_t pix = ((size_t)b * H + yh) * W + x0 + px;
       *(uint4*)(y + pix * Cout + co0 + cg * 8) = o;
-      if (rep == 2) *(uint4*)(y + ((size_t)B * plane + pix) * Cout + co0 + cg * 8) = o;
+      if (rep >= 2) *(uint4*)(y + ((size_t)B * plane + pix) * Cout + co0 + cg * 8) = o;
+      if (UNCOND) *(uint4*)(y + ((size_t)2 * B * plane + pix) * Cout + co0 + cg * 8) = pack8(acu[px]);
     }
   }
 }
@@ -753,11 +774,13 @@ extern "C" int da_conv_thin_in_bf16(const void* x, const void* w, const void* bi
 extern "C" int da_conv_in_inpaint(const void* x, const void* mask, const void* masked, const void* w, const void* bias, void* y,
                                   const float* table, const int* step_idx, int B, int H, int W, int Cout, int rep, int Bm,
                                   void* stream) {
-  if (!x || !mask || !masked || !w || !y || B <= 0 || H <= 0 || W <= 0 || (table && !step_idx)) return DA_ERR_INVALID;
-  if ((rep != 1 && rep != 2) || (Bm != 1 && Bm != B)) return DA_ERR_INVALID;
+  if (!x || !masked || !w || !y || B <= 0 || H <= 0 || W <= 0 || (table && !step_idx)) return DA_ERR_INVALID;
+  // mask == NULL: the 8-channel (latents | image latents) InstructPix2Pix form, one copy or the (text, image, uncond) triple
+  const bool pix2pix = mask == nullptr;
+  if ((rep != 1 && rep != (pix2pix ? 3 : 2)) || (Bm != 1 && Bm != B)) return DA_ERR_INVALID;
   if (Cout <= 0 || (Cout & 7) || ((uintptr_t)bias & 15)) return DA_ERR_UNSUPPORTED;
-  // the launch geometry of the four-pixel branch of da_conv_thin_in_bf16 with Cin = 9: 81 x coc floats of weights per chunk
-  const int kk = 81;
+  // the launch geometry of the four-pixel branch of da_conv_thin_in_bf16 with Cin = 9 (8): 81 (72) x coc floats of weights per chunk
+  const int kk = pix2pix ? 72 : 81;
   int coc = ((64 * 1024) / (kk * (int)sizeof(float))) & ~7;
   if (coc > Cout) coc = Cout;
   const int nchunk = (Cout + coc - 1) / coc;
@@ -765,9 +788,14 @@ extern "C" int da_conv_in_inpaint(const void* x, const void* mask, const void* m
   const size_t cap = 768 / nchunk > 0 ? 768 / nchunk : 1;
   size_t qblocks = ((size_t)B * H * ((W + 3) / 4) * (coc / 8) + 255) / 256;
   if (qblocks > cap) qblocks = cap;
-  DA_LAUNCH(conv_in_inpaint_kernel, dim3((unsigned)qblocks, (unsigned)nchunk), dim3(256), lds, (hipStream_t)stream, (const uint16_t*)x,
-            (const uint16_t*)mask, (const uint16_t*)masked, (const uint16_t*)w, (const uint16_t*)bias, (uint16_t*)y, table, step_idx, B, H,
-            W, Cout, rep, Bm == B && B > 1 ? 1 : 0, coc);
+#define DA_CII(CIN, UNCOND)                                                                                                            \
+  DA_LAUNCH((conv_in_inpaint_kernel<CIN, UNCOND>), dim3((unsigned)qblocks, (unsigned)nchunk), dim3(256), lds, (hipStream_t)stream,       \
+            (const uint16_t*)x, (const uint16_t*)mask, (const uint16_t*)masked, (const uint16_t*)w, (const uint16_t*)bias, (uint16_t*)y, \
+            table, step_idx, B, H, W, Cout, rep, Bm == B && B > 1 ? 1 : 0, coc)
+  if (!pix2pix) DA_CII(9, false);
+  else if (rep == 3) DA_CII(8, true);
+  else DA_CII(8, false);
+#undef DA_CII
   DA_CHECK_LAUNCH();
   return DA_OK;
 }

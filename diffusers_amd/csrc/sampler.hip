@@ -100,6 +100,25 @@ __global__ void cfg_rescale_apply_kernel(const T* __restrict__ eps, T* __restric
   }
 }
 
+// InstructPix2Pix's three-way guidance (pipeline_stable_diffusion_instruct_pix2pix.py, the `do_classifier_free_guidance` branch of
+// the denoising loop; the SDXL pipeline has the same expression):
+//   noise_pred = noise_pred_uncond + guidance_scale * (noise_pred_text - noise_pred_image)
+//                                  + image_guidance_scale * (noise_pred_image - noise_pred_uncond)
+// eps layout [3][n] = (text, image, uncond).  Python evaluates it left to right, every op rounded in the tensor dtype:
+//   rnd(rnd(u + rnd(g * rnd(t - i))) + rnd(ig * rnd(i - u)))
+// -- five torch launches in the reference, one here; the step kernel that follows runs with cfg = 0.
+template <typename T>
+__global__ void cfg_combine3_kernel(const T* __restrict__ eps, T* __restrict__ out, float g, float ig, size_t n) {
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+    const float t = IO<T>::ld(eps, i), im = IO<T>::ld(eps, n + i), u = IO<T>::ld(eps, 2 * n + i);
+    const float d_ti = IO<T>::rnd(__fsub_rn(t, im));
+    const float left = IO<T>::rnd(__fadd_rn(u, IO<T>::rnd(__fmul_rn(g, d_ti))));
+    const float d_iu = IO<T>::rnd(__fsub_rn(im, u));
+    const float right = IO<T>::rnd(__fmul_rn(ig, d_iu));
+    IO<T>::st(out, i, __fadd_rn(left, right));
+  }
+}
+
 // Euler (gamma = 0): table row = [sigma, sigma_next, dt, sqrt(sigma^2+1), c_out, sigma^2+1, -, timestep]
 // PRED: 0 epsilon, 1 v_prediction, 2 sample (scheduling_euler_discrete.py:760-775)
 template <typename T, bool CFG, int PRED>
@@ -615,6 +634,22 @@ extern "C" int da_flowmatch_step(const void* v, const void* x, void* out, const 
 
 extern "C" int da_cfg_rescale(const void* eps, void* out, float* ratio_ws, int B, long long n_per_, float guidance,
                               float guidance_rescale, int dtype, void* stream) {
+  if (dtype & DA_CFG_IMAGE_GUIDANCE) {
+    // three-way (text, image, uncond) guidance: `guidance_rescale` carries image_guidance_scale, no statistics, ratio_ws unused
+    dtype &= ~DA_CFG_IMAGE_GUIDANCE;
+    if (!eps || !out || B <= 0 || n_per_ <= 0) return DA_ERR_INVALID;
+    const size_t n3 = (size_t)n_per_ * (size_t)B;
+    if (dtype == DA_DTYPE_BF16)
+      DA_LAUNCH((cfg_combine3_kernel<uint16_t>), ew_grid(n3), dim3(256), 0, (hipStream_t)stream, (const uint16_t*)eps, (uint16_t*)out,
+                guidance, guidance_rescale, n3);
+    else if (dtype == DA_DTYPE_F32)
+      DA_LAUNCH((cfg_combine3_kernel<float>), ew_grid(n3), dim3(256), 0, (hipStream_t)stream, (const float*)eps, (float*)out, guidance,
+                guidance_rescale, n3);
+    else
+      return DA_ERR_UNSUPPORTED;
+    DA_CHECK_LAUNCH();
+    return DA_OK;
+  }
   if (!eps || !out || !ratio_ws || B <= 0 || n_per_ <= 1) return DA_ERR_INVALID;
   const size_t n_per = (size_t)n_per_, n = n_per * (size_t)B;
   hipStream_t s = (hipStream_t)stream;

@@ -9,7 +9,8 @@ from .autoencoder_kl_wan import AutoencoderKLWan
 from .autoencoder_tiny import AutoencoderTiny
 from .controlnet import ControlNetModel
 from .pipelines import (DDPMPipeline, FluxImg2ImgPipeline, FluxInpaintPipeline, FluxPipeline, StableDiffusionControlNetPipeline,
-                        StableDiffusionImg2ImgPipeline, StableDiffusionInpaintPipeline, StableDiffusionPipeline,
+                        StableDiffusionImg2ImgPipeline, StableDiffusionInpaintPipeline, StableDiffusionInstructPix2PixPipeline,
+                        StableDiffusionPipeline, StableDiffusionXLInstructPix2PixPipeline,
                         StableDiffusionXLControlNetPipeline, StableDiffusionXLImg2ImgPipeline, StableDiffusionXLInpaintPipeline,
                         StableDiffusionXLPipeline, WanPipeline)
 from .schedulers import DDPMScheduler
@@ -125,6 +126,13 @@ def _inpaint_unet_config(ucfg: dict, unet_in_channels: int) -> dict:
     return ucfg if unet_in_channels == ucfg.get("in_channels", 4) else dict(ucfg, in_channels=unet_in_channels)
 
 
+def _pix2pix_unet_config(ucfg: dict, img2img: bool, inpaint: bool, controlnet, tiny_vae: bool) -> dict:
+    """``pix2pix=True``: the 8-channel U-Net of an InstructPix2Pix checkpoint (latents | image latents); a pipeline of its own."""
+    if img2img or inpaint or controlnet or tiny_vae:
+        raise ValueError("pix2pix=True builds the InstructPix2Pix pipeline: not together with img2img / inpaint / controlnet / tiny_vae")
+    return dict(ucfg, in_channels=8)
+
+
 def _controlnet_for(ucfg: dict, tiny: bool, seed: int, device, idev, controlnet):
     """``controlnet=True``: a seeded ControlNet for the U-Net config; a ControlNetModel is taken as it is."""
     if controlnet is not True:
@@ -136,7 +144,7 @@ def _controlnet_for(ucfg: dict, tiny: bool, seed: int, device, idev, controlnet)
 def build_sdxl_pipeline(device="cuda", tiny: bool = False, seed: int = 0, init_device: Optional[str] = None,
                         with_encoder: bool = False, img2img: bool = False, inpaint: bool = False, unet_in_channels: int = 4,
                         controlnet=False, scheduler: Optional[str] = None, time_cond_proj_dim: Optional[int] = None,
-                        tiny_vae: bool = False):
+                        tiny_vae: bool = False, pix2pix: bool = False):
     """SDXL-base (BASELINE config 3) or its tiny sibling.  Full size: weights are generated on ``init_device``
     (default: the HIP device, ~2.6 B parameters in seconds) and freed after packing.  ``with_encoder``: the VAE's encoder as
     well; ``img2img``: the same components in a StableDiffusionXLImg2ImgPipeline, ``inpaint``: in a
@@ -144,22 +152,27 @@ def build_sdxl_pipeline(device="cuda", tiny: bool = False, seed: int = 0, init_d
     ``controlnet``: True (a seeded ControlNet, seed + 3) or a ControlNetModel -- a StableDiffusionXLControlNetPipeline (text-to-image).
     ``scheduler="lcm"``: LCMScheduler instead of Euler; ``time_cond_proj_dim``: a U-Net with the guidance-scale embedding input of the
     distilled LCM checkpoints (``time_embedding.cond_proj``).  ``tiny_vae``: AutoencoderTiny (TAESDXL, or its two-stage sibling with
-    ``tiny``) in the ``vae`` slot instead of AutoencoderKL -- text-to-image and ControlNet only."""
+    ``tiny``) in the ``vae`` slot instead of AutoencoderKL -- text-to-image and ControlNet only.  ``pix2pix``: an 8-channel U-Net and the
+    VAE with its encoder in a StableDiffusionXLInstructPix2PixPipeline (exclusive with img2img / inpaint / controlnet / tiny_vae)."""
     ucfg = dinit.TINY_SDXL_UNET if tiny else dinit.SDXL_UNET
     if time_cond_proj_dim is not None:
         ucfg = dict(ucfg, time_cond_proj_dim=int(time_cond_proj_dim))
     if inpaint:
         ucfg = _inpaint_unet_config(ucfg, unet_in_channels)
+    if pix2pix:
+        ucfg = _pix2pix_unet_config(ucfg, img2img, inpaint, controlnet, tiny_vae)
     vcfg = dinit.TINY_VAE if tiny else dinit.SDXL_VAE
     idev = init_device or ("cpu" if tiny else str(device))
     unet, _ = build_unet(ucfg, seed=seed, device=device, init_device=idev)
-    vae = _vae_for(tiny_vae, tiny, dinit.TAESDXL, dinit.TINY_TAESD, vcfg, seed + 1, device, idev, with_encoder or img2img or inpaint)
+    vae = _vae_for(tiny_vae, tiny, dinit.TAESDXL, dinit.TINY_TAESD, vcfg, seed + 1, device, idev, with_encoder or img2img or inpaint or pix2pix)
     sch = _scheduler_for(scheduler, lambda: EulerDiscreteScheduler(**SDXL_SCHEDULER))
     if controlnet:
         if img2img or inpaint:
             raise ValueError("controlnet= builds the text-to-image ControlNet pipeline (no ControlNet img2img / inpainting pipeline)")
         return StableDiffusionXLControlNetPipeline(vae=vae, unet=unet, scheduler=sch,
                                                    controlnet=_controlnet_for(ucfg, tiny, seed, device, idev, controlnet))
+    if pix2pix:
+        return StableDiffusionXLInstructPix2PixPipeline(vae=vae, unet=unet, scheduler=sch)
     cls = StableDiffusionXLInpaintPipeline if inpaint else StableDiffusionXLImg2ImgPipeline if img2img else StableDiffusionXLPipeline
     return cls(vae=vae, unet=unet, scheduler=sch)
 
@@ -167,23 +180,28 @@ def build_sdxl_pipeline(device="cuda", tiny: bool = False, seed: int = 0, init_d
 def build_sd15_pipeline(device="cuda", tiny: bool = False, seed: int = 0, init_device: Optional[str] = None,
                         with_encoder: bool = False, img2img: bool = False, inpaint: bool = False, unet_in_channels: int = 4,
                         controlnet=False, scheduler: Optional[str] = None, time_cond_proj_dim: Optional[int] = None,
-                        tiny_vae: bool = False):
-    """SD1.5 or its tiny sibling, as ``build_sdxl_pipeline`` (DDIM by default; ``tiny_vae``: TAESD)."""
+                        tiny_vae: bool = False, pix2pix: bool = False):
+    """SD1.5 or its tiny sibling, as ``build_sdxl_pipeline`` (DDIM by default; ``tiny_vae``: TAESD; ``pix2pix``: a
+    StableDiffusionInstructPix2PixPipeline)."""
     ucfg = dinit.TINY_SD15_UNET if tiny else dinit.SD15_UNET
     if time_cond_proj_dim is not None:
         ucfg = dict(ucfg, time_cond_proj_dim=int(time_cond_proj_dim))
     if inpaint:
         ucfg = _inpaint_unet_config(ucfg, unet_in_channels)
+    if pix2pix:
+        ucfg = _pix2pix_unet_config(ucfg, img2img, inpaint, controlnet, tiny_vae)
     vcfg = dinit.TINY_VAE if tiny else dinit.SD_VAE
     idev = init_device or ("cpu" if tiny else str(device))
     unet, _ = build_unet(ucfg, seed=seed, device=device, init_device=idev)
-    vae = _vae_for(tiny_vae, tiny, dinit.TAESD, dinit.TINY_TAESD, vcfg, seed + 1, device, idev, with_encoder or img2img or inpaint)
+    vae = _vae_for(tiny_vae, tiny, dinit.TAESD, dinit.TINY_TAESD, vcfg, seed + 1, device, idev, with_encoder or img2img or inpaint or pix2pix)
     sch = _scheduler_for(scheduler, lambda: DDIMScheduler(**SD15_SCHEDULER))
     if controlnet:
         if img2img or inpaint:
             raise ValueError("controlnet= builds the text-to-image ControlNet pipeline (no ControlNet img2img / inpainting pipeline)")
         return StableDiffusionControlNetPipeline(vae=vae, unet=unet, scheduler=sch,
                                                  controlnet=_controlnet_for(ucfg, tiny, seed, device, idev, controlnet))
+    if pix2pix:
+        return StableDiffusionInstructPix2PixPipeline(vae=vae, unet=unet, scheduler=sch)
     cls = StableDiffusionInpaintPipeline if inpaint else StableDiffusionImg2ImgPipeline if img2img else StableDiffusionPipeline
     return cls(vae=vae, unet=unet, scheduler=sch)
 

@@ -1108,6 +1108,28 @@ def cfg_rescale(eps2b: torch.Tensor, guidance: float, guidance_rescale: float, o
     return out
 
 
+def cfg_combine3(eps3b: torch.Tensor, guidance: float, image_guidance: float, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """InstructPix2Pix's three-way guidance in one launch (``da_cfg_rescale`` with ``DA_CFG_IMAGE_GUIDANCE``): eps3b [3B][...] =
+    (text, image, uncond) -> [B][...] ``uncond + guidance * (text - image) + image_guidance * (image - uncond)``, every op rounded
+    in the tensor dtype in Python's evaluation order of that expression (pipeline_stable_diffusion_instruct_pix2pix.py).  The
+    scheduler step then runs with ``cfg=False`` on the result."""
+    _req(eps3b, "model_output", None)
+    if eps3b.dtype not in (bf16, torch.float32) or eps3b.dim() < 1 or eps3b.shape[0] % 3 or eps3b.numel() == 0 or not eps3b.is_contiguous():
+        raise ValueError("cfg_combine3: contiguous bf16 / fp32 model output of a batch of 3 B rows (text, image, uncond)")
+    B = eps3b.shape[0] // 3
+    n_per = eps3b[0].numel()
+    shape = (B,) + tuple(eps3b.shape[1:])
+    if out is None:
+        out = torch.empty(shape, device=eps3b.device, dtype=eps3b.dtype)
+    else:
+        _req(out, "out", eps3b.dtype)
+        if tuple(out.shape) != shape or not out.is_contiguous():
+            raise ValueError(f"cfg_combine3: out must be a contiguous {shape} tensor, got {tuple(out.shape)}")
+    L.check(L.load().da_cfg_rescale(eps3b.data_ptr(), out.data_ptr(), None, B, n_per, float(guidance), float(image_guidance),
+                                    _dt(eps3b) | L.CFG_IMAGE_GUIDANCE, _stream()), "da_cfg_rescale")
+    return out
+
+
 def cast_f32_bf16(x: torch.Tensor, rep: int = 1) -> torch.Tensor:
     """fp32 -> bf16, replicated ``rep`` times along the batch dim."""
     _req(x, "x", torch.float32)
@@ -1321,6 +1343,40 @@ def conv_in_inpaint(x: torch.Tensor, mask: torch.Tensor, masked: torch.Tensor, w
     Cout = w.shape[0]
     y = torch.empty((rep * B, H, W_, Cout), device=x.device, dtype=bf16)
     L.check(L.load().da_conv_in_inpaint(x.data_ptr(), mask.data_ptr(), masked.data_ptr(), w.data_ptr(), _ptr(bias), y.data_ptr(),
+                                        _ptr(table), _ptr(step_idx), B, H, W_, Cout, rep, Bm, _stream()), "da_conv_in_inpaint")
+    return y
+
+
+def conv_in_pix2pix(x: torch.Tensor, image_latents: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor], *,
+                    table: Optional[torch.Tensor] = None, step_idx: Optional[torch.Tensor] = None, rep: int = 1) -> torch.Tensor:
+    """conv_in of an 8-channel InstructPix2Pix U-Net from its two sources (``da_conv_in_inpaint`` with a NULL mask): equals
+    ``conv_thin_in(cat([cat([s(x)] * rep), cat([img, img, zeros_like(img)][:rep])], dim=1), w, bias, ksize=3, in_nchw=True)`` bit for
+    bit, with s = euler_scale_model_input when ``table`` / ``step_idx`` are given.  x: [B][4][H][W]; image_latents [Bm][4][H][W],
+    Bm in {1, B}; w: [Cout][72]; rep 1, or 3 for the (text, image, uncond) rows; returns NHWC [rep * B][H][W][Cout]."""
+    _req(x, "x"), _req(image_latents, "image_latents"), _req(w, "w")
+    if x.dim() != 4 or x.shape[1] != 4:
+        raise ValueError(f"conv_in_pix2pix: latents must be (B, 4, H, W), got {tuple(x.shape)}")
+    B, _, H, W_ = x.shape
+    Bm = image_latents.shape[0]
+    if Bm not in (1, B) or tuple(image_latents.shape) != (Bm, 4, H, W_):
+        raise ValueError(f"conv_in_pix2pix: image_latents {tuple(image_latents.shape)} must be (Bm, 4, {H}, {W_}) with Bm = 1 or {B}")
+    if not (x.is_contiguous() and image_latents.is_contiguous() and w.is_contiguous()):
+        raise ValueError("conv_in_pix2pix: contiguous tensors required")
+    if w.dim() != 2 or w.shape[1] != 72:
+        raise ValueError(f"conv_in_pix2pix: an 8 -> Cout 3x3 weight [Cout][72] is required, got {tuple(w.shape)}")
+    if rep not in (1, 3):
+        raise ValueError("conv_in_pix2pix: rep must be 1 or 3")
+    if (table is None) != (step_idx is None):
+        raise ValueError("conv_in_pix2pix: pass `table` and `step_idx` together")
+    if table is not None:
+        _req(table, "table", torch.float32), _req(step_idx, "step_idx", torch.int32)
+    if bias is not None:
+        _req(bias, "bias")
+        if bias.data_ptr() % 16 or bias.numel() != w.shape[0] or not bias.is_contiguous():
+            raise ValueError("conv_in_pix2pix: bias must be a contiguous, 16-byte aligned [Cout] tensor")
+    Cout = w.shape[0]
+    y = torch.empty((rep * B, H, W_, Cout), device=x.device, dtype=bf16)
+    L.check(L.load().da_conv_in_inpaint(x.data_ptr(), None, image_latents.data_ptr(), w.data_ptr(), _ptr(bias), y.data_ptr(),
                                         _ptr(table), _ptr(step_idx), B, H, W_, Cout, rep, Bm, _stream()), "da_conv_in_inpaint")
     return y
 

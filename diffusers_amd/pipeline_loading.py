@@ -71,7 +71,7 @@ class PipelineLoadingMixin:
                 if isinstance(spec, (list, tuple)) and slot not in _DROPPED and spec[0] is not None:
                     raise ValueError(f"{cls.__name__} has no component slot {slot!r} ({spec})")
                 continue
-            if not isinstance(spec, (list, tuple)):            # a plain config value (force_zeros_for_empty_prompt, ...)
+            if not isinstance(spec, (list, tuple)):            # a plain config value (force_zeros_for_empty_prompt, is_cosxl_edit, ...)
                 kwargs[slot] = spec
                 continue
             library, class_name = spec

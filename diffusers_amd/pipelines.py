@@ -420,9 +420,7 @@ class _LatentDiffusionBase(_StepCallbacks, _CapturedStepLoop, PipelineLoadingMix
         eps = self._predict_noise(latents, cond, do_cfg)
         # in place (same buffer every replay); without CFG (guidance_scale <= 1, pipeline_stable_diffusion_xl.py:1202,
         # :1223) the U-Net ran on the un-doubled batch and the same kernel skips the combine
-        kw = {"eta": self._eta, "noise_table": self._noise_table} if self._eta > 0 else {}
-        if getattr(sch, "needs_step_noise", False):
-            kw = {"noise_table": self._noise_table}
+        kw = self._step_noise_kw()
         if do_cfg and self._guidance_rescale > 0.0:
             # pipeline_stable_diffusion_xl.py:1227-1229 / pipeline_stable_diffusion.py:1057-1059: combine, then rescale_noise_cfg
             # (per-sample std of the text and of the guided prediction: two small launches), then the step without its combine
@@ -431,6 +429,12 @@ class _LatentDiffusionBase(_StepCallbacks, _CapturedStepLoop, PipelineLoadingMix
             return latents
         sch.step_cfg(eps, latents, guidance_scale, out=latents, cfg=do_cfg, **kw)
         return latents
+
+    def _step_noise_kw(self) -> dict:
+        """What the fused step takes besides the prediction: DDIM's eta and its noise table, or a stochastic sampler's table."""
+        if getattr(self.scheduler, "needs_step_noise", False):
+            return {"noise_table": self._noise_table}
+        return {"eta": self._eta, "noise_table": self._noise_table} if self._eta > 0 else {}
 
     def _draw_step_noise(self, latents, generator, num_inference_steps: int, n_steps: int, begin: int = 0):
         """A stochastic sampler (``scheduler.needs_step_noise``) adds fresh noise in every step; the reference draws it inside
@@ -547,13 +551,16 @@ class _LatentDiffusionBase(_StepCallbacks, _CapturedStepLoop, PipelineLoadingMix
         else:
             self.scheduler.set_timesteps(device=self.device, **custom)
 
+    def _num_channels_latents(self) -> int:
+        return self.unet.config.in_channels
+
     def _noise_latents(self, latents, generator, batch: int, height: int, width: int):
         """prepare_latents of the txt2img pipelines.  The noise is drawn with a plain ``torch.randn`` on the generator's device,
         on the CPU without one -- NOT with ``_randn``, which draws on the target device without a generator and takes generator
         lists: seeded results depend on it.  (Like the reference's prepare_latents, user-supplied latents are taken as they are:
         no shape check, pipeline_stable_diffusion_xl.py:707-727.)"""
         if latents is None:
-            shape = (batch, self.unet.config.in_channels, height // self.vae_scale_factor, width // self.vae_scale_factor)
+            shape = (batch, self._num_channels_latents(), height // self.vae_scale_factor, width // self.vae_scale_factor)
             gdev = generator.device if generator is not None else torch.device("cpu")
             latents = torch.randn(shape, generator=generator, device=gdev, dtype=bf16)
         latents = latents.to(device=self.device, dtype=bf16).contiguous()
@@ -1324,6 +1331,201 @@ class StableDiffusionXLInpaintPipeline(_InpaintMixin, StableDiffusionXLImg2ImgPi
                                 guidance_rescale, original_size, crops_coords_top_left, target_size, negative_original_size,
                                 negative_crops_coords_top_left, negative_target_size, aesthetic_score, negative_aesthetic_score,
                                 clip_skip, callback_on_step_end, callback_on_step_end_tensor_inputs, use_graph)
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# InstructPix2Pix (pipeline_stable_diffusion_instruct_pix2pix.py, pipeline_stable_diffusion_xl_instruct_pix2pix.py)
+# ----------------------------------------------------------------------------------------------------------------------
+class _InstructPix2PixMixin:
+    """Instruction-based image editing on top of the text-to-image pipelines (timbrooks/instruct-pix2pix; SDXL-edit, CosXL-edit): an
+    8-channel U-Net reads the latents and the UNSCALED mode of the image's posterior, and guidance runs over a batch of three --
+    (text, image, unconditional), the last with a zero image -- with two scales.  The reference builds ``torch.cat([latents] * 3)``,
+    ``scale_model_input``, ``torch.cat([., image_latents], dim=1)`` and a five-op combine every step; here conv_in reads its two
+    sources in place and stores the three rows (ops.conv_in_pix2pix: the scale and the tripling folded in, the two rows with equal
+    inputs from one computation), and ONE launch combines (ops.cfg_combine3) in front of the scheduler's fused step, which runs
+    without its own combine.  Not done here: resizing ``image`` (it sets the output size), ``guidance_rescale``, a ControlNet or an
+    IP-Adapter next to it, and the Euler sigma work-around of early reference versions (prediction -> x0 -> prediction around the
+    combine, which current versions dropped)."""
+
+    _pix2pix = None                 # static input of the captured step: {"image_latents"}
+    _image_guidance_scale = 1.5
+    _scales_image_latents = False   # SDXL with is_cosxl_edit: image latents * vae.config.scaling_factor
+
+    def _check_pix2pix_components(self, controlnet=None):
+        if controlnet is not None:
+            raise NotImplementedError(f"{type(self).__name__}: a ControlNet next to InstructPix2Pix is not implemented by the engine "
+                                      "pipelines (`controlnet` must be None)")
+
+    def _arm_pix2pix(self, guidance_scale, image_guidance_scale, guidance_rescale, ip_adapter_image, ip_adapter_image_embeds,
+                     padding_mask_crop, callback_on_step_end, callback_on_step_end_tensor_inputs) -> bool:
+        """The refusals of a call and what every call sets first; returns ``do_cfg``: the reference's
+        ``guidance_scale > 1.0 and image_guidance_scale >= 1.0`` -- otherwise the batch is not tripled and nothing is combined."""
+        who = type(self).__name__
+        _refuse_tiny_vae(self.vae, who)
+        if ip_adapter_image is not None or ip_adapter_image_embeds is not None:
+            raise NotImplementedError("`ip_adapter_image` / `ip_adapter_image_embeds`: IP-Adapter is outside this engine")
+        if padding_mask_crop is not None:
+            raise NotImplementedError("`padding_mask_crop` (crop, resize and paste-back) is not implemented by the engine pipelines")
+        if guidance_rescale and float(guidance_rescale) > 0.0:
+            raise NotImplementedError(f"{who}: `guidance_rescale` > 0 is not implemented for the three-way guidance (the "
+                                      "text-to-image, img2img and inpainting pipelines have it)")
+        if _time_cond_dim(self.unet) is not None:
+            raise NotImplementedError(f"{who}: a U-Net with `time_cond_proj_dim` (guidance-scale embedding of the distilled LCM "
+                                      "checkpoints) has no InstructPix2Pix checkpoint and no engine path here")
+        self._arm(guidance_scale, 0.0, callback_on_step_end, callback_on_step_end_tensor_inputs)
+        self._image_guidance_scale = float(image_guidance_scale)
+        return guidance_scale > 1.0 and image_guidance_scale >= 1.0
+
+    def _prepare_image_latents(self, image, height, width, batch: int):
+        """prepare_image_latents: the MODE of ``vae.encode(image)`` -- no generator draw, and not multiplied by the VAE's
+        scaling_factor (but for ``is_cosxl_edit``) -- or ``image`` itself when it already has the latents' channel count; one image is
+        broadcast by the kernel, several are repeated to the batch.  Kept across calls in ``self._pix2pix`` (refreshed in place while
+        the shape stays: a captured step keeps reading the same buffer).  The zero image of the unconditional row is never stored."""
+        if image is None:
+            raise ValueError("`image` input cannot be undefined.")
+        vc = self.vae.config
+        if vc.get("latents_mean") is not None or vc.get("latents_std") is not None:
+            raise NotImplementedError("AutoencoderKL configs with latents_mean / latents_std are not supported by the engine pipelines")
+        dev, f = self.device, self.vae_scale_factor
+        prep = prepare_image(image, f, vc.latent_channels, dev)
+        if prep[0] == "latents":
+            il = prep[1].clone()
+        else:
+            _, img, nchw, normalize = prep
+            il = self.vae.encode_image(img, nchw=nchw, normalize=normalize).mode()
+            if self._scales_image_latents:
+                il = (il * float(vc.scaling_factor)).to(bf16)
+        n_lat, n_img, nu = vc.latent_channels, il.shape[1], self.unet.config.in_channels
+        if n_lat + n_img != nu:
+            raise ValueError(f"Incorrect configuration settings! The config of `pipeline.unet`: {self.unet.config} expects {nu} but "
+                             f"received `num_channels_latents`: {n_lat} + `num_channels_image`: {n_img}  = {n_lat + n_img}. Please "
+                             "verify the config of `pipeline.unet` or your `image` input.")
+        if n_lat != 4:
+            raise NotImplementedError("the InstructPix2Pix engine pipelines run 4-channel latents (the SD / SDXL VAE)")
+        H, W_ = il.shape[-2] * f, il.shape[-1] * f
+        if (height is not None and height != H) or (width is not None and width != W_):
+            raise ValueError(f"`height` x `width` = {height} x {width} but `image` is {H} x {W_} (the engine does not resize)")
+        n = il.shape[0]
+        if n != 1:
+            if batch % n:
+                raise ValueError(f"Cannot duplicate `image` of batch size {n} to {batch} text prompts.")
+            il = torch.cat([il] * (batch // n), 0)
+        self._pix2pix = _adopt_or_refresh(self._pix2pix, {"image_latents": il.contiguous()})
+        return H, W_
+
+    def _num_channels_latents(self) -> int:
+        return self.vae.config.latent_channels      # (the U-Net's in_channels count the image latents as well)
+
+    # ---- the captured step -------------------------------------------------------------------------------------
+    def _predict_noise(self, latents, cond, do_cfg):
+        """conv_in from (latents, image latents) with scale_model_input and the x3 folded in, then the U-Net: the row count comes
+        from the conditioning batch."""
+        sch = self.scheduler
+        euler = sch.scales_model_input
+        if euler:
+            if sch._step_index is None:
+                sch._init_step_index(sch.timesteps[0])
+            sch.is_scale_input_called = True
+        return self.unet(latents, None, None, conditioning=cond, sampler_table=sch.device_table, step_idx=sch.device_step,
+                         image_cond=self._pix2pix["image_latents"], scale_model_input=euler, return_dict=False)[0]
+
+    def _step(self, latents, cond, guidance_scale, do_cfg):
+        eps = self._predict_noise(latents, cond, do_cfg)
+        if do_cfg:
+            eps = ops.cfg_combine3(eps, guidance_scale, self._image_guidance_scale)
+        self.scheduler.step_cfg(eps, latents, guidance_scale, out=latents, cfg=False, **self._step_noise_kw())
+        return latents
+
+    def _make_graph_key(self, latents, cond, guidance_scale, do_cfg):
+        il = self._pix2pix["image_latents"]
+        return super()._make_graph_key(latents, cond, guidance_scale, do_cfg) + (
+            float(self._image_guidance_scale), ("image_latents", il.data_ptr(), tuple(il.shape)))
+
+
+class StableDiffusionInstructPix2PixPipeline(_InstructPix2PixMixin, StableDiffusionPipeline):
+    """pipeline_stable_diffusion_instruct_pix2pix.py on the engine (see _InstructPix2PixMixin); any SD scheduler of the engine."""
+
+    def __init__(self, vae, unet, scheduler, text_encoder=None, tokenizer=None, safety_checker=None, feature_extractor=None,
+                 image_encoder=None, requires_safety_checker: bool = False, controlnet=None):
+        self._check_pix2pix_components(controlnet)
+        super().__init__(vae, unet, scheduler, text_encoder, tokenizer, safety_checker, feature_extractor, requires_safety_checker)
+
+    def _conditioning_inputs(self, prompt_embeds, negative_prompt_embeds, do_cfg):
+        """_encode_prompt's ``torch.cat([prompt_embeds, negative_prompt_embeds, negative_prompt_embeds])``: the image row and the
+        unconditional row both read the negative prompt."""
+        pe = prompt_embeds.to(device=self.device, dtype=bf16)
+        if do_cfg:
+            npe = negative_prompt_embeds.to(device=self.device, dtype=bf16)
+            pe = torch.cat([pe, npe, npe], dim=0)
+        return pe.contiguous(), None
+
+    @torch.no_grad()
+    def __call__(self, prompt=None, image=None, num_inference_steps: int = 100, guidance_scale: float = 7.5,
+                 image_guidance_scale: float = 1.5, negative_prompt=None, num_images_per_prompt: int = 1, eta: float = 0.0,
+                 generator=None, latents: Optional[torch.Tensor] = None, prompt_embeds=None, negative_prompt_embeds=None,
+                 ip_adapter_image=None, ip_adapter_image_embeds=None, output_type: str = "pt", return_dict: bool = True,
+                 callback_on_step_end=None, callback_on_step_end_tensor_inputs=None, clip_skip=None, height: Optional[int] = None,
+                 width: Optional[int] = None, padding_mask_crop=None, guidance_rescale: float = 0.0, use_graph: bool = True):
+        do_cfg = self._arm_pix2pix(guidance_scale, image_guidance_scale, guidance_rescale, ip_adapter_image, ip_adapter_image_embeds,
+                                   padding_mask_crop, callback_on_step_end, callback_on_step_end_tensor_inputs)
+        embeds = self._prompt_inputs(prompt, negative_prompt, num_images_per_prompt, prompt_embeds, negative_prompt_embeds, clip_skip,
+                                     do_cfg)
+        self._set_schedule(num_inference_steps, None, None)
+        height, width = self._prepare_image_latents(image, height, width, embeds[0].shape[0])
+        latents = self._noise_latents(latents, generator, embeds[0].shape[0], height, width)
+        cond = self._conditioning(*embeds, do_cfg)
+        if eta > 0 and not self.scheduler.takes_eta:
+            raise ValueError("eta > 0 is a DDIMScheduler option")
+        return self._finish(latents, generator, cond, guidance_scale, do_cfg, len(self.scheduler.timesteps), 0, use_graph,
+                            output_type, return_dict, eta)
+
+
+class StableDiffusionXLInstructPix2PixPipeline(_InstructPix2PixMixin, StableDiffusionXLPipeline):
+    """pipeline_stable_diffusion_xl_instruct_pix2pix.py on the engine (see _InstructPix2PixMixin).  ``is_cosxl_edit``: the CosXL-edit
+    checkpoints take the image latents multiplied by the VAE's scaling_factor; ``denoising_end`` as in the text-to-image pipeline."""
+
+    def __init__(self, vae, unet, scheduler, text_encoder=None, text_encoder_2=None, tokenizer=None, tokenizer_2=None,
+                 force_zeros_for_empty_prompt: bool = True, add_watermarker=None, is_cosxl_edit: bool = False, controlnet=None):
+        self._check_pix2pix_components(controlnet)
+        super().__init__(vae, unet, scheduler, text_encoder, text_encoder_2, tokenizer, tokenizer_2, force_zeros_for_empty_prompt)
+        self.is_cosxl_edit = self._scales_image_latents = bool(is_cosxl_edit)
+
+    def _conditioning_inputs(self, prompt_embeds, negative_prompt_embeds, pooled_prompt_embeds, negative_pooled_prompt_embeds, ids,
+                             neg_ids, do_cfg):
+        """The reference's ``torch.cat([prompt_embeds, negative_prompt_embeds, negative_prompt_embeds])``, the pooled embeddings
+        alike, and ``torch.cat([add_time_ids] * 3)``."""
+        dev = self.device
+        pe = prompt_embeds.to(device=dev, dtype=bf16)
+        te = pooled_prompt_embeds.to(device=dev, dtype=bf16)
+        ids = ids.to(dev).repeat(pe.shape[0], 1)
+        if do_cfg:
+            npe, nte = (t.to(device=dev, dtype=bf16) for t in (negative_prompt_embeds, negative_pooled_prompt_embeds))
+            pe, te, ids = torch.cat([pe, npe, npe], dim=0), torch.cat([te, nte, nte], dim=0), torch.cat([ids, ids, ids], dim=0)
+        return pe.contiguous(), {"text_embeds": te, "time_ids": ids}
+
+    @torch.no_grad()
+    def __call__(self, prompt=None, prompt_2=None, image=None, height: Optional[int] = None, width: Optional[int] = None,
+                 num_inference_steps: int = 100, denoising_end: Optional[float] = None, guidance_scale: float = 5.0,
+                 image_guidance_scale: float = 1.5, negative_prompt=None, negative_prompt_2=None, num_images_per_prompt: int = 1,
+                 eta: float = 0.0, generator=None, latents: Optional[torch.Tensor] = None, prompt_embeds=None,
+                 negative_prompt_embeds=None, pooled_prompt_embeds=None, negative_pooled_prompt_embeds=None,
+                 ip_adapter_image=None, ip_adapter_image_embeds=None, output_type: str = "pt", return_dict: bool = True,
+                 guidance_rescale: float = 0.0, original_size: Optional[Tuple[int, int]] = None,
+                 crops_coords_top_left: Tuple[int, int] = (0, 0), target_size: Optional[Tuple[int, int]] = None,
+                 clip_skip=None, callback_on_step_end=None, callback_on_step_end_tensor_inputs=None, padding_mask_crop=None,
+                 use_graph: bool = True):
+        do_cfg = self._arm_pix2pix(guidance_scale, image_guidance_scale, guidance_rescale, ip_adapter_image, ip_adapter_image_embeds,
+                                   padding_mask_crop, callback_on_step_end, callback_on_step_end_tensor_inputs)
+        embeds = self._prompt_inputs(prompt, prompt_2, negative_prompt, negative_prompt_2, num_images_per_prompt, prompt_embeds,
+                                     negative_prompt_embeds, pooled_prompt_embeds, negative_pooled_prompt_embeds, clip_skip, do_cfg)
+        self._set_schedule(num_inference_steps, None, None)
+        height, width = self._prepare_image_latents(image, height, width, embeds[0].shape[0])
+        latents = self._noise_latents(latents, generator, embeds[0].shape[0], height, width)
+        ids = self._get_add_time_ids(original_size or (height, width), tuple(crops_coords_top_left), target_size or (height, width),
+                                     embeds[2].shape[-1])
+        cond = self._conditioning(*embeds, ids, ids, do_cfg)
+        return self._finish(latents, generator, cond, guidance_scale, do_cfg, denoising_end_steps(self.scheduler, denoising_end), 0,
+                            use_graph, output_type, return_dict, eta)
 
 
 # ----------------------------------------------------------------------------------------------------------------------

@@ -296,7 +296,7 @@ class UNet2DConditionModel(PretrainedMixin):
                 down_block_additional_residuals=None, mid_block_additional_residual=None,
                 down_intrablock_additional_residuals=None, encoder_attention_mask=None, return_dict: bool = True,
                 conditioning: Optional[Dict[str, Any]] = None, sampler_table=None, step_idx=None, inpaint_cond=None,
-                scale_model_input: bool = False, controlnet_handoff=None):
+                scale_model_input: bool = False, controlnet_handoff=None, image_cond=None):
         """Same signature as the reference forward (unet_2d_condition.py:979-994) plus engine extensions:
         ``conditioning`` (result of :meth:`precompute_conditioning`), ``sampler_table``/``step_idx`` (read the
         timestep from the device-resident sampler table so the call is HIP-graph replayable) and, for a 9-channel inpainting
@@ -304,7 +304,11 @@ class UNet2DConditionModel(PretrainedMixin):
         its nine input channels from the three tensors (ops.conv_in_inpaint; the CFG halves are stored from one computation, their
         count taken from the conditioning batch).  ``scale_model_input`` (with ``inpaint_cond`` and ``sampler_table``) applies the
         Euler scheduler's ``scale_model_input`` to the latents inside that conv.  Without ``inpaint_cond`` a 9-channel ``sample``
-        goes through the ordinary conv_in.  ``controlnet_handoff``: a callable ``f(skips, mid)`` that adds a ControlNet's residuals
+        goes through the ordinary conv_in.  ``image_cond=image_latents`` is the same for an 8-channel InstructPix2Pix U-Net
+        (ops.conv_in_pix2pix): ``sample`` is the 4-channel latents, channels 4-7 come from the image latents, and a conditioning batch
+        of three times the latents' selects the (text, image, uncond) rows, the last with a zero image, as the reference's
+        ``cat([image_latents, image_latents, zeros_like(image_latents)])`` builds them; it honours ``scale_model_input`` and is not
+        combined with ``inpaint_cond``.  An 8-channel ``sample`` without it goes through the ordinary conv_in.  ``controlnet_handoff``: a callable ``f(skips, mid)`` that adds a ControlNet's residuals
         with the engine's own launches (``ControlNetModel.handoff_``): called once, after the mid block, with the channels-last skip
         list of the down blocks and the mid block's output, it updates those tensors IN PLACE -- no torch op, so the step stays
         recordable as a strict launch plan.  Not together with the two reference residual arguments.
@@ -349,7 +353,19 @@ class UNet2DConditionModel(PretrainedMixin):
         if c.time_cond_proj_dim is not None and conditioning.get("timestep_cond") is None:
             raise ValueError(f"this U-Net has time_cond_proj_dim={c.time_cond_proj_dim}: `timestep_cond` is required "
                              "(forward(timestep_cond=) or precompute_conditioning(timestep_cond=))")
-        if inpaint_cond is not None:
+        if image_cond is not None:
+            if inpaint_cond is not None:
+                raise ValueError("`image_cond` (InstructPix2Pix, 8 input channels) and `inpaint_cond` (inpainting, 9) exclude each other")
+            if c.in_channels != 8 or Cin != 4:
+                raise ValueError(f"`image_cond` is for a U-Net with 8 input channels fed 4-channel latents (this one has "
+                                 f"{c.in_channels}, `sample` has {Cin})")
+            if scale_model_input and sampler_table is None:
+                raise ValueError("`scale_model_input` reads the sampler table: pass `sampler_table` / `step_idx`")
+            rep = conditioning["batch"] // B
+            if rep not in (1, 3) or rep * B != conditioning["batch"]:
+                raise ValueError("conditioning batch must be the latents' batch, or three times it (text, image, unconditional)")
+            B = rep * B
+        elif inpaint_cond is not None:
             if c.in_channels != 9 or Cin != 4:
                 raise ValueError(f"`inpaint_cond` is for a U-Net with 9 input channels fed 4-channel latents (this one has "
                                  f"{c.in_channels}, `sample` has {Cin})")
@@ -360,7 +376,7 @@ class UNet2DConditionModel(PretrainedMixin):
                 raise ValueError("conditioning batch must be the latents' batch, or twice it (classifier-free guidance)")
             B = rep * B
         elif scale_model_input:
-            raise ValueError("`scale_model_input` is an option of `inpaint_cond`")
+            raise ValueError("`scale_model_input` is an option of `inpaint_cond` / `image_cond`")
         if conditioning["batch"] != B:
             raise ValueError("conditioning batch does not match sample batch")
         kvs = conditioning["kvs"]
@@ -384,7 +400,11 @@ class UNet2DConditionModel(PretrainedMixin):
         emb = self.time_proj(emb)                    # the resnets below take their columns of this
 
         # 2. conv_in: NCHW -> channels-last
-        if inpaint_cond is not None:
+        if image_cond is not None:
+            x = ops.conv_in_pix2pix(sample.contiguous(), image_cond, self.conv_in_w, self.conv_in_b,
+                                    table=sampler_table if scale_model_input else None,
+                                    step_idx=step_idx if scale_model_input else None, rep=rep)
+        elif inpaint_cond is not None:
             x = ops.conv_in_inpaint(sample.contiguous(), inpaint_cond[0], inpaint_cond[1], self.conv_in_w, self.conv_in_b,
                                     table=sampler_table if scale_model_input else None,
                                     step_idx=step_idx if scale_model_input else None, rep=rep)

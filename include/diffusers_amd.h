@@ -447,6 +447,8 @@ int da_rmsnorm_channels_bf16(const void* x, const void* gamma, void* y, long lon
  * ------------------------------------------------------------------------------------------------------------------ */
 #define DA_DTYPE_BF16 0
 #define DA_DTYPE_F32 1
+/* OR-ed into da_cfg_rescale's `dtype`: three-way (text, image, uncond) InstructPix2Pix guidance instead of rescale_noise_cfg */
+#define DA_CFG_IMAGE_GUIDANCE 0x100
 #define DA_PRED_EPSILON 0
 #define DA_PRED_V 1
 #define DA_PRED_SAMPLE 2
@@ -499,7 +501,12 @@ int da_inpaint_blend(void* latents, const void* image_latents, const void* noise
 /* rescale_noise_cfg (pipelines/stable_diffusion/pipeline_stable_diffusion.py:69-92; SDXL :1227-1229, SD :1057-1059): eps
  * [2][B][n_per] = (uncond, cond) -> out [B][n_per] = guidance_rescale * (cfg * std(text) / std(cfg)) + (1 - guidance_rescale) * cfg
  * with cfg = uncond + guidance * (cond - uncond), every torch op rounded in the tensor dtype; ratio_ws: B floats of scratch.
- * The step kernels then run with cfg = 0 on `out`. */
+ * The step kernels then run with cfg = 0 on `out`.
+ * dtype | DA_CFG_IMAGE_GUIDANCE: InstructPix2Pix's guidance (pipeline_stable_diffusion_instruct_pix2pix.py, the same expression in
+ * pipeline_stable_diffusion_xl_instruct_pix2pix.py) in ONE launch.  eps [3][B][n_per] = (text, image, uncond), the argument in
+ * guidance_rescale's place carries image_guidance_scale (ig), ratio_ws may be NULL, n_per >= 1:
+ *   out = rnd(rnd(uncond + rnd(guidance * rnd(text - image))) + rnd(ig * rnd(image - uncond)))
+ * every op rounded in the tensor dtype, in Python's evaluation order of the reference's expression: bit-identical to it. */
 int da_cfg_rescale(const void* eps, void* out, float* ratio_ws, int B, long long n_per, float guidance, float guidance_rescale,
                    int dtype, void* stream);
 /* out[r][:] = bf16(x) for r < rep: latents.to(transformer_dtype) (pipeline_wan.py:600) + CFG batch doubling */
@@ -566,7 +573,13 @@ int da_conv_thin_out_bf16(const void* x, const void* w, const void* bias, void* 
  * in, NHWC out, w [Cout][81]) on cat([s(x)] * rep, [mask] * rep, [masked] * rep, dim=1), bit for bit.  x: bf16 [B][4][H][W] (the un-doubled
  * latents), mask [Bm][1][H][W], masked [Bm][4][H][W], Bm in {1, B}; s(x) = bf16(x / table[*step_idx][3]) (da_euler_scale_model_input)
  * when table != NULL, else x; rep in {1, 2}: y [rep * B][H][W][Cout], the CFG halves computed once and stored twice.  bias NULL or
- * 16-byte aligned, Cout % 8 == 0. */
+ * 16-byte aligned, Cout % 8 == 0.
+ * mask == NULL: the 8-channel conv_in of an InstructPix2Pix U-Net (timbrooks/instruct-pix2pix, SDXL-edit / CosXL-edit) from its two
+ * sources: channels 0-3 from x as above, channels 4-7 from masked [Bm][4][H][W] (here the image latents), w [Cout][72].  rep in {1, 3}.
+ * rep == 3: y [3 B][H][W][Cout] in the (text, image, uncond) row order of the reference's
+ * cat([cat([s(x)] * 3), cat([image_latents, image_latents, zeros_like(image_latents)])], dim=1): copies 0 and 1 are stored from one
+ * computation, copy 2 is the convolution with channels 4-7 equal to zero (a second accumulator set in the same pass).  Bit for bit
+ * da_conv_thin_in_bf16 (Cin = 8) on that tensor.  mask != NULL with rep == 3, mask == NULL with rep == 2: DA_ERR_INVALID. */
 int da_conv_in_inpaint(const void* x, const void* mask, const void* masked, const void* w, const void* bias, void* y,
                        const float* table, const int* step_idx, int B, int H, int W, int Cout, int rep, int Bm, void* stream);
 
