@@ -14,6 +14,11 @@
 // torch op; 0-d fp32 scalars promote nothing), so results are bit-identical to the reference for identical inputs.
 // Per-step scalars live in a device table (8 floats per step) indexed by a device-resident step counter, so a whole
 // denoising step can be captured once in a HIP graph and replayed for every step.
+//
+// Every kernel but the statistics pass is elementwise and is put together from the shared pieces below: its loop from
+// EW_EACH / EW_EACH4 + EW_TAIL, its guided model output from load_eps / LOAD_EPS4, its x0 from x0_alpha_beta / x0_sigma, and its
+// entry point picks the instantiation with dispatch_dtype / dispatch_step and sizes a 4-wide launch with vec_split.
+#include <type_traits>
 #include "common.cuh"
 
 namespace {
@@ -33,6 +38,49 @@ struct IO<float> {
   static __device__ __forceinline__ float rnd(float v) { return v; }
 };
 
+template <typename T>
+struct Vec4;
+template <>
+struct Vec4<uint16_t> {
+  static __device__ __forceinline__ void ld(const uint16_t* p, size_t i, float (&v)[4]) {
+    const uint2 r = *reinterpret_cast<const uint2*>(p + i);
+    v[0] = __uint_as_float(r.x << 16), v[1] = __uint_as_float(r.x & 0xffff0000u);
+    v[2] = __uint_as_float(r.y << 16), v[3] = __uint_as_float(r.y & 0xffff0000u);
+  }
+  static __device__ __forceinline__ void st(uint16_t* p, size_t i, const float (&v)[4]) {
+    uint2 r;
+    r.x = (uint32_t)f2bf(v[0]) | ((uint32_t)f2bf(v[1]) << 16);
+    r.y = (uint32_t)f2bf(v[2]) | ((uint32_t)f2bf(v[3]) << 16);
+    *reinterpret_cast<uint2*>(p + i) = r;
+  }
+};
+template <>
+struct Vec4<float> {
+  static __device__ __forceinline__ void ld(const float* p, size_t i, float (&v)[4]) {
+    const float4 r = *reinterpret_cast<const float4*>(p + i);
+    v[0] = r.x, v[1] = r.y, v[2] = r.z, v[3] = r.w;
+  }
+  static __device__ __forceinline__ void st(float* p, size_t i, const float (&v)[4]) {
+    *reinterpret_cast<float4*>(p + i) = make_float4(v[0], v[1], v[2], v[3]);
+  }
+};
+
+// The grid-stride loop of every elementwise kernel here, as a loop header in front of the kernel's own body: i = lo + W * thread,
+// stepping W * (threads of the grid), while i < hi -- W elements per thread per trip.  A macro, not a function that takes the body
+// as a lambda, because of the code hipcc generates: blockDim.x read in a device function goes through the partial-last-workgroup
+// path that a kernel body is spared, and with the body inlined from a callee the CFG instantiations address their loads with six
+// to eight more VGPRs (always_inline, [=] captures and indices passed in do not help).  Expanded in place the header gives the
+// code of a loop written out by hand.
+#define EW_SPAN(i, W, lo, hi)                                                             \
+  for (size_t i = (lo) + ((size_t)blockIdx.x * blockDim.x + threadIdx.x) * (W); i < (hi); \
+       i += (size_t)gridDim.x * blockDim.x * (W))
+// scalar form: one element per thread per trip over [0, n)
+#define EW_EACH(i, n) EW_SPAN(i, 1, 0, n)
+// "4-wide body + scalar tail" form: EW_EACH4's body takes elements [i, i + 4) of the leading n_vec (a multiple of 4, see
+// vec_split), EW_TAIL's body element i of the rest; both must run the same per-element arithmetic.
+#define EW_EACH4(i, n_vec) EW_SPAN(i, 4, 0, n_vec)
+#define EW_TAIL(i, n_vec, n) EW_SPAN(i, 1, n_vec, n)
+
 // noise_pred = uncond + g * (text - uncond), every op in the tensor dtype
 template <typename T>
 __device__ __forceinline__ float cfg_combine(float u, float c, float g) {
@@ -46,6 +94,53 @@ template <typename T, bool CFG>
 __device__ __forceinline__ float load_eps(const T* eps, size_t i, size_t n, float g) {
   if (CFG) return cfg_combine<T>(IO<T>::ld(eps, i), IO<T>::ld(eps, n + i), g);
   return IO<T>::ld(eps, i);
+}
+// the same for elements [i, i + 4) through 4-wide loads, into `float e[4]`.  A macro for the reason EW_SPAN is one: as a
+// function it changes the vector loops of the CFG instantiations of both kernels that use it (up to 8 more VGPRs).
+#define LOAD_EPS4(T, CFG, eps, i, n, g, e)                                                \
+  {                                                                                       \
+    if (CFG) {                                                                            \
+      float u[4], c[4];                                                                   \
+      Vec4<T>::ld(eps, i, u), Vec4<T>::ld(eps, (n) + (i), c);                             \
+      _Pragma("unroll") for (int j = 0; j < 4; ++j) e[j] = cfg_combine<T>(u[j], c[j], g); \
+    } else {                                                                              \
+      Vec4<T>::ld(eps, i, e);                                                             \
+    }                                                                                     \
+  }
+
+// element i of an n-element tensor, stored `rep` times along the batch (torch.cat([x] * rep) fused)
+template <typename T>
+__device__ __forceinline__ void store_rep(T* out, size_t i, size_t n, int rep, float v) {
+  for (int r = 0; r < rep; ++r) IO<T>::st(out, (size_t)r * n + i, v);
+}
+
+// pred_original_sample of the alpha / beta schedulers (DDIM, DDPM, LCM) from cb = sqrt(beta_t), ca = sqrt(alpha_t), the model
+// output e and the sample s, every op rounded in the tensor dtype.  PRED: 0 epsilon, 1 v_prediction, 2 sample
+//   PRED 0   x0 = (s - cb * e) / ca        PRED 1   x0 = ca * s - cb * e        PRED 2   x0 = e
+// (scheduling_ddim.py:455-468, scheduling_ddpm.py:505-517, scheduling_lcm.py step())
+template <typename T, int PRED>
+__device__ __forceinline__ float x0_alpha_beta(float cb, float ca, float e, float s) {
+  if (PRED == 0) {
+    float x0 = IO<T>::rnd(__fmul_rn(cb, e));
+    x0 = IO<T>::rnd(__fsub_rn(s, x0));
+    return IO<T>::rnd(__fdiv_rn(x0, ca));
+  }
+  if (PRED == 1) return IO<T>::rnd(__fsub_rn(IO<T>::rnd(__fmul_rn(ca, s)), IO<T>::rnd(__fmul_rn(cb, e))));
+  return e;
+}
+
+// pred_original_sample (fp32) of the sigma schedulers (Euler, Euler ancestral); PRED as above
+// (scheduling_euler_discrete.py:760-775)
+struct EulerCoef {
+  float sigma, dt, c_out, s2p1;
+};
+
+template <typename T, int PRED>
+__device__ __forceinline__ float x0_sigma(const EulerCoef& k, float e, float s) {
+  if (PRED == 0) return __fsub_rn(s, IO<T>::rnd(__fmul_rn(k.sigma, e)));  // sample - sigma_hat * model_output  (model dtype)
+  // model_output * (-sigma / sqrt(sigma^2+1)) (model dtype) + sample / (sigma^2+1) (fp32)
+  if (PRED == 1) return __fadd_rn(IO<T>::rnd(__fmul_rn(e, k.c_out)), __fdiv_rn(s, k.s2p1));
+  return e;
 }
 
 // rescale_noise_cfg (pipelines/stable_diffusion/pipeline_stable_diffusion.py:69-92), used when guidance_rescale > 0:
@@ -91,7 +186,7 @@ __global__ __launch_bounds__(1024) void cfg_rescale_stats_kernel(const T* __rest
 template <typename T>
 __global__ void cfg_rescale_apply_kernel(const T* __restrict__ eps, T* __restrict__ out, const float* __restrict__ ratio,
                                          float g, float gr, float one_minus_gr, size_t n_per, size_t n) {
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+  EW_EACH(i, n) {
     const float cv = cfg_combine<T>(IO<T>::ld(eps, i), IO<T>::ld(eps, n + i), g);
     const float resc = IO<T>::rnd(__fmul_rn(cv, ratio[i / n_per]));
     const float a = IO<T>::rnd(__fmul_rn(gr, resc));
@@ -109,7 +204,7 @@ __global__ void cfg_rescale_apply_kernel(const T* __restrict__ eps, T* __restric
 // -- five torch launches in the reference, one here; the step kernel that follows runs with cfg = 0.
 template <typename T>
 __global__ void cfg_combine3_kernel(const T* __restrict__ eps, T* __restrict__ out, float g, float ig, size_t n) {
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+  EW_EACH(i, n) {
     const float t = IO<T>::ld(eps, i), im = IO<T>::ld(eps, n + i), u = IO<T>::ld(eps, 2 * n + i);
     const float d_ti = IO<T>::rnd(__fsub_rn(t, im));
     const float left = IO<T>::rnd(__fadd_rn(u, IO<T>::rnd(__fmul_rn(g, d_ti))));
@@ -121,28 +216,22 @@ __global__ void cfg_combine3_kernel(const T* __restrict__ eps, T* __restrict__ o
 
 // Euler (gamma = 0): table row = [sigma, sigma_next, dt, sqrt(sigma^2+1), c_out, sigma^2+1, -, timestep]
 // PRED: 0 epsilon, 1 v_prediction, 2 sample (scheduling_euler_discrete.py:760-775)
+template <typename T, int PRED>
+__device__ __forceinline__ float euler_one(const EulerCoef& k, float e, float s) {
+  const float x0 = x0_sigma<T, PRED>(k, e, s);               // pred_original_sample (fp32); s = sample.to(float32)
+  const float der = __fdiv_rn(__fsub_rn(s, x0), k.sigma);    // derivative
+  return __fadd_rn(s, __fmul_rn(der, k.dt));
+}
+
 template <typename T, bool CFG, int PRED>
 __global__ void euler_step_kernel(const T* __restrict__ eps, const T* __restrict__ x, T* __restrict__ out,
                                   const float* __restrict__ table, const int* __restrict__ step_idx, float g,
                                   size_t n) {
   const float* row = table + (size_t)(*step_idx) * 8;
-  const float sigma = row[0], dt = row[2], c_out = row[4], s2p1 = row[5];
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+  const EulerCoef k = {row[0], row[2], row[4], row[5]};
+  EW_EACH(i, n) {
     const float e = load_eps<T, CFG>(eps, i, n, g);
-    const float s = IO<T>::ld(x, i);                       // sample.to(float32)
-    float x0;                                              // pred_original_sample (fp32)
-    if (PRED == 0) {
-      const float se = IO<T>::rnd(__fmul_rn(sigma, e));    // sigma_hat * model_output  (model dtype)
-      x0 = __fsub_rn(s, se);
-    } else if (PRED == 1) {
-      // model_output * (-sigma / sqrt(sigma^2+1)) (model dtype) + sample / (sigma^2+1) (fp32)
-      x0 = __fadd_rn(IO<T>::rnd(__fmul_rn(e, c_out)), __fdiv_rn(s, s2p1));
-    } else {
-      x0 = e;
-    }
-    const float der = __fdiv_rn(__fsub_rn(s, x0), sigma);  // derivative
-    const float prev = __fadd_rn(s, __fmul_rn(der, dt));
-    IO<T>::st(out, i, prev);
+    IO<T>::st(out, i, euler_one<T, PRED>(k, e, IO<T>::ld(x, i)));
   }
 }
 
@@ -151,10 +240,7 @@ template <typename T>
 __global__ void euler_scale_input_kernel(const T* __restrict__ x, T* __restrict__ out, const float* __restrict__ table,
                                          const int* __restrict__ step_idx, int rep, size_t n) {
   const float den = table[(size_t)(*step_idx) * 8 + 3];
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
-    const float v = __fdiv_rn(IO<T>::ld(x, i), den);
-    for (int r = 0; r < rep; ++r) IO<T>::st(out, (size_t)r * n + i, v);
-  }
+  EW_EACH(i, n) store_rep<T>(out, i, n, rep, __fdiv_rn(IO<T>::ld(x, i), den));
 }
 
 // DDIM / DDPM: row = [sqrt(beta_t), sqrt(alpha_t), k0, ke, kx, kn, clip_range(0=off), timestep]
@@ -171,22 +257,16 @@ __global__ void x0_linear_step_kernel(const T* __restrict__ eps, const T* __rest
   const float* row = table + (size_t)(*step_idx) * 8;
   if (noise) noise += (size_t)(*step_idx) * noise_step_stride;  // pre-drawn per-step noise: graph-replay safe
   const float cb = row[0], ca = row[1], k0 = row[2], ke = row[3], kx = row[4], kn = row[5], clip = row[6];
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+  EW_EACH(i, n) {
     const float e = load_eps<T, CFG>(eps, i, n, g);
     const float s = IO<T>::ld(x, i);
-    float x0, pe;
-    if (PRED == 0) {
-      x0 = IO<T>::rnd(__fmul_rn(cb, e));
-      x0 = IO<T>::rnd(__fsub_rn(s, x0));
-      x0 = IO<T>::rnd(__fdiv_rn(x0, ca));
+    float x0 = x0_alpha_beta<T, PRED>(cb, ca, e, s), pe;
+    if (PRED == 0)
       pe = e;
-    } else if (PRED == 1) {
-      x0 = IO<T>::rnd(__fsub_rn(IO<T>::rnd(__fmul_rn(ca, s)), IO<T>::rnd(__fmul_rn(cb, e))));
+    else if (PRED == 1)
       pe = IO<T>::rnd(__fadd_rn(IO<T>::rnd(__fmul_rn(ca, e)), IO<T>::rnd(__fmul_rn(cb, s))));
-    } else {
-      x0 = e;
+    else
       pe = IO<T>::rnd(__fdiv_rn(IO<T>::rnd(__fsub_rn(s, IO<T>::rnd(__fmul_rn(ca, x0)))), cb));
-    }
     if (clip > 0.f) x0 = fminf(fmaxf(x0, -clip), clip);
     float acc = IO<T>::rnd(__fmul_rn(k0, x0));
     if (ke != 0.f) acc = IO<T>::rnd(__fadd_rn(acc, IO<T>::rnd(__fmul_rn(ke, pe))));
@@ -209,19 +289,10 @@ __global__ void lcm_step_kernel(const T* __restrict__ eps, const T* __restrict__
   const float* row = table + (size_t)(*step_idx) * 8;
   noise += (size_t)(*step_idx) * noise_step_stride;
   const float cb = row[0], ca = row[1], c_out = row[2], c_skip = row[3], pa = row[4], pb = row[5], clip = row[6];
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+  EW_EACH(i, n) {
     const float e = load_eps<T, CFG>(eps, i, n, g);
     const float s = IO<T>::ld(x, i);
-    float x0;
-    if (PRED == 0) {
-      x0 = IO<T>::rnd(__fmul_rn(cb, e));
-      x0 = IO<T>::rnd(__fsub_rn(s, x0));
-      x0 = IO<T>::rnd(__fdiv_rn(x0, ca));
-    } else if (PRED == 1) {
-      x0 = IO<T>::rnd(__fsub_rn(IO<T>::rnd(__fmul_rn(ca, s)), IO<T>::rnd(__fmul_rn(cb, e))));
-    } else {
-      x0 = e;
-    }
+    float x0 = x0_alpha_beta<T, PRED>(cb, ca, e, s);
     if (clip > 0.f) x0 = fminf(fmaxf(x0, -clip), clip);
     float acc = IO<T>::rnd(__fadd_rn(IO<T>::rnd(__fmul_rn(c_out, x0)), IO<T>::rnd(__fmul_rn(c_skip, s))));
     if (pb != 0.f)
@@ -239,7 +310,7 @@ __global__ void flowmatch_step_kernel(const TV* __restrict__ v, const TX* __rest
                                       const float* __restrict__ table, const int* __restrict__ step_idx, float g,
                                       size_t n) {
   const float dt = table[(size_t)(*step_idx) * 8 + 2];
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+  EW_EACH(i, n) {
     const float e = load_eps<TV, CFG>(v, i, n, g);
     const float s = IO<TX>::ld(x, i);
     const float de = IO<TV>::rnd(__fmul_rn(dt, e));
@@ -265,7 +336,7 @@ __global__ void unipc_flow_step_kernel(const TV* __restrict__ v, TX* __restrict_
   const float c1c = r[3], c2c = r[4], c3c = r[5], rk_c = r[6];
   const float rho0 = IO<TX>::rnd(r[7]), rhol = IO<TX>::rnd(r[8]);   // rhos_c is a tensor of the sample dtype
   const float c1p = r[10], c2p = r[11], c3p = r[12], rk_p = r[13];
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+  EW_EACH(i, n) {
     const float e = load_eps<TV, CFG>(v, i, n, g);
     const float xs = IO<TX>::ld(x, i);
     const float m1o = IO<TX>::ld(m1, i);
@@ -329,33 +400,6 @@ __device__ __forceinline__ float dpm_update(const DpmCoef& k, float xs, float x0
   return xn;
 }
 
-template <typename T>
-struct Vec4;
-template <>
-struct Vec4<uint16_t> {
-  static __device__ __forceinline__ void ld(const uint16_t* p, size_t i, float (&v)[4]) {
-    const uint2 r = *reinterpret_cast<const uint2*>(p + i);
-    v[0] = __uint_as_float(r.x << 16), v[1] = __uint_as_float(r.x & 0xffff0000u);
-    v[2] = __uint_as_float(r.y << 16), v[3] = __uint_as_float(r.y & 0xffff0000u);
-  }
-  static __device__ __forceinline__ void st(uint16_t* p, size_t i, const float (&v)[4]) {
-    uint2 r;
-    r.x = (uint32_t)f2bf(v[0]) | ((uint32_t)f2bf(v[1]) << 16);
-    r.y = (uint32_t)f2bf(v[2]) | ((uint32_t)f2bf(v[3]) << 16);
-    *reinterpret_cast<uint2*>(p + i) = r;
-  }
-};
-template <>
-struct Vec4<float> {
-  static __device__ __forceinline__ void ld(const float* p, size_t i, float (&v)[4]) {
-    const float4 r = *reinterpret_cast<const float4*>(p + i);
-    v[0] = r.x, v[1] = r.y, v[2] = r.z, v[3] = r.w;
-  }
-  static __device__ __forceinline__ void st(float* p, size_t i, const float (&v)[4]) {
-    *reinterpret_cast<float4*>(p + i) = make_float4(v[0], v[1], v[2], v[3]);
-  }
-};
-
 // n_vec (a multiple of 4, 0 when a pointer is not 16-byte aligned or, with CFG, the cond half is not) elements go through
 // 4-wide loads / stores, the rest through the scalar tail; both run the same per-element arithmetic.
 template <typename TX, typename TV, bool CFG, int PRED>
@@ -367,17 +411,9 @@ __global__ void dpmpp_2m_step_kernel(const TV* __restrict__ eps, TX* __restrict_
   DpmCoef k;
   k.a0 = row[0], k.b0 = row[1], k.cx = row[2], k.c0 = row[3], k.cd = row[4];
   k.second = row[6] != 0.f && step != *begin_idx;
-  const size_t tid = (size_t)blockIdx.x * blockDim.x + threadIdx.x, nth = (size_t)gridDim.x * blockDim.x;
-  for (size_t i = tid * 4; i < n_vec; i += nth * 4) {
+  EW_EACH4(i, n_vec) {
     float e[4], xs[4], mo[4], x0[4], xn[4];
-    if (CFG) {
-      float u[4], c[4];
-      Vec4<TV>::ld(eps, i, u), Vec4<TV>::ld(eps, n + i, c);
-#pragma unroll
-      for (int j = 0; j < 4; ++j) e[j] = cfg_combine<TV>(u[j], c[j], g);
-    } else {
-      Vec4<TV>::ld(eps, i, e);
-    }
+    LOAD_EPS4(TV, CFG, eps, i, n, g, e);
     Vec4<TX>::ld(x, i, xs);
     if (k.second) Vec4<float>::ld(m1, i, mo);
 #pragma unroll
@@ -388,7 +424,7 @@ __global__ void dpmpp_2m_step_kernel(const TV* __restrict__ eps, TX* __restrict_
     Vec4<float>::st(m1, i, x0);
     Vec4<TX>::st(x, i, xn);
   }
-  for (size_t i = n_vec + tid; i < n; i += nth) {
+  EW_TAIL(i, n_vec, n) {
     const float e = load_eps<TV, CFG>(eps, i, n, g);
     const float xs = IO<TX>::ld(x, i);
     const float x0 = dpm_x0<PRED>(k, e, xs);
@@ -408,24 +444,9 @@ __global__ void dpmpp_2m_step_kernel(const TV* __restrict__ eps, TX* __restrict_
 //   out  = T(prev)
 // noise + *step_idx * noise_step_stride is this step's pre-drawn randn (stride 0: one buffer the host refills per step), so the
 // step stays graph-replayable.  A row with sigma_up == 0 (the last one) skips the noise read: x + T(n * 0) == x.
-struct EulerACoef {
-  float sigma, dt, c_out, s2p1, sigma_up;
-};
-
-template <typename T, int PRED>
-__device__ __forceinline__ float euler_a_one(const EulerACoef& k, float e, float s) {
-  float x0;
-  if (PRED == 0)
-    x0 = __fsub_rn(s, IO<T>::rnd(__fmul_rn(k.sigma, e)));
-  else
-    x0 = __fadd_rn(IO<T>::rnd(__fmul_rn(e, k.c_out)), __fdiv_rn(s, k.s2p1));
-  const float der = __fdiv_rn(__fsub_rn(s, x0), k.sigma);
-  return __fadd_rn(s, __fmul_rn(der, k.dt));
-}
-
 template <typename T>
-__device__ __forceinline__ float euler_a_noise(const EulerACoef& k, float prev, float nz) {
-  return __fadd_rn(prev, IO<T>::rnd(__fmul_rn(nz, k.sigma_up)));
+__device__ __forceinline__ float euler_a_noise(float sigma_up, float prev, float nz) {
+  return __fadd_rn(prev, IO<T>::rnd(__fmul_rn(nz, sigma_up)));
 }
 
 // n_vec as in dpmpp_2m_step_kernel: the leading multiple of 4 elements when every base (the cond half and every noise row
@@ -436,35 +457,27 @@ __global__ void euler_ancestral_step_kernel(const T* __restrict__ eps, const T* 
                                             size_t n, size_t n_vec, size_t noise_step_stride) {
   const int step = *step_idx;
   const float* row = table + (size_t)step * 8;
-  EulerACoef k;
-  k.sigma = row[0], k.dt = row[2], k.c_out = row[4], k.s2p1 = row[5], k.sigma_up = row[6];
+  const EulerCoef k = {row[0], row[2], row[4], row[5]};
+  const float sigma_up = row[6];
   noise += (size_t)step * noise_step_stride;
-  const bool add = k.sigma_up != 0.f;   // uniform over the launch
-  const size_t tid = (size_t)blockIdx.x * blockDim.x + threadIdx.x, nth = (size_t)gridDim.x * blockDim.x;
-  for (size_t i = tid * 4; i < n_vec; i += nth * 4) {
+  const bool add = sigma_up != 0.f;   // uniform over the launch
+  EW_EACH4(i, n_vec) {
     float e[4], xs[4], nz[4], o[4];
-    if (CFG) {
-      float u[4], c[4];
-      Vec4<T>::ld(eps, i, u), Vec4<T>::ld(eps, n + i, c);
-#pragma unroll
-      for (int j = 0; j < 4; ++j) e[j] = cfg_combine<T>(u[j], c[j], g);
-    } else {
-      Vec4<T>::ld(eps, i, e);
-    }
+    LOAD_EPS4(T, CFG, eps, i, n, g, e);
     Vec4<T>::ld(x, i, xs);
 #pragma unroll
-    for (int j = 0; j < 4; ++j) o[j] = euler_a_one<T, PRED>(k, e[j], xs[j]);
+    for (int j = 0; j < 4; ++j) o[j] = euler_one<T, PRED>(k, e[j], xs[j]);
     if (add) {
       Vec4<T>::ld(noise, i, nz);
 #pragma unroll
-      for (int j = 0; j < 4; ++j) o[j] = euler_a_noise<T>(k, o[j], nz[j]);
+      for (int j = 0; j < 4; ++j) o[j] = euler_a_noise<T>(sigma_up, o[j], nz[j]);
     }
     Vec4<T>::st(out, i, o);
   }
-  for (size_t i = n_vec + tid; i < n; i += nth) {
+  EW_TAIL(i, n_vec, n) {
     const float e = load_eps<T, CFG>(eps, i, n, g);
-    float o = euler_a_one<T, PRED>(k, e, IO<T>::ld(x, i));
-    if (add) o = euler_a_noise<T>(k, o, IO<T>::ld(noise, i));
+    float o = euler_one<T, PRED>(k, e, IO<T>::ld(x, i));
+    if (add) o = euler_a_noise<T>(sigma_up, o, IO<T>::ld(noise, i));
     IO<T>::st(out, i, o);
   }
 }
@@ -497,9 +510,8 @@ __global__ __launch_bounds__(256) void inpaint_blend_kernel(uint16_t* __restrict
   const int row = min(max(*step_idx, 0), n_rows - 1);
   BlendCoef k;
   k.a = coef[2 * row], k.b = coef[2 * row + 1];
-  const size_t tid = (size_t)blockIdx.x * blockDim.x + threadIdx.x, nth = (size_t)gridDim.x * blockDim.x;
   if (VEC) {
-    for (size_t i = tid * 8; i < n; i += nth * 8) {
+    EW_SPAN(i, 8, 0, n) {
       const size_t b = i / chw, p = i % hw;
       const uint4 lq = *(const uint4*)(lat + i), xq = *(const uint4*)(x0 + i), nq = *(const uint4*)(noise + i);
       const uint4 mq = *(const uint4*)(mask + (mask_per_sample ? b * hw : 0) + p);
@@ -510,7 +522,7 @@ __global__ __launch_bounds__(256) void inpaint_blend_kernel(uint16_t* __restrict
       *(uint4*)(lat + i) = pack8(o);
     }
   } else {
-    for (size_t i = tid; i < n; i += nth) {
+    EW_EACH(i, n) {
       const size_t b = i / chw, p = i % hw;
       const float m = bf2f(mask[(mask_per_sample ? b * hw : 0) + p]);
       lat[i] = f2bf(inpaint_blend_one(k, bf2f(lat[i]), bf2f(x0[i]), bf2f(noise[i]), m));
@@ -523,18 +535,12 @@ __global__ void advance_step_kernel(int* step_idx) { *step_idx += 1; }
 // out = x * s in the tensor dtype (latents * init_noise_sigma, pipeline_stable_diffusion.py:713)
 template <typename T>
 __global__ void mul_scalar_kernel(const T* __restrict__ x, T* __restrict__ out, float sc, int rep, size_t n) {
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
-    const float v = __fmul_rn(IO<T>::ld(x, i), sc);
-    for (int r = 0; r < rep; ++r) IO<T>::st(out, (size_t)r * n + i, v);  // rep > 1: torch.cat([x] * rep) fused
-  }
+  EW_EACH(i, n) store_rep<T>(out, i, n, rep, __fmul_rn(IO<T>::ld(x, i), sc));
 }
 
 // latents.to(transformer_dtype) (pipeline_wan.py:600) fused with the CFG batch doubling: fp32 -> bf16, `rep` copies
 __global__ void cast_f32_bf16_kernel(const float* __restrict__ x, uint16_t* __restrict__ out, int rep, size_t n) {
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
-    const uint16_t v = f2bf(x[i]);
-    for (int r = 0; r < rep; ++r) out[(size_t)r * n + i] = v;
-  }
+  EW_EACH(i, n) store_rep<uint16_t>(out, i, n, rep, x[i]);
 }
 
 inline dim3 ew_grid(size_t n) {
@@ -544,6 +550,64 @@ inline dim3 ew_grid(size_t n) {
   return dim3((unsigned)b);
 }
 
+// How a launch of the "4-wide body + scalar tail" form splits its n elements.  4-wide accesses need every base in `bases` (the
+// OR of the operand pointers) 16-byte aligned, and so every offset the kernel adds to a base: the cond half of the model output,
+// n elements of `esz` bytes in, when `cfg`, and a noise row, a multiple of `row_bytes` in.  n_vec = the leading multiple of 4
+// when all are, else 0; work = what ew_grid has to cover, the longer of the two loops.
+struct VecSplit {
+  size_t n_vec, work;
+};
+inline VecSplit vec_split(uintptr_t bases, size_t esz, size_t n, bool cfg, size_t row_bytes = 0) {
+  const bool aligned = bases % 16 == 0 && row_bytes % 16 == 0 && (!cfg || (n * esz) % 16 == 0);
+  const size_t n_vec = aligned ? n - n % 4 : 0;
+  return {n_vec, n_vec / 4 > n - n_vec ? n_vec / 4 : n - n_vec};
+}
+
+// Runtime (dtype, cfg, pred_type) -> template arguments.  Each level calls f with a tag value whose TYPE carries the choice and
+// returns what f returns, so the innermost f launches, checks the launch and returns the status.
+template <typename T>
+struct Type {
+  using type = T;
+};
+template <typename F>
+int dispatch_dtype(int dtype, F f) {  // f(Type<uint16_t>) / f(Type<float>); any other dtype: DA_ERR_UNSUPPORTED, f not called
+  if (dtype == DA_DTYPE_BF16) return f(Type<uint16_t>{});
+  if (dtype == DA_DTYPE_F32) return f(Type<float>{});
+  return DA_ERR_UNSUPPORTED;
+}
+template <typename F>
+int dispatch_bool(bool b, F f) {  // f(std::true_type) / f(std::false_type)
+  return b ? f(std::true_type{}) : f(std::false_type{});
+}
+template <int N, typename F>
+int dispatch_int(int v, F f) {  // f(std::integral_constant<int, v>) for v in [0, N), which the caller has checked
+  if constexpr (N > 1) {
+    if (v != N - 1) return dispatch_int<N - 1>(v, f);
+  }
+  return f(std::integral_constant<int, N - 1>{});
+}
+// all three at once, for the step kernels templated on <T, CFG, PRED>: f(Type<T>, bool constant, int constant in [0, NPRED))
+template <int NPRED, typename F>
+int dispatch_step(int dtype, bool cfg, int pred, F f) {
+  return dispatch_dtype(dtype, [&](auto t) {
+    return dispatch_bool(cfg, [&](auto c) { return dispatch_int<NPRED>(pred, [&](auto p) { return f(t, c, p); }); });
+  });
+}
+// the (sample TX, model output TV) pairs of the flow schedulers: bf16 / bf16, f32 / f32 and f32 / bf16; f(Type<TX>, Type<TV>)
+template <typename F>
+int dispatch_flow_dtypes(int x_dtype, int v_dtype, F f) {
+  return dispatch_dtype(x_dtype, [&](auto tx) {
+    return dispatch_dtype(v_dtype, [&](auto tv) {
+      if constexpr (std::is_same_v<decltype(tx), Type<uint16_t>> && std::is_same_v<decltype(tv), Type<float>>)
+        return DA_ERR_UNSUPPORTED;
+      else
+        return f(tx, tv);
+    });
+  });
+}
+template <typename Tag>
+using type_of = typename Tag::type;
+
 }  // namespace
 
 extern "C" int da_euler_step(const void* eps, const void* x, void* out, const float* table, const int* step_idx,
@@ -552,21 +616,13 @@ extern "C" int da_euler_step(const void* eps, const void* x, void* out, const fl
   if (pred_type < 0 || pred_type > 2) return DA_ERR_INVALID;
   const size_t n = (size_t)n_;
   hipStream_t s = (hipStream_t)stream;
-#define DA_EU(T, C, P) \
-  DA_LAUNCH((euler_step_kernel<T, C, P>), ew_grid(n), dim3(256), 0, s, (const T*)eps, (const T*)x, (T*)out, table, step_idx, guidance, n)
-#define DA_EU_P(T, C) \
-  do { if (pred_type == 0) DA_EU(T, C, 0); else if (pred_type == 1) DA_EU(T, C, 1); else DA_EU(T, C, 2); } while (0)
-  if (dtype == DA_DTYPE_BF16) {
-    if (cfg) DA_EU_P(uint16_t, true); else DA_EU_P(uint16_t, false);
-  } else if (dtype == DA_DTYPE_F32) {
-    if (cfg) DA_EU_P(float, true); else DA_EU_P(float, false);
-  } else {
-    return DA_ERR_UNSUPPORTED;
-  }
-#undef DA_EU_P
-#undef DA_EU
-  DA_CHECK_LAUNCH();
-  return DA_OK;
+  return dispatch_step<3>(dtype, cfg, pred_type, [&](auto t, auto c, auto p) {
+    using T = type_of<decltype(t)>;
+    DA_LAUNCH((euler_step_kernel<T, c.value, p.value>), ew_grid(n), dim3(256), 0, s, (const T*)eps, (const T*)x, (T*)out, table,
+              step_idx, guidance, n);
+    DA_CHECK_LAUNCH();
+    return DA_OK;
+  });
 }
 
 extern "C" int da_euler_scale_model_input(const void* x, void* out, const float* table, const int* step_idx, int rep,
@@ -574,14 +630,12 @@ extern "C" int da_euler_scale_model_input(const void* x, void* out, const float*
   if (!x || !out || !table || !step_idx || n_ <= 0 || rep <= 0) return DA_ERR_INVALID;
   const size_t n = (size_t)n_;
   hipStream_t s = (hipStream_t)stream;
-  if (dtype == DA_DTYPE_BF16)
-    DA_LAUNCH((euler_scale_input_kernel<uint16_t>), ew_grid(n), dim3(256), 0, s, (const uint16_t*)x, (uint16_t*)out, table, step_idx, rep, n);
-  else if (dtype == DA_DTYPE_F32)
-    DA_LAUNCH((euler_scale_input_kernel<float>), ew_grid(n), dim3(256), 0, s, (const float*)x, (float*)out, table, step_idx, rep, n);
-  else
-    return DA_ERR_UNSUPPORTED;
-  DA_CHECK_LAUNCH();
-  return DA_OK;
+  return dispatch_dtype(dtype, [&](auto t) {
+    using T = type_of<decltype(t)>;
+    DA_LAUNCH((euler_scale_input_kernel<T>), ew_grid(n), dim3(256), 0, s, (const T*)x, (T*)out, table, step_idx, rep, n);
+    DA_CHECK_LAUNCH();
+    return DA_OK;
+  });
 }
 
 extern "C" int da_x0_linear_step(const void* eps, const void* x, const void* noise, long long noise_step_stride,
@@ -595,25 +649,14 @@ extern "C" int da_x0_linear_step(const void* eps, const void* x, const void* noi
   if (lcm && !noise) return DA_ERR_INVALID;
   const size_t n = (size_t)n_;
   hipStream_t s = (hipStream_t)stream;
-#define DA_XL_K(K, T, C, P)                                                                                         \
-  DA_LAUNCH((K<T, C, P>), ew_grid(n), dim3(256), 0, s, (const T*)eps, (const T*)x, (const T*)noise, (T*)out, table, \
-            step_idx, guidance, n, (size_t)noise_step_stride)
-#define DA_XL(T, C, P) \
-  do { if (lcm) DA_XL_K(lcm_step_kernel, T, C, P); else DA_XL_K(x0_linear_step_kernel, T, C, P); } while (0)
-#define DA_XL_P(T, C) \
-  do { if (pred == 0) DA_XL(T, C, 0); else if (pred == 1) DA_XL(T, C, 1); else DA_XL(T, C, 2); } while (0)
-  if (dtype == DA_DTYPE_BF16) {
-    if (cfg) DA_XL_P(uint16_t, true); else DA_XL_P(uint16_t, false);
-  } else if (dtype == DA_DTYPE_F32) {
-    if (cfg) DA_XL_P(float, true); else DA_XL_P(float, false);
-  } else {
-    return DA_ERR_UNSUPPORTED;
-  }
-#undef DA_XL_P
-#undef DA_XL
-#undef DA_XL_K
-  DA_CHECK_LAUNCH();
-  return DA_OK;
+  return dispatch_step<3>(dtype, cfg, pred, [&](auto t, auto c, auto p) {
+    using T = type_of<decltype(t)>;
+    const auto kernel = lcm ? lcm_step_kernel<T, c.value, p.value> : x0_linear_step_kernel<T, c.value, p.value>;
+    DA_LAUNCH(kernel, ew_grid(n), dim3(256), 0, s, (const T*)eps, (const T*)x, (const T*)noise, (T*)out, table, step_idx,
+              guidance, n, (size_t)noise_step_stride);
+    DA_CHECK_LAUNCH();
+    return DA_OK;
+  });
 }
 
 extern "C" int da_flowmatch_step(const void* v, const void* x, void* out, const float* table, const int* step_idx,
@@ -621,54 +664,44 @@ extern "C" int da_flowmatch_step(const void* v, const void* x, void* out, const 
   if (!v || !x || !out || !table || !step_idx || n_ <= 0) return DA_ERR_INVALID;
   const size_t n = (size_t)n_;
   hipStream_t s = (hipStream_t)stream;
-#define DA_FM(TX, TV, C) \
-  DA_LAUNCH((flowmatch_step_kernel<TX, TV, C>), ew_grid(n), dim3(256), 0, s, (const TV*)v, (const TX*)x, (TV*)out, table, step_idx, guidance, n)
-  if (dtype == DA_DTYPE_BF16 && x_dtype == DA_DTYPE_BF16) { if (cfg) DA_FM(uint16_t, uint16_t, true); else DA_FM(uint16_t, uint16_t, false); }
-  else if (dtype == DA_DTYPE_F32 && x_dtype == DA_DTYPE_F32) { if (cfg) DA_FM(float, float, true); else DA_FM(float, float, false); }
-  else if (dtype == DA_DTYPE_BF16 && x_dtype == DA_DTYPE_F32) { if (cfg) DA_FM(float, uint16_t, true); else DA_FM(float, uint16_t, false); }
-  else return DA_ERR_UNSUPPORTED;
-#undef DA_FM
-  DA_CHECK_LAUNCH();
-  return DA_OK;
+  return dispatch_flow_dtypes(x_dtype, dtype, [&](auto tx, auto tv) {
+    return dispatch_bool(cfg, [&](auto c) {
+      using TX = type_of<decltype(tx)>;
+      using TV = type_of<decltype(tv)>;
+      DA_LAUNCH((flowmatch_step_kernel<TX, TV, c.value>), ew_grid(n), dim3(256), 0, s, (const TV*)v, (const TX*)x, (TV*)out, table,
+                step_idx, guidance, n);
+      DA_CHECK_LAUNCH();
+      return DA_OK;
+    });
+  });
 }
 
 extern "C" int da_cfg_rescale(const void* eps, void* out, float* ratio_ws, int B, long long n_per_, float guidance,
                               float guidance_rescale, int dtype, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
   if (dtype & DA_CFG_IMAGE_GUIDANCE) {
     // three-way (text, image, uncond) guidance: `guidance_rescale` carries image_guidance_scale, no statistics, ratio_ws unused
-    dtype &= ~DA_CFG_IMAGE_GUIDANCE;
     if (!eps || !out || B <= 0 || n_per_ <= 0) return DA_ERR_INVALID;
     const size_t n3 = (size_t)n_per_ * (size_t)B;
-    if (dtype == DA_DTYPE_BF16)
-      DA_LAUNCH((cfg_combine3_kernel<uint16_t>), ew_grid(n3), dim3(256), 0, (hipStream_t)stream, (const uint16_t*)eps, (uint16_t*)out,
-                guidance, guidance_rescale, n3);
-    else if (dtype == DA_DTYPE_F32)
-      DA_LAUNCH((cfg_combine3_kernel<float>), ew_grid(n3), dim3(256), 0, (hipStream_t)stream, (const float*)eps, (float*)out, guidance,
-                guidance_rescale, n3);
-    else
-      return DA_ERR_UNSUPPORTED;
-    DA_CHECK_LAUNCH();
-    return DA_OK;
+    return dispatch_dtype(dtype & ~DA_CFG_IMAGE_GUIDANCE, [&](auto t) {
+      using T = type_of<decltype(t)>;
+      DA_LAUNCH((cfg_combine3_kernel<T>), ew_grid(n3), dim3(256), 0, s, (const T*)eps, (T*)out, guidance, guidance_rescale, n3);
+      DA_CHECK_LAUNCH();
+      return DA_OK;
+    });
   }
   if (!eps || !out || !ratio_ws || B <= 0 || n_per_ <= 1) return DA_ERR_INVALID;
   const size_t n_per = (size_t)n_per_, n = n_per * (size_t)B;
-  hipStream_t s = (hipStream_t)stream;
   const float omg = (float)(1.0 - (double)guidance_rescale);   // the reference forms (1 - guidance_rescale) in Python doubles
-  if (dtype == DA_DTYPE_BF16) {
-    DA_LAUNCH((cfg_rescale_stats_kernel<uint16_t>), dim3(B), dim3(1024), 0, s, (const uint16_t*)eps, ratio_ws, guidance, n_per, B);
+  return dispatch_dtype(dtype, [&](auto t) {
+    using T = type_of<decltype(t)>;
+    DA_LAUNCH((cfg_rescale_stats_kernel<T>), dim3(B), dim3(1024), 0, s, (const T*)eps, ratio_ws, guidance, n_per, B);
     DA_CHECK_LAUNCH();
-    DA_LAUNCH((cfg_rescale_apply_kernel<uint16_t>), ew_grid(n), dim3(256), 0, s, (const uint16_t*)eps, (uint16_t*)out, ratio_ws,
-              guidance, guidance_rescale, omg, n_per, n);
-  } else if (dtype == DA_DTYPE_F32) {
-    DA_LAUNCH((cfg_rescale_stats_kernel<float>), dim3(B), dim3(1024), 0, s, (const float*)eps, ratio_ws, guidance, n_per, B);
-    DA_CHECK_LAUNCH();
-    DA_LAUNCH((cfg_rescale_apply_kernel<float>), ew_grid(n), dim3(256), 0, s, (const float*)eps, (float*)out, ratio_ws, guidance,
+    DA_LAUNCH((cfg_rescale_apply_kernel<T>), ew_grid(n), dim3(256), 0, s, (const T*)eps, (T*)out, ratio_ws, guidance,
               guidance_rescale, omg, n_per, n);
-  } else {
-    return DA_ERR_UNSUPPORTED;
-  }
-  DA_CHECK_LAUNCH();
-  return DA_OK;
+    DA_CHECK_LAUNCH();
+    return DA_OK;
+  });
 }
 
 extern "C" int da_advance_step(int* step_idx, void* stream) {
@@ -682,14 +715,12 @@ extern "C" int da_mul_scalar(const void* x, void* out, float sc, int rep, long l
   if (!x || !out || n_ <= 0 || rep <= 0) return DA_ERR_INVALID;
   const size_t n = (size_t)n_;
   hipStream_t s = (hipStream_t)stream;
-  if (dtype == DA_DTYPE_BF16)
-    DA_LAUNCH((mul_scalar_kernel<uint16_t>), ew_grid(n), dim3(256), 0, s, (const uint16_t*)x, (uint16_t*)out, sc, rep, n);
-  else if (dtype == DA_DTYPE_F32)
-    DA_LAUNCH((mul_scalar_kernel<float>), ew_grid(n), dim3(256), 0, s, (const float*)x, (float*)out, sc, rep, n);
-  else
-    return DA_ERR_UNSUPPORTED;
-  DA_CHECK_LAUNCH();
-  return DA_OK;
+  return dispatch_dtype(dtype, [&](auto t) {
+    using T = type_of<decltype(t)>;
+    DA_LAUNCH((mul_scalar_kernel<T>), ew_grid(n), dim3(256), 0, s, (const T*)x, (T*)out, sc, rep, n);
+    DA_CHECK_LAUNCH();
+    return DA_OK;
+  });
 }
 
 extern "C" int da_unipc_flow_step(const void* v, void* x, void* last, void* m1, void* m2, const float* coef,
@@ -698,16 +729,16 @@ extern "C" int da_unipc_flow_step(const void* v, void* x, void* last, void* m1, 
   if (!v || !x || !last || !m1 || !m2 || !coef || !step_idx || n_ <= 0) return DA_ERR_INVALID;
   const size_t n = (size_t)n_;
   hipStream_t s = (hipStream_t)stream;
-#define DA_UP(TX, TV, C)                                                                                       \
-  DA_LAUNCH((unipc_flow_step_kernel<TX, TV, C>), ew_grid(n), dim3(256), 0, s, (const TV*)v, (TX*)x, (TX*)last, \
-            (TX*)m1, (TX*)m2, coef, step_idx, guidance, n)
-  if (x_dtype == DA_DTYPE_F32 && v_dtype == DA_DTYPE_F32) { if (cfg) DA_UP(float, float, true); else DA_UP(float, float, false); }
-  else if (x_dtype == DA_DTYPE_F32 && v_dtype == DA_DTYPE_BF16) { if (cfg) DA_UP(float, uint16_t, true); else DA_UP(float, uint16_t, false); }
-  else if (x_dtype == DA_DTYPE_BF16 && v_dtype == DA_DTYPE_BF16) { if (cfg) DA_UP(uint16_t, uint16_t, true); else DA_UP(uint16_t, uint16_t, false); }
-  else return DA_ERR_UNSUPPORTED;
-#undef DA_UP
-  DA_CHECK_LAUNCH();
-  return DA_OK;
+  return dispatch_flow_dtypes(x_dtype, v_dtype, [&](auto tx, auto tv) {
+    return dispatch_bool(cfg, [&](auto c) {
+      using TX = type_of<decltype(tx)>;
+      using TV = type_of<decltype(tv)>;
+      DA_LAUNCH((unipc_flow_step_kernel<TX, TV, c.value>), ew_grid(n), dim3(256), 0, s, (const TV*)v, (TX*)x, (TX*)last, (TX*)m1,
+                (TX*)m2, coef, step_idx, guidance, n);
+      DA_CHECK_LAUNCH();
+      return DA_OK;
+    });
+  });
 }
 
 extern "C" int da_dpmpp_2m_step(const void* eps, void* x, float* m1, const float* table, const int* step_idx,
@@ -719,27 +750,19 @@ extern "C" int da_dpmpp_2m_step(const void* eps, void* x, float* m1, const float
     return DA_ERR_UNSUPPORTED;
   const size_t n = (size_t)n_;
   hipStream_t s = (hipStream_t)stream;
-  // 4-wide accesses: 16-byte aligned bases; with CFG the cond half starts n elements in, so n must be a multiple of 4 too
-  const bool aligned = ((uintptr_t)eps | (uintptr_t)x | (uintptr_t)m1) % 16 == 0 && (!cfg || n % 4 == 0);
-  const size_t n_vec = aligned ? n - n % 4 : 0;
-  const size_t work = n_vec / 4 > n - n_vec ? n_vec / 4 : n - n_vec;
-#define DA_DP(TX, TV, C, P)                                                                                          \
-  DA_LAUNCH((dpmpp_2m_step_kernel<TX, TV, C, P>), ew_grid(work), dim3(256), 0, s, (const TV*)eps, (TX*)x, m1, table, \
-            step_idx, begin_idx, guidance, n, n_vec)
-#define DA_DP_P(TX, TV, C) \
-  do { if (pred_type == 0) DA_DP(TX, TV, C, 0); else if (pred_type == 1) DA_DP(TX, TV, C, 1); else DA_DP(TX, TV, C, 2); } while (0)
-#define DA_DP_C(TX, TV) \
-  do { if (cfg) DA_DP_P(TX, TV, true); else DA_DP_P(TX, TV, false); } while (0)
-  if (x_dtype == DA_DTYPE_BF16) {
-    if (e_dtype == DA_DTYPE_BF16) DA_DP_C(uint16_t, uint16_t); else DA_DP_C(uint16_t, float);
-  } else {
-    if (e_dtype == DA_DTYPE_BF16) DA_DP_C(float, uint16_t); else DA_DP_C(float, float);
-  }
-#undef DA_DP_C
-#undef DA_DP_P
-#undef DA_DP
-  DA_CHECK_LAUNCH();
-  return DA_OK;
+  // with CFG the cond half starts n elements in and n must be a multiple of 4, whatever the model output's dtype: the condition of
+  // 4-byte elements (a bf16 model output is read 8 bytes at a time and would need no more)
+  const VecSplit vs = vec_split((uintptr_t)eps | (uintptr_t)x | (uintptr_t)m1, sizeof(float), n, cfg);
+  return dispatch_dtype(x_dtype, [&](auto tx) {
+    return dispatch_step<3>(e_dtype, cfg, pred_type, [&](auto tv, auto c, auto p) {
+      using TX = type_of<decltype(tx)>;
+      using TV = type_of<decltype(tv)>;
+      DA_LAUNCH((dpmpp_2m_step_kernel<TX, TV, c.value, p.value>), ew_grid(vs.work), dim3(256), 0, s, (const TV*)eps, (TX*)x, m1,
+                table, step_idx, begin_idx, guidance, n, vs.n_vec);
+      DA_CHECK_LAUNCH();
+      return DA_OK;
+    });
+  });
 }
 
 extern "C" int da_euler_ancestral_step(const void* eps, const void* x, const void* noise, long long noise_step_stride,
@@ -750,25 +773,16 @@ extern "C" int da_euler_ancestral_step(const void* eps, const void* x, const voi
   if (dtype != DA_DTYPE_BF16 && dtype != DA_DTYPE_F32) return DA_ERR_UNSUPPORTED;
   const size_t n = (size_t)n_, esz = dtype == DA_DTYPE_BF16 ? 2 : 4;
   hipStream_t s = (hipStream_t)stream;
-  // 4-wide accesses: every base 16-byte aligned -- with CFG the cond half n elements in, and the noise row of any step
-  const bool aligned = ((uintptr_t)eps | (uintptr_t)x | (uintptr_t)noise | (uintptr_t)out) % 16 == 0 &&
-                       ((size_t)noise_step_stride * esz) % 16 == 0 && (!cfg || (n * esz) % 16 == 0);
-  const size_t n_vec = aligned ? n - n % 4 : 0;
-  const size_t work = n_vec / 4 > n - n_vec ? n_vec / 4 : n - n_vec;
-#define DA_EA(T, C, P)                                                                                                    \
-  DA_LAUNCH((euler_ancestral_step_kernel<T, C, P>), ew_grid(work), dim3(256), 0, s, (const T*)eps, (const T*)x, (const T*)noise, \
-            (T*)out, table, step_idx, guidance, n, n_vec, (size_t)noise_step_stride)
-#define DA_EA_P(T, C) \
-  do { if (pred_type == 0) DA_EA(T, C, 0); else DA_EA(T, C, 1); } while (0)
-  if (dtype == DA_DTYPE_BF16) {
-    if (cfg) DA_EA_P(uint16_t, true); else DA_EA_P(uint16_t, false);
-  } else {
-    if (cfg) DA_EA_P(float, true); else DA_EA_P(float, false);
-  }
-#undef DA_EA_P
-#undef DA_EA
-  DA_CHECK_LAUNCH();
-  return DA_OK;
+  // every base 16-byte aligned -- with CFG the cond half n elements in, and the noise row of any step
+  const VecSplit vs = vec_split((uintptr_t)eps | (uintptr_t)x | (uintptr_t)noise | (uintptr_t)out, esz, n, cfg,
+                                (size_t)noise_step_stride * esz);
+  return dispatch_step<2>(dtype, cfg, pred_type, [&](auto t, auto c, auto p) {
+    using T = type_of<decltype(t)>;
+    DA_LAUNCH((euler_ancestral_step_kernel<T, c.value, p.value>), ew_grid(vs.work), dim3(256), 0, s, (const T*)eps, (const T*)x,
+              (const T*)noise, (T*)out, table, step_idx, guidance, n, vs.n_vec, (size_t)noise_step_stride);
+    DA_CHECK_LAUNCH();
+    return DA_OK;
+  });
 }
 
 extern "C" int da_cast_f32_bf16(const float* x, void* out, int rep, long long n_, void* stream) {
@@ -787,12 +801,11 @@ extern "C" int da_inpaint_blend(void* latents, const void* image_latents, const 
   const size_t hw = (size_t)HW, chw = (size_t)C * hw, n = (size_t)B * chw;
   hipStream_t s = (hipStream_t)stream;
   const bool vec = hw % 8 == 0 && ((uintptr_t)latents | (uintptr_t)image_latents | (uintptr_t)noise | (uintptr_t)mask) % 16 == 0;
-  if (vec)
-    DA_LAUNCH(inpaint_blend_kernel<true>, ew_grid(n / 8), dim3(256), 0, s, (uint16_t*)latents, (const uint16_t*)image_latents,
-              (const uint16_t*)noise, (const uint16_t*)mask, coef, step_idx, n_rows, chw, hw, Bm == B && B > 1 ? 1 : 0, n);
-  else
-    DA_LAUNCH(inpaint_blend_kernel<false>, ew_grid(n), dim3(256), 0, s, (uint16_t*)latents, (const uint16_t*)image_latents,
-              (const uint16_t*)noise, (const uint16_t*)mask, coef, step_idx, n_rows, chw, hw, Bm == B && B > 1 ? 1 : 0, n);
-  DA_CHECK_LAUNCH();
-  return DA_OK;
+  return dispatch_bool(vec, [&](auto v) {
+    DA_LAUNCH(inpaint_blend_kernel<v.value>, ew_grid(vec ? n / 8 : n), dim3(256), 0, s, (uint16_t*)latents,
+              (const uint16_t*)image_latents, (const uint16_t*)noise, (const uint16_t*)mask, coef, step_idx, n_rows, chw, hw,
+              Bm == B && B > 1 ? 1 : 0, n);
+    DA_CHECK_LAUNCH();
+    return DA_OK;
+  });
 }

@@ -928,8 +928,10 @@ def _dt(t: torch.Tensor) -> int:
 
 
 def _check_sampler(what: str, x: torch.Tensor, model_out: torch.Tensor, out: Optional[torch.Tensor], cfg: bool,
-                   same_dtype: bool = True) -> None:
-    """The sampler kernels index their operands flat: every tensor must be a contiguous HIP tensor of the right size."""
+                   same_dtype: bool = True, out_dtype: Optional[torch.dtype] = None) -> Optional[torch.Tensor]:
+    """The sampler kernels index their operands flat: every tensor must be a contiguous HIP tensor of the right size.  With
+    ``out_dtype`` (the dtype the step's result has) returns ``out``, allocated in the sample's shape when it is None and checked
+    for that dtype otherwise."""
     _req(x, "sample", None), _req(model_out, "model_output", None)
     if model_out.numel() != x.numel() * (2 if cfg else 1):
         raise ValueError(f"{what}: model_output must hold {'[2 x sample] (uncond, cond)' if cfg else 'as many'} "
@@ -942,6 +944,13 @@ def _check_sampler(what: str, x: torch.Tensor, model_out: torch.Tensor, out: Opt
         _req(out, "out", None)
         if out.numel() != x.numel() or not out.is_contiguous():
             raise ValueError(f"{what}: out must be a contiguous tensor of the sample's size")
+    if out_dtype is None:
+        return None
+    if out is None:
+        return torch.empty(x.shape, device=x.device, dtype=out_dtype)
+    if out.dtype != out_dtype:
+        raise TypeError(f"{what}: out must have the {'sample' if out_dtype == x.dtype else 'model output'}'s dtype")
+    return out
 
 
 def euler_scale_model_input(x: torch.Tensor, table: torch.Tensor, step_idx: torch.Tensor, rep: int = 1) -> torch.Tensor:
@@ -956,11 +965,7 @@ def euler_scale_model_input(x: torch.Tensor, table: torch.Tensor, step_idx: torc
 
 def euler_step(eps: torch.Tensor, x: torch.Tensor, table: torch.Tensor, step_idx: torch.Tensor, *, cfg: bool,
                guidance: float, out: Optional[torch.Tensor] = None, pred_type: int = L.PRED_EPSILON) -> torch.Tensor:
-    _check_sampler("euler_step", x, eps, out, cfg)
-    if out is None:
-        out = torch.empty_like(x)
-    elif out.dtype != x.dtype:
-        raise TypeError("euler_step: out must have the sample's dtype")
+    out = _check_sampler("euler_step", x, eps, out, cfg, out_dtype=x.dtype)
     L.check(L.load().da_euler_step(eps.data_ptr(), x.data_ptr(), out.data_ptr(), table.data_ptr(), step_idx.data_ptr(),
                                    int(cfg), guidance, x.numel(), _dt(x), int(pred_type), _stream()), "da_euler_step")
     return out
@@ -983,11 +988,9 @@ def euler_ancestral_step(eps: torch.Tensor, x: torch.Tensor, noise: torch.Tensor
         raise ValueError(f"euler_ancestral_step: model_output ({eps.dtype}) and sample ({x.dtype}) must have the same dtype")
     if pred_type not in (L.PRED_EPSILON, L.PRED_V):
         raise ValueError("euler_ancestral_step: pred_type must be epsilon or v_prediction")
-    _check_sampler("euler_ancestral_step", x, eps, out, cfg)
-    if out is None:
-        out = torch.empty_like(x)
-    elif out.dtype != x.dtype:
+    if out is not None and out.dtype != x.dtype:
         raise ValueError("euler_ancestral_step: out must have the sample's dtype")
+    out = _check_sampler("euler_ancestral_step", x, eps, out, cfg, out_dtype=x.dtype)
     if table.dtype != torch.float32 or table.dim() != 2 or table.shape[1] != 8 or not table.is_contiguous():
         raise ValueError("euler_ancestral_step: table must be a contiguous [steps][8] fp32 tensor")
     if step_idx.dtype != torch.int32:
@@ -1012,16 +1015,12 @@ def x0_linear_step(eps: torch.Tensor, x: torch.Tensor, noise: Optional[torch.Ten
                    pred_type: int = L.PRED_EPSILON) -> torch.Tensor:
     """DDIM / DDPM update, or -- ``pred_type = L.PRED_LCM + L.PRED_*`` -- the latent-consistency update (see da_x0_linear_step),
     + the CFG combine when ``cfg``.  The consistency update needs ``noise``; ``out`` may be the sample (in place)."""
-    _check_sampler("x0_linear_step", x, eps, out, cfg)
+    out = _check_sampler("x0_linear_step", x, eps, out, cfg, out_dtype=x.dtype)
     pred_type = int(pred_type)
     if pred_type not in (0, 1, 2, L.PRED_LCM, L.PRED_LCM + 1, L.PRED_LCM + 2):
         raise ValueError(f"x0_linear_step: pred_type {pred_type} is none of 0-2 (DDIM / DDPM) and 4-6 (consistency update)")
     if pred_type & L.PRED_LCM and noise is None:
         raise ValueError("x0_linear_step: the consistency update (pred_type 4-6) needs `noise`")
-    if out is None:
-        out = torch.empty_like(x)
-    elif out.dtype != x.dtype:
-        raise TypeError("x0_linear_step: out must have the sample's dtype")
     if noise is not None:
         _req(noise, "noise", None)
         if noise.dtype != x.dtype or not noise.is_contiguous():
@@ -1041,13 +1040,9 @@ def flowmatch_step(v: torch.Tensor, x: torch.Tensor, table: torch.Tensor, step_i
     """FlowMatch-Euler update.  The result has the MODEL OUTPUT's dtype, as in the reference (the sample is upcast to
     fp32 for the update and the result cast ``.to(model_output.dtype)``): (sample, model output) = bf16/bf16, f32/f32 or
     f32/bf16 -- the last is what the reference's Wan loop passes on its first step."""
-    _check_sampler("flowmatch_step", x, v, out, cfg, same_dtype=False)
+    out = _check_sampler("flowmatch_step", x, v, out, cfg, same_dtype=False, out_dtype=v.dtype)
     if (_dt(x), _dt(v)) not in ((L.DTYPE_BF16, L.DTYPE_BF16), (L.DTYPE_F32, L.DTYPE_F32), (L.DTYPE_F32, L.DTYPE_BF16)):
         raise TypeError("flowmatch_step: (sample, model output) dtypes must be bf16/bf16, f32/f32 or f32/bf16")
-    if out is None:
-        out = torch.empty(x.shape, device=x.device, dtype=v.dtype)
-    elif out.dtype != v.dtype:
-        raise TypeError("flowmatch_step: out must have the model output's dtype (the reference casts the result to it)")
     L.check(L.load().da_flowmatch_step(v.data_ptr(), x.data_ptr(), out.data_ptr(), table.data_ptr(),
                                        step_idx.data_ptr(), int(cfg), guidance, x.numel(), _dt(v), _dt(x), _stream()),
             "da_flowmatch_step")
