@@ -33,6 +33,8 @@ _EXPORTS = {
     "DPMSolverMultistepScheduler": "schedulers",
     "EulerAncestralDiscreteScheduler": "schedulers",
     "LCMScheduler": "schedulers",
+    "HeunDiscreteScheduler": "schedulers",
+    "KDPM2DiscreteScheduler": "schedulers",
     "StableDiffusionPipeline": "pipelines",
     "StableDiffusionXLPipeline": "pipelines",
     "StableDiffusionImg2ImgPipeline": "pipelines",

@@ -36,6 +36,7 @@ SPLITK_MAX = 24              # DA_SPLITK_MAX
 PRED_EPSILON, PRED_V, PRED_SAMPLE = 0, 1, 2
 PRED_TYPES = {"epsilon": PRED_EPSILON, "v_prediction": PRED_V, "sample": PRED_SAMPLE}
 PRED_LCM = 4                 # da_x0_linear_step only: added to a PRED_*, selects the latent-consistency update (LCMScheduler)
+PRED_SECOND_ORDER = 8        # da_dpmpp_2m_step only: added to a PRED_*, selects the Heun / DPM2 predictor-corrector step
 
 
 class GemmParams(C.Structure):

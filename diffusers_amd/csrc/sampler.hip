@@ -5,6 +5,7 @@
 //                      pipelines/stable_diffusion_xl/pipeline_stable_diffusion_xl.py:1223-1225
 //   Euler              schedulers/scheduling_euler_discrete.py:326-348 (scale_model_input), :685-800 (step)
 //   Euler ancestral    schedulers/scheduling_euler_ancestral_discrete.py (step; per-step noise from a pre-drawn table)
+//   Heun, DPM2         schedulers/scheduling_heun_discrete.py, scheduling_k_dpm_2_discrete.py (step; one kernel, the phase in the row)
 //   DDIM               schedulers/scheduling_ddim.py:384-514
 //   DDPM               schedulers/scheduling_ddpm.py:461-567
 //   FlowMatch Euler    schedulers/scheduling_flow_match_euler_discrete.py:423-523
@@ -434,6 +435,57 @@ __global__ void dpmpp_2m_step_kernel(const TV* __restrict__ eps, TX* __restrict_
   }
 }
 
+// Second-order single-step samplers -- Heun (Karras et al. 2022, Alg. 1 without churn; HeunDiscreteScheduler) and DPM2 (k-diffusion
+// sample_dpm_2; KDPM2DiscreteScheduler) -- as the reference models them: 2n - 1 schedule entries, predictor and corrector alternating,
+// one model call per entry.  ONE kernel serves every entry; what an entry is stands in its row:
+//   row = [sigma_eval, c_hist, dt_x, sqrt(sigma_eval^2+1), c_out, sigma_eval^2+1, phase, timestep]
+// slots 0, 3, 4, 5, 7 are the Euler row (euler_scale_input_kernel and the U-Net's sinusoid read the same table).  With x0 = x0_sigma at
+// sigma_eval and d = (x - x0) / sigma_eval:
+//   phase 0 (Euler entry)   x <- x + dt_x d
+//   phase 1 (predictor)     m1 <- x + c_hist d,  x <- x + dt_x d
+//   phase 2 (corrector)     x <- m1 + dt_x d                                   (m1 is left as it is)
+// Both samplers get by with the one fp32 buffer m1: Heun's x + dt (d + d') / 2 = (x + (dt/2) d) + (dt/2) d' (c_hist = dt/2, the
+// corrector's dt_x = dt/2), DPM2's x + dt d_mid keeps m1 = x (c_hist = 0).  fp32 arithmetic, one rounding at the store of x, as
+// dpmpp_2m_step_kernel; the phase is uniform over the launch.  TX = dtype of the sample, TV = dtype of the model output.
+template <typename TV, int PRED>
+__device__ __forceinline__ float sigma_slope(const EulerCoef& k, float e, float s) {
+  return __fdiv_rn(__fsub_rn(s, x0_sigma<TV, PRED>(k, e, s)), k.sigma);
+}
+
+// n_vec as in dpmpp_2m_step_kernel.
+template <typename TX, typename TV, bool CFG, int PRED>
+__global__ void second_order_step_kernel(const TV* __restrict__ eps, TX* __restrict__ x, float* __restrict__ m1,
+                                         const float* __restrict__ table, const int* __restrict__ step_idx, float g, size_t n,
+                                         size_t n_vec) {
+  const float* row = table + (size_t)(*step_idx) * 8;
+  const EulerCoef k = {row[0], row[2], row[4], row[5]};
+  const float c_hist = row[1];
+  const int phase = (int)row[6];
+  const bool predictor = phase == 1, corrector = phase == 2;
+  EW_EACH4(i, n_vec) {
+    float e[4], xs[4], base[4], h[4], xn[4];
+    LOAD_EPS4(TV, CFG, eps, i, n, g, e);
+    Vec4<TX>::ld(x, i, xs);
+    if (corrector) Vec4<float>::ld(m1, i, base);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const float d = sigma_slope<TV, PRED>(k, e[j], xs[j]);
+      h[j] = __fadd_rn(xs[j], __fmul_rn(c_hist, d));
+      xn[j] = __fadd_rn(corrector ? base[j] : xs[j], __fmul_rn(k.dt, d));
+    }
+    if (predictor) Vec4<float>::st(m1, i, h);
+    Vec4<TX>::st(x, i, xn);
+  }
+  EW_TAIL(i, n_vec, n) {
+    const float e = load_eps<TV, CFG>(eps, i, n, g);
+    const float xs = IO<TX>::ld(x, i);
+    const float d = sigma_slope<TV, PRED>(k, e, xs);
+    const float base = corrector ? m1[i] : xs;
+    if (predictor) m1[i] = __fadd_rn(xs, __fmul_rn(c_hist, d));
+    IO<TX>::st(x, i, __fadd_rn(base, __fmul_rn(k.dt, d)));
+  }
+}
+
 // Euler ancestral ("Euler a", schedulers/scheduling_euler_ancestral_discrete.py step):
 //   row = [sigma, sigma_to, dt = sigma_down - sigma, sqrt(sigma^2+1), c_out, sigma^2+1, sigma_up, timestep]
 // slots 0, 1, 3, 4, 5, 7 are the Euler row (euler_scale_input_kernel reads slot 3 of the same table); dt and sigma_up are evaluated
@@ -745,7 +797,10 @@ extern "C" int da_dpmpp_2m_step(const void* eps, void* x, float* m1, const float
                                 const int* begin_idx, int cfg, float guidance, long long n_, int x_dtype, int e_dtype,
                                 int pred_type, void* stream) {
   if (!eps || !x || !m1 || !table || !step_idx || !begin_idx || n_ <= 0) return DA_ERR_INVALID;
-  if (pred_type < 0 || pred_type > 2) return DA_ERR_INVALID;
+  // bit 3 (DA_PRED_SECOND_ORDER) selects the predictor / corrector step of Heun and DPM2; the low bits stay the prediction type
+  const bool second_order = (pred_type & DA_PRED_SECOND_ORDER) != 0;
+  const int pred = pred_type & ~DA_PRED_SECOND_ORDER;
+  if (pred_type < 0 || pred < 0 || pred > 2) return DA_ERR_INVALID;
   if ((x_dtype != DA_DTYPE_BF16 && x_dtype != DA_DTYPE_F32) || (e_dtype != DA_DTYPE_BF16 && e_dtype != DA_DTYPE_F32))
     return DA_ERR_UNSUPPORTED;
   const size_t n = (size_t)n_;
@@ -754,9 +809,15 @@ extern "C" int da_dpmpp_2m_step(const void* eps, void* x, float* m1, const float
   // 4-byte elements (a bf16 model output is read 8 bytes at a time and would need no more)
   const VecSplit vs = vec_split((uintptr_t)eps | (uintptr_t)x | (uintptr_t)m1, sizeof(float), n, cfg);
   return dispatch_dtype(x_dtype, [&](auto tx) {
-    return dispatch_step<3>(e_dtype, cfg, pred_type, [&](auto tv, auto c, auto p) {
+    return dispatch_step<3>(e_dtype, cfg, pred, [&](auto tv, auto c, auto p) {
       using TX = type_of<decltype(tx)>;
       using TV = type_of<decltype(tv)>;
+      if (second_order) {
+        DA_LAUNCH((second_order_step_kernel<TX, TV, c.value, p.value>), ew_grid(vs.work), dim3(256), 0, s, (const TV*)eps, (TX*)x,
+                  m1, table, step_idx, guidance, n, vs.n_vec);
+        DA_CHECK_LAUNCH();
+        return DA_OK;
+      }
       DA_LAUNCH((dpmpp_2m_step_kernel<TX, TV, c.value, p.value>), ew_grid(vs.work), dim3(256), 0, s, (const TV*)eps, (TX*)x, m1,
                 table, step_idx, begin_idx, guidance, n, vs.n_vec);
       DA_CHECK_LAUNCH();

@@ -16,7 +16,8 @@ from .pipelines import (DDPMPipeline, FluxImg2ImgPipeline, FluxInpaintPipeline, 
 from .schedulers import DDPMScheduler
 from .unet_2d import UNet2DModel
 from .transformer_wan import WanTransformer3DModel
-from .schedulers import DDIMScheduler, EulerDiscreteScheduler, FlowMatchEulerDiscreteScheduler, LCMScheduler
+from .schedulers import (DDIMScheduler, EulerDiscreteScheduler, FlowMatchEulerDiscreteScheduler, HeunDiscreteScheduler,
+                         KDPM2DiscreteScheduler, LCMScheduler)
 from .transformer_flux import FluxTransformer2DModel
 from .unet_2d_condition import UNet2DConditionModel
 
@@ -41,13 +42,24 @@ LCM_SCHEDULER = dict(beta_start=0.00085, beta_end=0.012, beta_schedule="scaled_l
                      timestep_scaling=10.0)
 
 
+# the second-order single-step samplers ("Heun", "DPM2") on the same betas: HeunDiscreteScheduler(**SECOND_ORDER_SCHEDULER),
+# KDPM2DiscreteScheduler(**SECOND_ORDER_SCHEDULER); n steps are 2n - 1 model calls
+SECOND_ORDER_SCHEDULER = dict(beta_start=0.00085, beta_end=0.012, beta_schedule="scaled_linear", steps_offset=1,
+                              timestep_spacing="leading")
+
+
 def _scheduler_for(scheduler: Optional[str], default):
-    """``scheduler=None``: the pipeline's usual one (``default()``); ``"lcm"``: LCMScheduler."""
+    """``scheduler=None``: the pipeline's usual one (``default()``); ``"lcm"``: LCMScheduler; ``"heun"`` / ``"kdpm2"``:
+    HeunDiscreteScheduler / KDPM2DiscreteScheduler."""
     if scheduler is None:
         return default()
     if scheduler == "lcm":
         return LCMScheduler(**LCM_SCHEDULER)
-    raise ValueError("scheduler must be None (the pipeline's default) or 'lcm'")
+    if scheduler == "heun":
+        return HeunDiscreteScheduler(**SECOND_ORDER_SCHEDULER)
+    if scheduler == "kdpm2":
+        return KDPM2DiscreteScheduler(**SECOND_ORDER_SCHEDULER)
+    raise ValueError("scheduler must be None (the pipeline's default), 'lcm', 'heun' or 'kdpm2'")
 
 
 def build_unet(cfg: dict, seed: int = 0, device="cuda", init_device: Optional[str] = None, state_dict=None):

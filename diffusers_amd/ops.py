@@ -1086,6 +1086,30 @@ def dpmpp_2m_step_(eps: torch.Tensor, x: torch.Tensor, m1: torch.Tensor, table: 
     return x
 
 
+def second_order_step_(eps: torch.Tensor, x: torch.Tensor, m1: torch.Tensor, table: torch.Tensor, step_idx: torch.Tensor,
+                       begin_idx: torch.Tensor, *, cfg: bool = False, guidance: float = 0.0,
+                       pred_type: int = L.PRED_EPSILON) -> torch.Tensor:
+    """IN PLACE entry of a second-order single-step sampler (Heun, DPM2; see da_dpmpp_2m_step with DA_PRED_SECOND_ORDER): the
+    row's phase says whether x <- the Euler / predictor step (a predictor also writes m1, fp32, the sample's size) or the
+    corrector step from m1.  ``pred_type`` is a plain L.PRED_*; sample and model output are bf16 or fp32, independently."""
+    require_hip(x, "sample", (bf16, torch.float32)), require_hip(eps, "model_output", (bf16, torch.float32))
+    require_hip(m1, "m1", (torch.float32,))
+    _check_sampler("second_order_step_", x, eps, None, cfg, same_dtype=False)
+    if m1.numel() != x.numel() or not m1.is_contiguous():
+        raise ValueError("second_order_step_: the history m1 must be a contiguous fp32 tensor of the sample's size")
+    for t_, name, dt in ((table, "table", torch.float32), (step_idx, "step_idx", torch.int32), (begin_idx, "begin_idx", torch.int32)):
+        _req(t_, name, dt)
+    if table.dim() != 2 or table.shape[1] != 8 or not table.is_contiguous():
+        raise ValueError("second_order_step_: table must be a contiguous [entries][8] fp32 tensor")
+    pred_type = int(pred_type)
+    if pred_type not in (L.PRED_EPSILON, L.PRED_V, L.PRED_SAMPLE):
+        raise ValueError(f"second_order_step_: pred_type {pred_type} is none of epsilon (0), v_prediction (1), sample (2)")
+    L.check(L.load().da_dpmpp_2m_step(eps.data_ptr(), x.data_ptr(), m1.data_ptr(), table.data_ptr(), step_idx.data_ptr(),
+                                      begin_idx.data_ptr(), int(cfg), float(guidance), x.numel(), _dt(x), _dt(eps),
+                                      L.PRED_SECOND_ORDER | pred_type, _stream()), "da_dpmpp_2m_step")
+    return x
+
+
 def cfg_rescale(eps2b: torch.Tensor, guidance: float, guidance_rescale: float, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """``rescale_noise_cfg`` after the CFG combine (pipeline_stable_diffusion.py:69-92): eps2b [2B][...] = (uncond, cond) ->
     [B][...] guided and rescaled noise prediction, rounding as the reference's op chain does.  Two launches (per-sample

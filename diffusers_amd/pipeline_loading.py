@@ -95,7 +95,7 @@ class PipelineLoadingMixin:
             if klass is None:
                 raise NotImplementedError(
                     f"{slot}: the engine has no {class_name} (its samplers: DDIM, DDPM, DPMSolverMultistep, EulerAncestralDiscrete, "
-                    f"EulerDiscrete, FlowMatchEulerDiscrete, LCM, UniPCMultistep; its models: the U-Nets, DiTs and VAEs of SURVEY.md 8a) -- pass `{slot}=` yourself")
+                    f"EulerDiscrete, FlowMatchEulerDiscrete, HeunDiscrete, KDPM2Discrete, LCM, UniPCMultistep; its models: the U-Nets, DiTs and VAEs of SURVEY.md 8a) -- pass `{slot}=` yourself")
             if (sub / SCHEDULER_CONFIG).is_file():
                 return klass.from_config(json.loads((sub / SCHEDULER_CONFIG).read_text()))
             return klass.from_pretrained(root, subfolder=slot, variant=variant, device=device, cache_packed=cache_packed)

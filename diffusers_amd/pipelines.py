@@ -25,7 +25,8 @@ from . import ops
 from .autoencoder_kl import AutoencoderKL
 from .pipeline_loading import PipelineLoadingMixin
 from .schedulers import (DDPMScheduler, DPMSolverMultistepScheduler, EulerAncestralDiscreteScheduler,
-                         EulerDiscreteScheduler, FlowMatchEulerDiscreteScheduler, LCMScheduler, UniPCMultistepScheduler)
+                         EulerDiscreteScheduler, FlowMatchEulerDiscreteScheduler, HeunDiscreteScheduler, KDPM2DiscreteScheduler,
+                         LCMScheduler, UniPCMultistepScheduler)
 from .transformer_flux import FluxTransformer2DModel
 from .transformer_wan import WanTransformer3DModel
 from .unet_2d import UNet2DModel
@@ -667,7 +668,8 @@ class StableDiffusionXLPipeline(_LatentDiffusionBase):
 
     def _takes_custom_schedule(self) -> bool:
         """(whatever else the scheduler is, its own ``set_timesteps`` answers)"""
-        return not isinstance(self.scheduler, (DPMSolverMultistepScheduler, EulerAncestralDiscreteScheduler))
+        return not isinstance(self.scheduler, (DPMSolverMultistepScheduler, EulerAncestralDiscreteScheduler, HeunDiscreteScheduler,
+                                               KDPM2DiscreteScheduler))
 
     def _set_schedule(self, num_inference_steps, timesteps, sigmas):
         if timesteps is not None and sigmas is not None:    # retrieve_timesteps, :142-143
@@ -868,9 +870,11 @@ class _Img2ImgMixin:
         ``get_timesteps``, refused when no step is left."""
         _check_strength(strength)
         self._set_schedule(num_inference_steps, timesteps, sigmas)
-        ts, n_steps, begin = get_timesteps(self.scheduler, len(self.scheduler.timesteps), strength, denoising_start)
+        sch = self.scheduler
+        # (a second-order sampler's schedule has two entries per step but the last: strength counts steps, the loop runs entries)
+        ts, n_steps, begin = get_timesteps(sch, (len(sch.timesteps) + sch.order - 1) // sch.order, strength, denoising_start)
         _no_steps(strength, n_steps)
-        return ts, n_steps, begin
+        return ts, len(ts), begin
 
     def _start_latents(self, image, mask_image, masked_image_latents, height, width, latents, timestep, batch: int, generator,
                        strength: float, add_noise: bool, noise_dtype, padding_mask_crop=None):

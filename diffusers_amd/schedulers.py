@@ -9,6 +9,8 @@ Host side (schedule construction) is numpy / torch-CPU scalar math written to fo
   FlowMatchEulerDiscreteScheduler schedulers/scheduling_flow_match_euler_discrete.py:283-382, :423-523
   DPMSolverMultistepScheduler     schedulers/scheduling_dpmsolver_multistep.py (dpmsolver++, order <= 2; float64 host scalars)
   LCMScheduler                    schedulers/scheduling_lcm.py (latent-consistency sampling; per-step noise, pre-drawn)
+  HeunDiscreteScheduler           schedulers/scheduling_heun_discrete.py (second order: 2n - 1 entries, one fused two-phase step)
+  KDPM2DiscreteScheduler          schedulers/scheduling_k_dpm_2_discrete.py (DPM2; the same step, another table)
 Per-step scalars are evaluated once with fp32 torch scalar ops (same ops, same order as the reference evaluates them
 every step) and stored in a device table of 8 floats per step; a device-resident step counter selects the row, so a
 denoising step is HIP-graph replayable.  ``step_cfg`` additionally fuses the classifier-free-guidance combine.
@@ -1421,3 +1423,200 @@ class DPMSolverMultistepScheduler(_SchedulerBase):
     def step_inplace(self, model_output, sample):
         self._before_step(self.timesteps[0])
         return self._run(model_output, sample, False, 0.0)
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+class _SecondOrderBase(_EulerBase):
+    """What HeunDiscreteScheduler and KDPM2DiscreteScheduler share: second-order single-step samplers the reference runs as
+    2n - 1 schedule entries for n steps -- predictor and corrector alternating, one model call per entry, the step into sigma = 0 a
+    single Euler entry.  Every entry is one row of the device table,
+      [sigma_eval, c_hist, dt_x, sqrt(sigma_eval^2+1), c_out, sigma_eval^2+1, phase, timestep]      phase 0 Euler, 1 predictor, 2 corrector
+    (slots 0, 3, 4, 5, 7 as the Euler row, so ``scale_model_input`` and the U-Net's sinusoid read it unchanged), and ONE kernel
+    (da_dpmpp_2m_step with DA_PRED_SECOND_ORDER) serves every entry: with d = (x - x0) / sigma_eval a predictor stores the history
+    m1 = x + c_hist d and moves x by dt_x d, a corrector writes x = m1 + dt_x d.  The pipelines' captured step is replayed once per
+    entry and never learns which kind it ran.  The sigmas are the ladder EulerDiscreteScheduler forms for the same options, evaluated
+    -- with every other scalar of the rows -- in float64 on the host and rounded once to fp32 (as DPMSolverMultistepScheduler does).
+    ``timesteps`` and ``sigmas`` have one value per entry (``sigmas`` the terminal 0 behind them), so ``add_noise``,
+    ``add_noise_table`` and ``scale_model_input`` work on the noise level the latents of an entry actually have."""
+
+    order = 2
+    _common_defaults = dict(num_train_timesteps=1000, beta_start=0.00085, beta_end=0.012, beta_schedule="linear", trained_betas=None,
+                            prediction_type="epsilon", use_karras_sigmas=False, use_exponential_sigmas=False, use_beta_sigmas=False,
+                            timestep_spacing="linspace", steps_offset=0)
+
+    def __init__(self, **kwargs):
+        super().__init__(**kwargs)
+        c = self.config
+        name = type(self).__name__
+        if c.use_beta_sigmas:
+            raise NotImplementedError(f"{name}: use_beta_sigmas=True is not implemented")
+        if c.get("clip_sample", False):
+            raise NotImplementedError(f"{name}: clip_sample=True is not implemented")
+        if c.use_karras_sigmas and c.use_exponential_sigmas:
+            raise ValueError("Only one of `config.use_beta_sigmas`, `config.use_exponential_sigmas`, "
+                             "`config.use_karras_sigmas` can be used.")
+        if c.prediction_type not in L.PRED_TYPES:
+            raise ValueError(f"{name}: prediction_type={c.prediction_type!r} is not implemented ('epsilon', 'v_prediction' or "
+                             "'sample')")
+        self._pred = L.PRED_TYPES[c.prediction_type]
+        if c.trained_betas is not None:
+            betas = np.asarray(c.trained_betas, dtype=np.float64)
+        elif c.beta_schedule == "linear":
+            betas = np.linspace(c.beta_start, c.beta_end, c.num_train_timesteps, dtype=np.float64)
+        elif c.beta_schedule == "scaled_linear":
+            betas = np.linspace(c.beta_start ** 0.5, c.beta_end ** 0.5, c.num_train_timesteps, dtype=np.float64) ** 2
+        else:
+            raise NotImplementedError(f"{name}: beta_schedule={c.beta_schedule!r} is not implemented ('linear' or 'scaled_linear')")
+        ac = np.cumprod(1.0 - betas)
+        self._sig_all = np.sqrt((1.0 - ac) / ac)            # float64 training ladder, ascending
+        self.betas = torch.from_numpy(betas).float()
+        self.alphas = 1.0 - self.betas
+        self.alphas_cumprod = torch.from_numpy(ac).float()
+        n_train = len(betas)
+        ts = np.linspace(0, n_train - 1, n_train, dtype=float)[::-1].copy()
+        self.timesteps = torch.from_numpy(ts).to(dtype=torch.float32)
+        self._timesteps_host = self.timesteps.numpy()
+        self.sigmas = torch.from_numpy(np.concatenate([self._sig_all[::-1], [0.0]]).astype(np.float32))
+        self.is_scale_input_called = False
+        self._hist = None           # fp32: what a predictor entry leaves for its corrector
+        self.phases = None          # per entry: 0 Euler, 1 predictor, 2 corrector
+
+    # -- the schedule ----------------------------------------------------------------------------------------------------
+    def _ladder(self, n: int):
+        """(sigmas float64 [n + 1] with the terminal 0, timesteps float64 [n]) as EulerDiscreteScheduler.set_timesteps forms them."""
+        c = self.config
+        base = self._sig_all
+        ts = _euler_spaced_timesteps(c.timestep_spacing, len(base), n, c.steps_offset).astype(np.float64)
+        sig = np.interp(ts, np.arange(0, len(base)), base)
+        if c.use_karras_sigmas or c.use_exponential_sigmas:
+            sig = _respaced_sigmas(float(sig[-1]), float(sig[0]), n, karras=c.use_karras_sigmas)     # between the extremes
+            ts = np.array([float(_sigma_to_t(s_, np.log(base))) for s_ in sig])
+        return np.concatenate([sig, [0.0]]), ts
+
+    def _entries(self, sig: np.ndarray, ts: np.ndarray):
+        """Per entry (sigma_eval, c_hist, dt_x, phase, timestep) in float64; the subclass says what its two phases are."""
+        raise NotImplementedError
+
+    def set_timesteps(self, num_inference_steps: int = None, device=None, num_train_timesteps=None, timesteps=None):
+        name = type(self).__name__
+        if timesteps is not None:
+            raise NotImplementedError(f"custom timesteps are not supported by the HIP {name}")
+        if num_inference_steps is None or int(num_inference_steps) < 1:
+            raise ValueError("`num_inference_steps` must be a positive number of steps.")
+        n = int(num_inference_steps)
+        sig, ts = self._ladder(n)
+        if not (np.diff(sig) < 0).all():
+            raise ValueError(f"{name}: the sigmas of a {n}-step schedule do not decrease strictly (more steps than training "
+                             "timesteps?)")
+        ent = np.asarray(self._entries(sig, ts), dtype=np.float64)           # [2n - 1][5]
+        s = ent[:, 0]
+        rows = np.zeros((len(ent), 8), dtype=np.float64)
+        rows[:, 0], rows[:, 1], rows[:, 2] = s, ent[:, 1], ent[:, 2]
+        rows[:, 3], rows[:, 4], rows[:, 5] = np.sqrt(s * s + 1.0), -s / np.sqrt(s * s + 1.0), s * s + 1.0
+        rows[:, 6], rows[:, 7] = ent[:, 3], ent[:, 4]
+        rows = rows.astype(np.float32)
+        if not np.isfinite(rows).all():
+            raise ValueError(f"{name}: non-finite step coefficients")
+        self.phases = [int(p) for p in ent[:, 3]]
+        self.sigmas = torch.from_numpy(np.concatenate([s, [0.0]]).astype(np.float32))    # per entry; kept on the CPU
+        ts32 = ent[:, 4].astype(np.float32)
+        self._set_schedule(n, torch.from_numpy(ts32).to(device=device), ts32, rows, device)
+
+    # -- index bookkeeping -----------------------------------------------------------------------------------------------
+    @property
+    def state_in_first_order(self) -> bool:
+        """True where the next entry is a predictor (or the final Euler entry), as the reference's ``dt is None``."""
+        return self._step_index is None or self._step_index % 2 == 0
+
+    def _refuse_corrector_start(self, index: int):
+        if int(index) % 2:
+            raise ValueError(f"{type(self).__name__}: a loop cannot begin at entry {index}, a corrector (it would read a history "
+                             "no predictor wrote); begin indices are even")
+
+    def set_begin_index(self, begin_index: int = 0):
+        self._refuse_corrector_start(begin_index)
+        super().set_begin_index(begin_index)
+
+    def reset(self, index: int = 0):
+        self._refuse_corrector_start(index)
+        super().reset(index)
+
+    def _before_step(self, timestep):
+        self._require_schedule()
+        if self._step_index is None:
+            self._init_step_index(timestep)
+        if not 0 <= self._step_index < len(self._timesteps_host):
+            raise IndexError(f"{type(self).__name__}: entry {self._step_index} of a schedule of {len(self._timesteps_host)} "
+                             "entries (call set_timesteps() or reset() before another loop)")
+
+    def history(self, sample):
+        """The fp32 history buffer for samples of this size (allocated once: captured graphs hold its address).  A corrector reads
+        what the predictor in front of it wrote and a loop begins on a predictor, so it is not cleared between loops."""
+        if self._hist is None or self._hist.shape != sample.shape or self._hist.device != sample.device:
+            self._hist = torch.zeros(sample.shape, dtype=torch.float32, device=sample.device)
+        return self._hist
+
+    def graph_buffers(self, sample):
+        return (self.history(sample).data_ptr(),)
+
+    # -- the step --------------------------------------------------------------------------------------------------------
+    def _run(self, model_output, sample, cfg, guidance_scale):
+        """The one caller of these classes' fused step (ops.second_order_step_): ``sample`` is updated in place."""
+        ops.second_order_step_(model_output, sample, self.history(sample), self._table, self._step_dev, self._step_dev, cfg=cfg,
+                               guidance=float(guidance_scale), pred_type=self._pred)
+        self._advance()
+        return sample
+
+    def step(self, model_output, timestep, sample, return_dict: bool = True):
+        self._before_step(timestep)
+        return self._result(self._run(model_output.contiguous(), sample.contiguous().clone(), False, 0.0), return_dict)
+
+    def step_cfg(self, model_output_2b, sample, guidance_scale: float, out=None, cfg: bool = True):
+        """Engine extension: CFG combine (``cfg=False``: a plain model output) + the entry, written over ``sample`` (graph replay)."""
+        if out is not None and out.data_ptr() != sample.data_ptr():
+            raise ValueError(f"{type(self).__name__}.step_cfg updates `sample` in place")
+        self._before_step(self.timesteps[0])
+        return self._run(model_output_2b, sample, cfg, guidance_scale)
+
+    def step_inplace(self, model_output, sample):
+        self._before_step(self.timesteps[0])
+        return self._run(model_output, sample, False, 0.0)
+
+
+class HeunDiscreteScheduler(_SecondOrderBase):
+    """schedulers/scheduling_heun_discrete.py ("Heun"): Karras et al. 2022, Alg. 1 without churn.  Step i < n - 1, dt = sigma_{i+1} -
+    sigma_i: the predictor entry evaluates the model at sigma_i and moves x by dt d, the corrector entry evaluates it at sigma_{i+1}
+    and leaves x_i + dt (d + d') / 2 = (x_i + (dt/2) d) + (dt/2) d' -- the bracket is the one history tensor.  ``timesteps`` =
+    [t0, t1, t1, t2, t2, ...]."""
+
+    _defaults = dict(_SecondOrderBase._common_defaults, clip_sample=False, clip_sample_range=1.0)
+
+    def _entries(self, sig, ts):
+        n = len(ts)
+        ent = []
+        for i in range(n - 1):
+            dt = sig[i + 1] - sig[i]
+            ent.append((sig[i], dt / 2, dt, 1, ts[i]))
+            ent.append((sig[i + 1], 0.0, dt / 2, 2, ts[i + 1]))
+        ent.append((sig[n - 1], 0.0, sig[n] - sig[n - 1], 0, ts[n - 1]))
+        return ent
+
+
+class KDPM2DiscreteScheduler(_SecondOrderBase):
+    """schedulers/scheduling_k_dpm_2_discrete.py ("DPM2"): k-diffusion's sample_dpm_2, the midpoint method in log sigma.  Step i <
+    n - 1, sigma_mid = exp((ln sigma_i + ln sigma_{i+1}) / 2): the predictor entry evaluates the model at sigma_i and moves x to
+    sigma_mid, the corrector entry evaluates it there -- at the fractional timestep whose training sigma is sigma_mid -- and leaves
+    x_i + (sigma_{i+1} - sigma_i) d_mid; the history tensor is x_i.  ``timesteps`` = [t0, t_mid01, t1, t_mid12, ..., t_{n-1}]."""
+
+    _defaults = dict(_SecondOrderBase._common_defaults)
+
+    def _entries(self, sig, ts):
+        n = len(ts)
+        log_base = np.log(self._sig_all)
+        ent = []
+        for i in range(n - 1):
+            mid = np.exp((np.log(sig[i]) + np.log(sig[i + 1])) / 2)
+            ent.append((sig[i], 0.0, mid - sig[i], 1, ts[i]))
+            ent.append((mid, 0.0, sig[i + 1] - sig[i], 2, float(_sigma_to_t(mid, log_base))))
+        ent.append((sig[n - 1], 0.0, sig[n] - sig[n - 1], 0, ts[n - 1]))
+        return ent

@@ -452,6 +452,8 @@ int da_rmsnorm_channels_bf16(const void* x, const void* gamma, void* y, long lon
 #define DA_PRED_EPSILON 0
 #define DA_PRED_V 1
 #define DA_PRED_SAMPLE 2
+/* OR-ed into da_dpmpp_2m_step's `pred_type`: the predictor / corrector step of the second-order single-step samplers (Heun, DPM2) */
+#define DA_PRED_SECOND_ORDER 8
 int da_euler_scale_model_input(const void* x, void* out, const float* table, const int* step_idx, int rep, long long n,
                                int dtype, void* stream);
 int da_euler_step(const void* eps, const void* x, void* out, const float* table, const int* step_idx, int cfg,
@@ -484,7 +486,22 @@ int da_unipc_flow_step(const void* v, void* x, void* last, void* m1, void* m2, c
  * x; m1 is an fp32 tensor of n elements whatever the sample's dtype.  row = [alpha_s0, sigma_s0, cx, c0, cd, -, second_order_allowed,
  * timestep]: x' = cx x + c0 x0 [+ cd (x0 - m1)], the bracket only when the row allows it and *step_idx != *begin_idx (the first
  * step of a loop is first order wherever it starts).  fp32 arithmetic, one rounding at the store of x.  x_dtype (sample) and
- * e_dtype (model output) are independent: bf16 or f32 each. */
+ * e_dtype (model output) are independent: bf16 or f32 each.
+ * pred_type | DA_PRED_SECOND_ORDER (8, 9, 10): one entry of a second-order single-step sampler -- Heun (Karras et al. 2022, Alg. 1
+ * without churn; HeunDiscreteScheduler) or DPM2 (k-diffusion sample_dpm_2; KDPM2DiscreteScheduler) -- which the reference runs as
+ * 2n - 1 schedule entries, predictor and corrector alternating, one model call each.  Same arguments; begin_idx is not read; m1 is the
+ * sampler's ONE history buffer.  row = [sigma_eval, c_hist, dt_x, sqrt(sigma_eval^2+1), c_out, sigma_eval^2+1, phase, timestep]
+ * (slots 0, 3, 4, 5, 7 as the Euler row: da_euler_scale_model_input and the U-Net's sinusoid read the same table).  Per element, with
+ * e the guided model output (the CFG combine rounded in the model output's dtype T) and s = float(x):
+ *   x0 = s - T(sigma_eval e)   |   T(e c_out) + s / (sigma_eval^2+1)   |   e                 (epsilon | v_prediction | sample)
+ *   d  = (s - x0) / sigma_eval
+ *   phase 0 (a plain Euler entry)   x <- s + dt_x d
+ *   phase 1 (predictor)             m1 <- s + c_hist d,   x <- s + dt_x d
+ *   phase 2 (corrector)             x <- m1 + dt_x d                       (m1 is left as it is)
+ * every op a correctly rounded fp32 op in the order written (product, then sum), one rounding at the store of x.  Heun: predictor
+ * sigma_eval = sigma_i, dt_x = dt, c_hist = dt / 2; corrector sigma_eval = sigma_{i+1}, dt_x = dt / 2, so that x + dt (d + d') / 2 =
+ * (x + (dt/2) d) + (dt/2) d'.  DPM2: predictor dt_x = sigma_mid - sigma_i, c_hist = 0 (m1 = x); corrector sigma_eval = sigma_mid,
+ * dt_x = sigma_{i+1} - sigma_i.  The phase is read once per launch.  3..7 and >= 11: DA_ERR_INVALID, as before. */
 int da_dpmpp_2m_step(const void* eps, void* x, float* m1, const float* table, const int* step_idx, const int* begin_idx,
                      int cfg, float guidance, long long n, int x_dtype, int e_dtype, int pred_type, void* stream);
 int da_advance_step(int* step_idx, void* stream);
