@@ -267,6 +267,13 @@ class AutoencoderKL(PretrainedMixin):
         self._built = False
         self.post_quant_conv = None
         self.encoder = None
+        # the reference's tiling / slicing attributes (autoencoder_kl.py __init__): plain and settable
+        self.use_tiling = False
+        self.use_slicing = False
+        ss = self.config.sample_size
+        self.tile_sample_min_size = ss[0] if isinstance(ss, (list, tuple)) else ss
+        self.tile_latent_min_size = int(self.tile_sample_min_size / (2 ** (len(self.config.block_out_channels) - 1)))
+        self.tile_overlap_factor = 0.25
 
     def load_state_dict(self, state_dict: Dict[str, torch.Tensor], device="cuda", strict: bool = False):
         """Packs the decoder half (``decoder.*``, ``post_quant_conv.*``) of a reference AutoencoderKL state_dict, and the encoder
@@ -365,17 +372,58 @@ class AutoencoderKL(PretrainedMixin):
         return DiagonalGaussianDistribution(self.encoder, raw, strides, (B, H // f, W_ // f),
                                             torch.float32 if self.config.force_upcast else bf16)
 
-    def decode(self, z: torch.Tensor, return_dict: bool = True, generator=None, *, latents_div: float = 1.0,
-               latents_add: float = 0.0, postprocess: Optional[str] = None):
-        """autoencoder_kl.py:214-240.  ``latents_div`` / ``latents_add`` fuse the pipeline's
-        ``latents / scaling_factor (+ shift_factor)`` (pipeline_stable_diffusion_xl.py:1283, pipeline_flux.py:960) into
-        the first conv's input read.  ``postprocess`` ("pt" / "np" / "uint8") fuses the pipeline's
-        ``image_processor.postprocess`` (image_processor.py:738-786) into the last pass of ``conv_out``: the sample is then the
-        finished image ([0, 1] fp32 NCHW / NHWC, or NHWC bytes) instead of the bf16 decoder output in [-1, 1]."""
-        if not self._built:
-            raise RuntimeError("AutoencoderKL: call load_state_dict() first")
-        ops.require_hip(z, "z")
-        z = z.contiguous()
+    # ---- tiling / slicing (autoencoder_kl.py enable_tiling / enable_slicing / tiled_decode) ----
+    def enable_tiling(self, use_tiling: bool = True):
+        self.use_tiling = use_tiling
+
+    def disable_tiling(self):
+        self.enable_tiling(False)
+
+    def enable_slicing(self):
+        self.use_slicing = True
+
+    def disable_slicing(self):
+        self.use_slicing = False
+
+    def _tile_plan(self, H: int, W: int):
+        """The reference's tiled_decode bookkeeping for an H x W latent grid, host only: ``(E, rows, image_h, image_w)`` with ``E`` the
+        blend extent and ``rows`` the tiles in decode order, each a dict -- latent slice (``i``, ``j``, ``lh``, ``lw``; edge tiles are
+        smaller), decoded size (``h``, ``w``), the piece kept (``keep_h``, ``keep_w`` = the tile cropped to ``row_limit``) and where the
+        concatenations put it (``y0``, ``x0``: the running sums of the pieces before it; the image size is the sum of the pieces)."""
+        tl, S, factor = self.tile_latent_min_size, self.tile_sample_min_size, self.tile_overlap_factor
+        up = 2 ** (len(self.config.block_out_channels) - 1)
+        overlap = int(tl * (1 - factor))
+        E = int(S * factor)
+        row_limit = S - E
+        if overlap < 1:
+            raise ValueError(f"tile_latent_min_size = {tl} with tile_overlap_factor = {factor} gives overlap_size = {overlap} < 1: the "
+                             "tiles would not advance")
+        if E < 0 or row_limit < 1:
+            raise ValueError(f"tile_sample_min_size = {S} with tile_overlap_factor = {factor} gives blend_extent = {E} and row_limit = "
+                             f"{row_limit}: nothing of a tile would be kept")
+        starts = [list(range(0, n, overlap)) for n in (H, W)]
+        for name, n, st in zip(("rows", "columns"), (H, W), starts):
+            for a in st[:-1]:                                    # every tile but the last is some tile's upper / left neighbour
+                if min(tl, n - a) * up < E:
+                    raise ValueError(f"tile_sample_min_size = {S} with tile_overlap_factor = {factor} gives blend_extent = {E}, more "
+                                     f"than the {min(tl, n - a) * up} {name} of a tile that is blended into its neighbour "
+                                     f"(tile_latent_min_size = {tl}, latent grid {H} x {W})")
+        rows, y0 = [], 0
+        for i in starts[0]:
+            lh = min(tl, H - i)
+            row, x0 = [], 0
+            for j in starts[1]:
+                lw = min(tl, W - j)
+                t = dict(i=i, j=j, lh=lh, lw=lw, h=lh * up, w=lw * up, keep_h=min(lh * up, row_limit), keep_w=min(lw * up, row_limit),
+                         y0=y0, x0=x0)
+                row.append(t)
+                x0 += t["keep_w"]
+            rows.append(row)
+            y0 += row[0]["keep_h"]
+        return E, rows, y0, x0
+
+    def _trunk(self, z: torch.Tensor, latents_div: float, latents_add: float) -> torch.Tensor:
+        """post_quant_conv ... conv_norm_out + SiLU on contiguous NCHW latents: the NHWC input of conv_out."""
         if self.post_quant_conv:
             x = ops.conv_thin_in(z, self.pqc_w, self.pqc_b, ksize=1, in_nchw=True, in_div=latents_div, in_add=latents_add)
             x = ops.conv_thin_in(x, self.conv_in_w, self.conv_in_b, ksize=3, in_nchw=False)
@@ -391,8 +439,84 @@ class AutoencoderKL(PretrainedMixin):
                 x = rn(x)
             if st["up"] is not None:
                 x = st["up"](x)
-        x = self.conv_norm_out(x, silu=True)
-        img = ops.conv_thin_out(x, self.conv_out_w, self.conv_out_b, postprocess=postprocess)
+        return self.conv_norm_out(x, silu=True)
+
+    def _decode(self, z: torch.Tensor, latents_div: float, latents_add: float, postprocess: Optional[str]) -> torch.Tensor:
+        return ops.conv_thin_out(self._trunk(z, latents_div, latents_add), self.conv_out_w, self.conv_out_b, postprocess=postprocess)
+
+    def _decode_tile(self, z: torch.Tensor, latents_div: float, latents_add: float):
+        """One tile up to conv_out, its result left where the conv wrote it: ``(raw, (sB, sC, sP))``."""
+        return ops.conv_thin_out_tile(self._trunk(z, latents_div, latents_add), self.conv_out_w, self.conv_out_b)
+
+    def _image_like(self, B: int, H: int, W: int, postprocess: Optional[str], device) -> torch.Tensor:
+        """The empty result of a decode: what ops.conv_thin_out returns for ``postprocess``."""
+        C = self.config.out_channels
+        if postprocess in ("np", "uint8"):
+            return torch.empty((B, H, W, C), device=device, dtype=torch.uint8 if postprocess == "uint8" else torch.float32)
+        if postprocess not in (None, "pt"):
+            raise ValueError(f"AutoencoderKL.decode: postprocess={postprocess!r} (use 'pt', 'np' or 'uint8')")
+        return torch.empty((B, C, H, W), device=device, dtype=bf16 if postprocess is None else torch.float32)
+
+    def _tiled_decode(self, z: torch.Tensor, latents_div: float, latents_add: float, postprocess: Optional[str],
+                      out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """autoencoder_kl.py tiled_decode: tiles decoded and blended in the reference's order, one ops.vae_tile_blend launch per tile
+        in place of its blend loops, crops, concatenations and the image processor.  Of the blended tiles only the previous row and
+        the current one stay alive."""
+        B, C = z.shape[0], self.config.out_channels
+        if C > 4:
+            raise NotImplementedError(f"AutoencoderKL: tiled decode of {C} image channels (the tile-blend kernel takes at most 4)")
+        E, rows, IH, IW = self._tile_plan(z.shape[2], z.shape[3])
+        if out is None:
+            out = self._image_like(B, IH, IW, postprocess, z.device)
+        above = None
+        for r, row in enumerate(rows):
+            done = []
+            for c, t in enumerate(row):
+                tile = z[:, :, t["i"]:t["i"] + t["lh"], t["j"]:t["j"] + t["lw"]].contiguous()
+                raw, strides = self._decode_tile(tile, latents_div, latents_add)
+                fin = ops.vae_tile_blend(raw, strides, batch=B, channels=C, height=t["h"], width=t["w"], image=out, y0=t["y0"],
+                                         x0=t["x0"], keep_h=t["keep_h"], keep_w=t["keep_w"], postprocess=postprocess, extent=E,
+                                         up=above[c] if above is not None else None, left=done[-1] if done else None,
+                                         want_fin=r + 1 < len(rows) or c + 1 < len(row))
+                done.append(fin)
+            above = done
+        return out
+
+    def decode(self, z: torch.Tensor, return_dict: bool = True, generator=None, *, latents_div: float = 1.0,
+               latents_add: float = 0.0, postprocess: Optional[str] = None):
+        """autoencoder_kl.py:214-240.  ``latents_div`` / ``latents_add`` fuse the pipeline's
+        ``latents / scaling_factor (+ shift_factor)`` (pipeline_stable_diffusion_xl.py:1283, pipeline_flux.py:960) into
+        the first conv's input read.  ``postprocess`` ("pt" / "np" / "uint8") fuses the pipeline's
+        ``image_processor.postprocess`` (image_processor.py:738-786) into the last pass of ``conv_out``: the sample is then the
+        finished image ([0, 1] fp32 NCHW / NHWC, or NHWC bytes) instead of the bf16 decoder output in [-1, 1].
+        ``use_tiling`` (``enable_tiling()``): a latent grid larger than ``tile_latent_min_size`` either way is decoded as the
+        reference's ``tiled_decode`` does -- overlapping tiles, each normalised on its own, seams blended -- and ``postprocess`` is
+        applied as each tile is placed.  ``use_slicing`` (``enable_slicing()``): a batch is decoded sample by sample."""
+        if not self._built:
+            raise RuntimeError("AutoencoderKL: call load_state_dict() first")
+        ops.require_hip(z, "z")
+        z = z.contiguous()
+        tl = self.tile_latent_min_size
+        tiled = self.use_tiling and (z.shape[-1] > tl or z.shape[-2] > tl)
+        if self.use_slicing and z.shape[0] > 1:
+            img = None
+            for b in range(z.shape[0]):
+                if tiled:
+                    if img is None:
+                        _, _, IH, IW = self._tile_plan(z.shape[2], z.shape[3])
+                        img = self._image_like(z.shape[0], IH, IW, postprocess, z.device)
+                    self._tiled_decode(z[b:b + 1], latents_div, latents_add, postprocess, out=img[b:b + 1])
+                else:
+                    # (conv_out's layout pass allocates its own result, so an untiled slice costs one extra copy of the image; the
+                    # tiled path above writes the output in place)
+                    one = self._decode(z[b:b + 1], latents_div, latents_add, postprocess)
+                    if img is None:
+                        img = torch.empty((z.shape[0],) + tuple(one.shape[1:]), device=one.device, dtype=one.dtype)
+                    img[b:b + 1].copy_(one)
+        elif tiled:
+            img = self._tiled_decode(z, latents_div, latents_add, postprocess)
+        else:
+            img = self._decode(z, latents_div, latents_add, postprocess)
         if not return_dict:
             return (img,)
         return DecoderOutput(sample=img)

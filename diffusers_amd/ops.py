@@ -1553,6 +1553,82 @@ def conv_thin_out_moments(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch
     return y, (Cout * H * W_, H * W_, 1)
 
 
+def conv_thin_out_tile(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor]):
+    """The decoder's conv_out (Cin -> at most 4 image channels) of ONE TILE of a tiled decode, without conv_thin_out's layout /
+    postprocess pass: ``(y, (sB, sC, sP))`` as conv_thin_out_moments hands the encoder's result on, for vae_tile_blend to read in
+    place.  Same values as conv_thin_out."""
+    if w.shape[0] > 4:
+        raise ValueError(f"conv_thin_out_tile: at most 4 output channels (the tile-blend kernel's limit), got {w.shape[0]}")
+    return conv_thin_out_moments(x, w, bias)
+
+
+_blend_weight_cache = {}
+
+
+def tile_blend_weights(extent: int, device) -> torch.Tensor:
+    """fp32 [E][2] = (float32(1 - k / E), float32(k / E)), both evaluated in float64 first: the scalars the reference's blend_v /
+    blend_h multiply bf16 tensors with.  Cached per (E, device)."""
+    E, device = int(extent), torch.device(device)
+    if E < 1:
+        raise ValueError(f"tile_blend_weights: blend extent {E} < 1")
+    key = (E, device)
+    t = _blend_weight_cache.get(key)
+    if t is None:
+        t = _blend_weight_cache[key] = torch.tensor([[1 - k / E, k / E] for k in range(E)], dtype=torch.float64).float().to(device)
+    return t
+
+
+def vae_tile_blend(src: torch.Tensor, strides, *, batch: int, channels: int, height: int, width: int, image: torch.Tensor,
+                   y0: int, x0: int, keep_h: int, keep_w: int, postprocess: Optional[str] = None, extent: int = 0,
+                   up: Optional[torch.Tensor] = None, left: Optional[torch.Tensor] = None, want_fin: bool = True):
+    """da_vae_tile_blend (csrc/vae_tile.hip; arithmetic in include/diffusers_amd.h): one tile of a tiled AutoencoderKL.decode.
+    ``src``: the tile's conv_out result read through ``strides`` = (sB, sC, sP) in elements (conv_thin_out_tile); ``up`` / ``left``: the
+    finished neighbours, contiguous NCHW bf16 [B][C][hu][width] / [B][C][height][wl]; ``extent``: the reference's blend_extent.  The
+    rectangle ``keep_h`` x ``keep_w`` of the blended tile is written at (``y0``, ``x0``) of ``image``: NCHW bf16 (``postprocess`` None),
+    NCHW fp32 ("pt"), NHWC fp32 ("np") or NHWC uint8 ("uint8").  Returns the blended tile, NCHW bf16 (None unless ``want_fin``).
+    Runs once per tile and has no plan number: refused while a launch plan is being recorded."""
+    if getattr(L._tls, "recorder", None) is not None:
+        raise RuntimeError("vae_tile_blend: not replayable by a launch plan (da_vae_tile_blend has no DA_FN_* number); decode outside "
+                           "the recording")
+    _req(src, "src")
+    B, C, h, w, E = int(batch), int(channels), int(height), int(width), int(extent)
+    if postprocess is not None and postprocess not in _PP_MODES:
+        raise ValueError(f"vae_tile_blend: postprocess={postprocess!r} (use None, 'pt', 'np' or 'uint8')")
+    mode = -1 if postprocess is None else _PP_MODES[postprocess]
+    if min(B, C, h, w) < 1 or C > 4 or E < 0:
+        raise ValueError(f"vae_tile_blend: a positive tile with 1 .. 4 channels and extent >= 0 required, got B = {B}, C = {C}, "
+                         f"{h} x {w}, extent = {E}")
+    sB, sC, sP = (int(v) for v in strides)
+    # a channels-last source with slots of >= 4 elements is read 4 channels at a time (the header's contract): whole slots must exist
+    last = (B - 1) * sB + ((C - 1) * sC if not (sC == 1 and sP >= 4) else 3) + (h * w - 1) * sP
+    if min(sB, sC, sP) < 0 or last >= src.numel():
+        raise ValueError(f"vae_tile_blend: strides {strides} reach element {last} of a {src.numel()}-element input")
+    hu = wl = 0
+    if up is not None:
+        _req(up, "up")
+        hu = up.shape[2] if up.dim() == 4 else -1
+        if not up.is_contiguous() or up.dim() != 4 or tuple(up.shape) != (B, C, hu, w) or hu < E:
+            raise ValueError(f"vae_tile_blend: up must be contiguous [{B}][{C}][>= {E}][{w}], got {tuple(up.shape)}")
+    if left is not None:
+        _req(left, "left")
+        wl = left.shape[3] if left.dim() == 4 else -1
+        if not left.is_contiguous() or left.dim() != 4 or tuple(left.shape) != (B, C, h, wl) or wl < E:
+            raise ValueError(f"vae_tile_blend: left must be contiguous [{B}][{C}][{h}][>= {E}], got {tuple(left.shape)}")
+    require_hip(image, "image", dtypes=(bf16 if mode < 0 else torch.uint8 if mode == 2 else torch.float32,))
+    if image.dim() != 4 or not image.is_contiguous() or image.shape[0] != B or image.shape[1 if mode <= 0 else 3] != C:
+        raise ValueError(f"vae_tile_blend: image must be contiguous, batch {B}, {C} channels ({'NCHW' if mode <= 0 else 'NHWC'}), got "
+                         f"{tuple(image.shape)}")
+    IH, IW = (image.shape[2], image.shape[3]) if mode <= 0 else (image.shape[1], image.shape[2])
+    if not (1 <= keep_h <= h and 1 <= keep_w <= w and 0 <= y0 and 0 <= x0 and y0 + keep_h <= IH and x0 + keep_w <= IW):
+        raise ValueError(f"vae_tile_blend: rectangle {keep_h} x {keep_w} at ({y0}, {x0}) of a {h} x {w} tile in a {IH} x {IW} image")
+    wt = tile_blend_weights(E, src.device) if E > 0 and (up is not None or left is not None) else None
+    fin = torch.empty((B, C, h, w), device=src.device, dtype=bf16) if want_fin else None
+    L.check(L.load().da_vae_tile_blend(src.data_ptr(), sB, sC, sP, _ptr(up), hu, _ptr(left), wl, _ptr(wt), E, _ptr(fin),
+                                       image.data_ptr(), B, C, h, w, int(keep_h), int(keep_w), IH, IW, int(y0), int(x0), mode,
+                                       _stream()), "da_vae_tile_blend")
+    return fin
+
+
 def vae_posterior_latents(x: torch.Tensor, strides, *, batch: int, hw: int, latent_channels: int, mode: int,
                           wq: Optional[torch.Tensor] = None, bq: Optional[torch.Tensor] = None, eps1: Optional[torch.Tensor] = None,
                           eps2: Optional[torch.Tensor] = None, shift: Optional[float] = None, scale: Optional[float] = None,

@@ -379,12 +379,36 @@ class _StepCallbacks:
         return not self._interrupt
 
 
+class _VaeTilingMixin:
+    """``enable_vae_tiling()`` / ``enable_vae_slicing()`` and their opposites, forwarded to the pipeline's ``vae`` (the reference's
+    pipeline methods).  The VAE sits outside the captured step: toggling them recaptures nothing."""
+
+    def _vae_switch(self, method: str, *args):
+        fn = getattr(self.vae, method, None)
+        if fn is None:
+            raise NotImplementedError(f"{type(self.vae).__name__} has no {method}(): tiled / sliced decoding is built for "
+                                      "AutoencoderKL only")
+        fn(*args)
+
+    def enable_vae_tiling(self):
+        self._vae_switch("enable_tiling")
+
+    def disable_vae_tiling(self):
+        self._vae_switch("disable_tiling")
+
+    def enable_vae_slicing(self):
+        self._vae_switch("enable_slicing")
+
+    def disable_vae_slicing(self):
+        self._vae_switch("disable_slicing")
+
+
 @dataclass
 class PipelineOutput:
     images: torch.Tensor
 
 
-class _LatentDiffusionBase(_StepCallbacks, _CapturedStepLoop, PipelineLoadingMixin):
+class _LatentDiffusionBase(_VaeTilingMixin, _StepCallbacks, _CapturedStepLoop, PipelineLoadingMixin):
     def __init__(self, vae: AutoencoderKL, unet: UNet2DConditionModel, scheduler):
         self.vae, self.unet, self.scheduler = vae, unet, scheduler
         self.vae_scale_factor = 2 ** (len(vae.config.block_out_channels) - 1) if vae is not None else 8
@@ -1728,7 +1752,7 @@ def calculate_shift(image_seq_len, base_seq_len: int = 256, max_seq_len: int = 4
     return image_seq_len * m + b
 
 
-class FluxPipeline(_StepCallbacks, _CapturedStepLoop, PipelineLoadingMixin):
+class FluxPipeline(_VaeTilingMixin, _StepCallbacks, _CapturedStepLoop, PipelineLoadingMixin):
     """pipelines/flux/pipeline_flux.py:654-980 for pre-computed prompt embeddings (FLUX.1-schnell protocol: no true-CFG,
     no guidance embedding).  The step body -- transformer forward + FlowMatch-Euler update -- is captured once in a HIP
     graph and replayed; latents stay in the packed (B, (h/2)(w/2), 64) layout of the reference throughout the loop."""
@@ -2085,7 +2109,7 @@ class FluxInpaintPipeline(FluxImg2ImgPipeline):
                                 use_graph, callback_on_step_end, callback_on_step_end_tensor_inputs)
 
 
-class WanPipeline(_StepCallbacks, _CapturedStepLoop, PipelineLoadingMixin):
+class WanPipeline(_VaeTilingMixin, _StepCallbacks, _CapturedStepLoop, PipelineLoadingMixin):
     """pipelines/wan/pipeline_wan.py:380-700 (Wan 2.1 T2V) for pre-computed prompt embeddings: the denoising loop.
     The reference runs the transformer twice per step (cond / uncond, :613-632); here the two are one batch-2 call
     (identical arithmetic per sample, twice the GEMM M) and ``uncond + g (cond - uncond)`` is fused into the FlowMatch

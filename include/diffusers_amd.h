@@ -676,6 +676,38 @@ int da_tiny_vae_latents_in(const void* x, void* y, int B, int L, int H, int W, f
                            void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------------
+ * Tiled AutoencoderKL.decode (autoencoder_kl.py tiled_decode, blend_v, blend_h): blend one decoded tile with its finished upper and
+ * left neighbours, crop it and place it in the full image -- one launch per tile, one thread per pixel, C <= 4 (csrc/vae_tile.hip).
+ *   da_vae_tile_blend   src: the tile's conv_out result, bf16, element (b, c, pixel p = y w + x) at src[b sB + c sC + p sP] (the
+ *                       strides of da_vae_posterior_latents: NCHW, or the 16-padded NHWC result of the implicit-GEMM conv_out), B x C
+ *                       x h x w.  A channels-last source with sC == 1 and sP >= 4 holds WHOLE pixel slots: its first 4 channels are read
+ *                       as one 8-byte load where sP, sB and the base allow, so element 3 of the last pixel must exist also when C < 4
+ *                       (the 16-padded conv_out result does).  up: the finished upper tile, NCHW bf16 [B][C][hu][w], or NULL.  left: the finished left tile, NCHW
+ *                       bf16 [B][C][h][wl], or NULL.  weights: fp32 [E][2] = (float(1 - k / E), float(k / E)) evaluated in double on
+ *                       the host (1.0f - (float)k / E is another number when E is no power of two); may be NULL when nothing blends.
+ *                       Per element, fp32 ops that are never contracted, in this order:
+ *                         v = src
+ *                         up   and y < min(hu, h, E):  v = bf16(bf16(up[hu - E + y][x] * w[y][0]) + bf16(v * w[y][1]))     blend_v
+ *                         left and x < min(wl, w, E):  v = bf16(bf16(left[y][wl - E + x] * w[x][0]) + bf16(v * w[x][1]))   blend_h
+ *                       -- the reference's three bf16 torch ops per blend; the rows are counted from the NEIGHBOUR's end (hu - E + y),
+ *                       as its a[:, :, -E + y, :] does, whatever the neighbour's size.  A NaN result (inf * 0, inf - inf) is stored
+ *                       as 0x7FC0 (torch itself has no single pattern there: its scalar fp32 -> bf16 conversion stores 0x7FC0, its
+ *                       vectorised CPU one 0xFFFF); an element no blend touches keeps its bits.  fin (NCHW bf16 [B][C][h][w], or NULL
+ *                       when no later tile reads it) <- v.  The rectangle y < keep_h, x < keep_w goes to (y0 + y, x0 + x) of the
+ *                       image [B][C][image_h][image_w]: mode -1: bf16 NCHW <- v; modes 0 / 1 / 2 as da_nhwc_take_postprocess on v:
+ *                       o = clamp(v * 0.5 + 0.5, 0, 1), 0: NCHW fp32, 1: NHWC fp32, 2: NHWC uint8 = rint(255 o).  Nothing else of
+ *                       the image is written.  E == 0 or no neighbour: a crop-and-place.
+ *                       DA_ERR_INVALID and no launch for: src or image NULL, weights NULL where something blends, a non-positive
+ *                       size, C outside 1 .. 4, E < 0, negative strides, a neighbour with hu < E or wl < E (the reference would index
+ *                       before its start), keep_h > h or keep_w > w or either < 1, a rectangle outside the image, a mode outside
+ *                       -1 .. 2, B > 65535, h w >= 2^31.  Runs once per tile of a decode, outside any recorded step: no DA_FN_* plan number (DA_ABI_VERSION
+ *                       stays 9).
+ * ------------------------------------------------------------------------------------------------------------------ */
+int da_vae_tile_blend(const void* src, long long sB, long long sC, long long sP, const void* up, int hu, const void* left, int wl,
+                      const void* weights, int E, void* fin, void* image, int B, int C, int h, int w, int keep_h, int keep_w,
+                      long long image_h, long long image_w, long long y0, long long x0, int mode, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------------
  * Launch plans: a recorded sequence of the launch entry points above, owned by the library and replayed by ONE call --
  * the C-ABI form of the denoising step the Python pipelines capture into a HIP graph (the reference's per-step work,
  * pipeline_stable_diffusion_xl.py:1186-1250: scale_model_input, the U-Net forward, the CFG combine, scheduler.step; and the
