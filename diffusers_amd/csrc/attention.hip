@@ -619,7 +619,8 @@ __global__ __launch_bounds__(64 * NW, (D <= 64 ? 2 : 1)) void attn_fwd_kernel(co
 
   // ---- epilogue ----
   const float l_tot = l_run + __shfl_xor(l_run, 32, 64);
-  const float inv = 1.0f / l_tot;
+  // masked: a query without a visible key (l = 0, O = 0) gives a row of zeros, not 0 * inf (include/diffusers_amd.h `bias`)
+  const float inv = (MASKED && !(l_tot > 0.f)) ? 0.f : 1.0f / l_tot;
   const int q = q0 + l31;
   if (q < p.Sq) {
     uint16_t* op = O + (size_t)q * p.o_row_stride;

@@ -333,7 +333,9 @@ __global__ __launch_bounds__(64 * NW, (D == 64 && NW == 4) ? 3 : (NW == 8 ? 2 : 
             const float delta = HAS_PREV ? fmaxf(mxr, 0.f) : mxr;
             const float m_new = bf2f(f2bf(m_run + delta));       // bf16-exact: it rides in the next tiles' MFMA
             const float d_eff = m_new - m_run;
-            alpha = __builtin_amdgcn_exp2f(-d_eff);
+            // first tile: O, l and the MFMA row sum are still zero and need no rescale -- and exp2(-d_eff) is +inf once the
+            // shift lands below -128 (every score of the wave's first tile far below zero): 0 * inf
+            alpha = HAS_PREV ? __builtin_amdgcn_exp2f(-d_eff) : 1.f;
             m_run = m_new;
             qx = __builtin_bit_cast(bf16x8_t, make_uint4(hi == 0 ? (uint32_t)f2bf(-m_new) : 0u, 0u, 0u, 0u));
 #pragma unroll

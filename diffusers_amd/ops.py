@@ -736,7 +736,7 @@ def attention(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, *, B: int, H: 
               kv_split: int = 0) -> torch.Tensor:
     """Flash attention over strided views; returns out [B*Sq][H*D].  ``causal`` / ``bias`` (D = 64 only): the masked
     variant for the text encoders -- ``bias`` is [B or 1][H or 1][Sq][>= ceil64(Skv)] (bf16 or fp32), added to
-    scale * q.k^T; entries <= -1e29 mask a key.  ``kv_split``: 0 = the library decides whether the launch's last partial round of
+    scale * q.k^T; entries <= -1e29 mask a key; a query whose keys are ALL masked gets a row of zeros (not NaN).  ``kv_split``: 0 = the library decides whether the launch's last partial round of
     query blocks is split over the keys (module flag ATTN_SPLIT), 1 = never, 2..8 = pinned (tests)."""
     _req(q, "q"), _req(k, "k"), _req(vt, "vt")
     if out is None:

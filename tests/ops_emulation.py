@@ -176,7 +176,8 @@ def attention(q, k, vt, *, B, H, D, Sq, Skv, Skv_alloc, q_row_stride, k_row_stri
     if causal:
         keep = torch.arange(Skv)[None, :] <= torch.arange(Sq)[:, None]
         sc = sc.masked_fill(~keep, float("-inf"))
-    p = torch.softmax(sc, dim=-1)
+    dead = torch.isinf(sc).all(dim=-1, keepdim=True)      # C ABI: a query without a visible key gives a row of zeros, not NaN
+    p = torch.softmax(sc.masked_fill(dead, 0.0), dim=-1).masked_fill(dead, 0.0)
     o = (p @ vv.transpose(2, 3)).permute(0, 2, 1, 3).reshape(B * Sq, H * D)
     return _store(o, out)
 
