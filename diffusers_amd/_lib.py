@@ -105,6 +105,8 @@ PASS_THROUGH = {
     "da_plan_launch": "replays an existing plan from inside the library; plans do not nest, the recorder never sees its launches",
     "da_tiny_vae_latents_in": "runs once per decode, outside any recorded step; ops.tiny_vae_latents_in refuses under a recording",
     "da_vae_tile_blend": "runs once per tile of a tiled decode, outside any recorded step; ops.vae_tile_blend refuses under a recording",
+    "da_vae_moments_tile_blend": "runs once per tile of a tiled / sliced encode, outside any recorded step; ops.vae_moments_tile_blend "
+                                 "refuses under a recording",
 }
 
 
@@ -172,6 +174,8 @@ SIGNATURES = {
     "da_tiny_vae_latents_in": (_i, [_vp, _vp, _i, _i, _i, _i, _f, _f, _f, _vp]),
     "da_vae_tile_blend": (_i, [_vp, _ll, _ll, _ll, _vp, _i, _vp, _i, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _ll, _ll, _ll, _ll, _i,
                                _vp]),
+    "da_vae_moments_tile_blend": (_i, [_vp, _ll, _ll, _ll, _vp, _vp, _vp, _i, _vp, _i, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _ll,
+                                       _ll, _ll, _ll, _vp]),
     "da_plan_create": (_i, [C.POINTER(PlanOp), _i, C.POINTER(C.c_void_p)]),
     "da_plan_launch": (_i, [_vp, _vp, C.POINTER(C.c_int)]),
     "da_plan_relocate": (_i, [_vp, _i, C.POINTER(C.c_void_p), C.POINTER(C.c_ulonglong), C.POINTER(C.c_void_p),

@@ -71,6 +71,20 @@ class VaeAttention:
         S = H * W_
         res = x.view(B * S, C)
         h = self.group_norm(x).view(B * S, C)
+        if S % 8 and self.head_dim in (64, 96, 128, 160) and not self.force_gemm_path:
+            # a token count that is no multiple of 8 (the one- and two-line edge tiles of a tiled encode): the flash kernel takes whole
+            # groups of 8 ALLOCATED keys, so K and V^T go into zero-padded buffers and Skv masks the keys past S
+            S8, n = (S + 7) // 8 * 8, self.inner
+            qk = ops.linear(h, self.wqk, self.bqk)
+            v = ops.linear(h, self.wv)
+            k = torch.zeros((B, S8, n), device=x.device, dtype=bf16)
+            k[:, :S] = qk.view(B, S, 2 * n)[:, :, n:]
+            vt = torch.zeros((n, B, S8), device=x.device, dtype=bf16)
+            vt[:, :, :S] = v.view(B, S, n).permute(2, 0, 1)
+            o = ops.attention(qk, k, vt, B=B, H=self.heads, D=self.head_dim, Sq=S, Skv=S, Skv_alloc=S8, q_row_stride=2 * n,
+                              k_row_stride=n, q_batch_stride=S * 2 * n, k_batch_stride=S8 * n, vt_ld=B * S8, vt_batch_stride=S8,
+                              scale=self.scale)
+            return ops.linear(o, self.wo, self.bo, residual=res).view(B, H, W_, C)
         # [B*S][2C] and [C][B*S] (V bias folded into self.bo): one paired launch (layers.Attention)
         qk, vt = ops.linear_pair({"x": h, "w": self.wqk, "bias": self.bqk}, {"x": self.wv, "w": h})
         if self.head_dim in (64, 96, 128, 160) and not self.force_gemm_path:
@@ -154,11 +168,18 @@ class DiagonalGaussianDistribution:
     kernel (csrc/vae_encode.hip); ``parameters`` / ``mean`` / ``logvar`` / ``std`` / ``var`` are the reference's attributes (the
     quant_conv output from the same kernel, the rest as the reference's bf16 torch ops on it)."""
 
-    def __init__(self, encoder: _Encoder, raw: torch.Tensor, strides, shape, noise_dtype):
+    def __init__(self, encoder: _Encoder, raw: torch.Tensor, strides, shape, noise_dtype, assembled: bool = False):
         self._enc, self._raw, self._strides = encoder, raw, strides
         self._B, self._H, self._W = shape
         self._noise_dtype = noise_dtype
         self._params = None
+        self._wq, self._bq = encoder.quant_w, encoder.quant_b
+        if assembled:
+            # a tiled / sliced encode: ``raw`` IS the moments [B][2L][H][W] (NCHW, quant_conv applied tile by tile)
+            hw = self._H * self._W
+            self._strides = (2 * encoder.latent_channels * hw, hw, 1)
+            self._params = raw
+            self._wq = self._bq = None
         self.deterministic = False
 
     @property
@@ -168,7 +189,7 @@ class DiagonalGaussianDistribution:
     def _run(self, mode, **kw) -> torch.Tensor:
         e = self._enc
         y = ops.vae_posterior_latents(self._raw, self._strides, batch=self._B, hw=self._H * self._W,
-                                      latent_channels=e.latent_channels, mode=mode, wq=e.quant_w, bq=e.quant_b, **kw)
+                                      latent_channels=e.latent_channels, mode=mode, wq=self._wq, bq=self._bq, **kw)
         return y.view(self._B, -1, self._H, self._W)
 
     @property
@@ -360,7 +381,10 @@ class AutoencoderKL(PretrainedMixin):
 
     def encode_image(self, img: torch.Tensor, *, nchw: bool, normalize: bool) -> DiagonalGaussianDistribution:
         """Engine extension: the caller's image -- fp32 NCHW / NHWC or uint8 NHWC (read as x / 255), ``normalize``: 2 x - 1
-        (VaeImageProcessor.preprocess) -- straight into the encoder.  Sizes must be multiples of 2 ** (len(block_out_channels) - 1)."""
+        (VaeImageProcessor.preprocess) -- straight into the encoder.  Sizes must be multiples of 2 ** (len(block_out_channels) - 1).
+        ``use_tiling`` (``enable_tiling()``): an image larger than ``tile_sample_min_size`` either way is encoded as the reference's
+        ``_tiled_encode`` does -- overlapping tiles, each normalised on its own, the moments blended at the seams; ``use_slicing``
+        (``enable_slicing()``): a batch is encoded sample by sample.  Either way the distribution is over the assembled moments."""
         self._require_encoder()
         ops.require_hip(img, "image", dtypes=(torch.float32, torch.uint8))
         B = img.shape[0]
@@ -368,9 +392,88 @@ class AutoencoderKL(PretrainedMixin):
         f = 2 ** (len(self.config.block_out_channels) - 1)
         if H % f or W_ % f:
             raise ValueError(f"AutoencoderKL.encode: image size {H} x {W_} is not a multiple of {f} (the engine does not resize)")
+        noise_dtype = torch.float32 if self.config.force_upcast else bf16
+        S = self.tile_sample_min_size
+        tiled = self.use_tiling and (W_ > S or H > S)
+        sliced = self.use_slicing and B > 1
+        if tiled or sliced:
+            moments = self._assembled_encode(img, nchw, normalize, tiled, sliced)
+            return DiagonalGaussianDistribution(self.encoder, moments, None, (B, moments.shape[2], moments.shape[3]), noise_dtype,
+                                                assembled=True)
         raw, strides = self.encoder(img, nchw=nchw, normalize=normalize)
-        return DiagonalGaussianDistribution(self.encoder, raw, strides, (B, H // f, W_ // f),
-                                            torch.float32 if self.config.force_upcast else bf16)
+        return DiagonalGaussianDistribution(self.encoder, raw, strides, (B, H // f, W_ // f), noise_dtype)
+
+    def _encode_tile_plan(self, H: int, W: int):
+        """The reference's _tiled_encode bookkeeping for an H x W pixel image, host only: ``(E, rows, Hl, Wl)`` with ``E`` the blend
+        extent in latent pixels and ``rows`` the tiles in encode order, each a dict -- pixel slice (``i``, ``j``, ``ph``, ``pw``; edge
+        tiles are smaller), latent size (``h``, ``w``), the piece kept (``keep_h``, ``keep_w`` = the tile cropped to ``row_limit``) and
+        where the concatenations put it (``y0``, ``x0``); ``(Hl, Wl)``, the assembled size, is the sum of the pieces."""
+        tl, S, factor = self.tile_latent_min_size, self.tile_sample_min_size, self.tile_overlap_factor
+        f = 2 ** (len(self.config.block_out_channels) - 1)
+        overlap = int(S * (1 - factor))
+        E = int(tl * factor)
+        row_limit = tl - E
+        if overlap < 1:
+            raise ValueError(f"tile_sample_min_size = {S} with tile_overlap_factor = {factor} gives overlap_size = {overlap} < 1: the "
+                             "tiles would not advance")
+        if E < 0 or row_limit < 1:
+            raise ValueError(f"tile_latent_min_size = {tl} with tile_overlap_factor = {factor} gives blend_extent = {E} and row_limit = "
+                             f"{row_limit}: nothing of a tile would be kept")
+        if overlap % f or S % f:
+            raise ValueError(f"tile_sample_min_size = {S} with tile_overlap_factor = {factor} gives overlap_size = {overlap}: both must "
+                             f"be multiples of {f}, the VAE's downscale factor (the engine does not floor odd tiles)")
+        starts = [list(range(0, n, overlap)) for n in (H, W)]
+        for name, n, st in zip(("rows", "columns"), (H, W), starts):
+            for a in st[:-1]:                                    # every tile but the last is some tile's upper / left neighbour
+                if min(S, n - a) // f < E:
+                    raise ValueError(f"tile_latent_min_size = {tl} with tile_overlap_factor = {factor} gives blend_extent = {E}, more "
+                                     f"than the {min(S, n - a) // f} latent {name} of a tile that is blended into its neighbour "
+                                     f"(tile_sample_min_size = {S}, image {H} x {W})")
+        rows, y0 = [], 0
+        for i in starts[0]:
+            ph = min(S, H - i)
+            row, x0 = [], 0
+            for j in starts[1]:
+                pw = min(S, W - j)
+                t = dict(i=i, j=j, ph=ph, pw=pw, h=ph // f, w=pw // f, keep_h=min(ph // f, row_limit), keep_w=min(pw // f, row_limit),
+                         y0=y0, x0=x0)
+                row.append(t)
+                x0 += t["keep_w"]
+            rows.append(row)
+            y0 += row[0]["keep_h"]
+        return E, rows, y0, x0
+
+    def _assembled_encode(self, img: torch.Tensor, nchw: bool, normalize: bool, tiled: bool, sliced: bool) -> torch.Tensor:
+        """autoencoder_kl.py _tiled_encode (``tiled``) and encode's per-sample loop (``sliced``): the moments [B][2L][Hl][Wl], NCHW
+        bf16, quant_conv applied.  Tiles are encoded and blended in the reference's order, one ops.vae_moments_tile_blend launch per
+        tile in place of its quant_conv, blend loops, crops and concatenations; of the blended tiles only the previous row and the
+        current one stay alive.  Untiled slices are one tile with no neighbour: quant_conv and place."""
+        B = img.shape[0]
+        H, W_ = (img.shape[2], img.shape[3]) if nchw else (img.shape[1], img.shape[2])
+        f = 2 ** (len(self.config.block_out_channels) - 1)
+        if tiled:
+            E, rows, Hl, Wl = self._encode_tile_plan(H, W_)
+        else:
+            E, Hl, Wl = 0, H // f, W_ // f
+            rows = [[dict(i=0, j=0, ph=H, pw=W_, h=Hl, w=Wl, keep_h=Hl, keep_w=Wl, y0=0, x0=0)]]
+        enc = self.encoder
+        moments = torch.empty((B, 2 * enc.latent_channels, Hl, Wl), device=img.device, dtype=bf16)
+        for b0, b1 in ([(b, b + 1) for b in range(B)] if sliced else [(0, B)]):
+            above = None
+            for r, row in enumerate(rows):
+                done = []
+                for c, t in enumerate(row):
+                    ys, xs = slice(t["i"], t["i"] + t["ph"]), slice(t["j"], t["j"] + t["pw"])
+                    tile = (img[b0:b1, :, ys, xs] if nchw else img[b0:b1, ys, xs, :]).contiguous()
+                    raw, strides = enc(tile, nchw=nchw, normalize=normalize)
+                    fin = ops.vae_moments_tile_blend(raw, strides, batch=b1 - b0, latent_channels=enc.latent_channels, height=t["h"],
+                                                     width=t["w"], moments=moments[b0:b1], y0=t["y0"], x0=t["x0"],
+                                                     keep_h=t["keep_h"], keep_w=t["keep_w"], wq=enc.quant_w, bq=enc.quant_b, extent=E,
+                                                     up=above[c] if above is not None else None, left=done[-1] if done else None,
+                                                     want_fin=r + 1 < len(rows) or c + 1 < len(row))
+                    done.append(fin)
+                above = done
+        return moments
 
     # ---- tiling / slicing (autoencoder_kl.py enable_tiling / enable_slicing / tiled_decode) ----
     def enable_tiling(self, use_tiling: bool = True):

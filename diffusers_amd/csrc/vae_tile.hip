@@ -117,7 +117,155 @@ void launch_mode(const TileArgs& a, bool blend, bool vec, const dim3& blocks, hi
 #undef DA_TILE
 }
 
+// ---- tiled AutoencoderKL.encode (autoencoder_kl.py _tiled_encode): the moments of one encoded tile -------------------------------
+// One launch per tile does everything between the tile's conv_out and the assembled moments: quant_conv (as
+// posterior_latents_kernel: p[o] = bf16(bq[o] + sum_k wq[o][k] x[k]), k ascending, fp32 fma, one rounding), the vertical blend
+// against the finished upper tile, the horizontal blend against the finished left tile on the vertical blend's result (blend_bits:
+// the rounding points and the NaN rule above), `fin` for the tiles that come later and the kept rectangle at its place in the NCHW
+// moments tensor.  One thread per latent pixel holds all C2 = 2 L channels of it; the house rules above apply: every load
+// unconditional from a clamped address with a select afterwards, all loads of a pixel before its arithmetic, size_t offsets, a
+// 32-bit pixel index.  VEC: a channels-last source (sC == 1) whose pixels are 16-byte aligned is read as C2 / 8 16-byte loads -- the
+// 16-padded result of the thin conv_out (C2 = 8) and the NHWC result of the 16-channel VAEs' conv_out (C2 = 32) both are.  The
+// quant_conv weights live in registers (C2 = 8 only, as in the posterior kernel).
+struct MomentsArgs {
+  const uint16_t* src;      // the tile's conv_out result: element (b, c, p) at b sB + c sC + p sP, p = y w + x
+  long long sB, sC, sP;
+  const uint16_t* wq;       // [C2][C2], QC only
+  const uint16_t* bq;       // [C2]
+  const uint16_t* up;       // finished upper tile, NCHW bf16 [B][C2][hu][w], or the source (never read through then)
+  const uint16_t* left;     // finished left tile, NCHW bf16 [B][C2][h][wl], or the source
+  const float* wt;          // [E][2] = (w0, w1)
+  uint16_t* fin;            // NCHW bf16 [B][C2][h][w] or NULL
+  uint16_t* out;            // the assembled moments, NCHW bf16 [B][C2][HL][WL]
+  int h, w, hu, wl, E;
+  int ev, eh;               // rows / columns that blend
+  int keep_h, keep_w;
+  long long HL, WL, y0, x0;
+};
+
+template <int C2, bool QC, bool BLEND, bool VEC>
+__global__ __launch_bounds__(256) void vae_moments_tile_blend_kernel(const MomentsArgs a) {
+  static_assert(C2 % 8 == 0 && (!QC || C2 == 8), "whole 16-byte groups; a quant_conv in registers at C2 = 8 only");
+  // quant_conv weights and bias, loaded once per thread before the pixel loop (uniform addresses: scalar loads)
+  float wf[QC ? C2 * C2 : 1], bfv[QC ? C2 : 1];
+  if (QC) {
+#pragma unroll
+    for (int j = 0; j < C2 * C2; ++j) wf[j] = bf2f(a.wq[j]);
+#pragma unroll
+    for (int o = 0; o < C2; ++o) bfv[o] = bf2f(a.bq[o]);
+  }
+  const unsigned hw = (unsigned)a.h * (unsigned)a.w, uw = (unsigned)a.w;
+  const size_t b = blockIdx.y;
+  for (unsigned p = blockIdx.x * 256u + threadIdx.x; p < hw; p += gridDim.x * 256u) {
+    const int y = (int)(p / uw), x = (int)(p - (unsigned)y * uw);
+    uint16_t s[C2], u[BLEND ? C2 : 1], l[BLEND ? C2 : 1];
+    float wv0 = 0.f, wv1 = 0.f, wh0 = 0.f, wh1 = 0.f;
+    const bool bv = BLEND && y < a.ev, bh = BLEND && x < a.eh;
+    // ---- loads ----
+    const size_t soff = b * (size_t)a.sB + (size_t)p * (size_t)a.sP;
+    if (VEC) {
+#pragma unroll
+      for (int g = 0; g < C2 / 8; ++g) {
+        const uint4 q = *(const uint4*)(a.src + soff + 8 * g);
+        const uint32_t r[4] = {q.x, q.y, q.z, q.w};
+#pragma unroll
+        for (int k = 0; k < 4; ++k) s[8 * g + 2 * k] = (uint16_t)(r[k] & 0xffffu), s[8 * g + 2 * k + 1] = (uint16_t)(r[k] >> 16);
+      }
+    } else {
+#pragma unroll
+      for (int c = 0; c < C2; ++c) s[c] = a.src[soff + (size_t)c * (size_t)a.sC];
+    }
+    if (BLEND) {
+      const bool has_up = a.ev > 0, has_left = a.eh > 0;
+      const size_t yu = bv ? (size_t)(a.hu - a.E + y) : 0, xu = has_up ? (size_t)x : 0;
+      const size_t xl = bh ? (size_t)(a.wl - a.E + x) : 0, yl = has_left ? (size_t)y : 0;
+      const size_t bu = has_up ? b : 0, bl = has_left ? b : 0;
+#pragma unroll
+      for (int c = 0; c < C2; ++c) {
+        const size_t cu = has_up ? (size_t)c : 0, cl = has_left ? (size_t)c : 0;
+        u[c] = a.up[((bu * C2 + cu) * (size_t)a.hu + yu) * (size_t)a.w + xu];
+        l[c] = a.left[((bl * C2 + cl) * (size_t)a.h + yl) * (size_t)a.wl + xl];
+      }
+      const float2 wv = *(const float2*)(a.wt + 2 * (bv ? y : 0));
+      const float2 wh = *(const float2*)(a.wt + 2 * (bh ? x : 0));
+      wv0 = wv.x, wv1 = wv.y, wh0 = wh.x, wh1 = wh.y;
+    }
+    // ---- quant_conv, blend, store ----
+    uint16_t pm[C2];
+    if (QC) {
+#pragma unroll
+      for (int o = 0; o < C2; ++o) {
+        float acc = bfv[o];
+#pragma unroll
+        for (int k = 0; k < C2; ++k) acc = fmaf(wf[o * C2 + k], bf2f(s[k]), acc);
+        pm[o] = f2bf(acc);
+      }
+    } else {
+#pragma unroll
+      for (int o = 0; o < C2; ++o) pm[o] = s[o];
+    }
+    const bool kept = y < a.keep_h && x < a.keep_w;
+    const size_t Y = (size_t)(a.y0 + y), X = (size_t)(a.x0 + x);
+#pragma unroll
+    for (int c = 0; c < C2; ++c) {
+      uint16_t v = pm[c];
+      if (BLEND) {
+        const uint16_t tv = blend_bits(u[c], v, wv0, wv1);
+        v = bv ? tv : v;
+        const uint16_t th = blend_bits(l[c], v, wh0, wh1);
+        v = bh ? th : v;
+      }
+      if (a.fin) a.fin[((b * C2 + c) * (size_t)a.h + (size_t)y) * (size_t)a.w + (size_t)x] = v;
+      if (kept) a.out[((b * C2 + c) * (size_t)a.HL + Y) * (size_t)a.WL + X] = v;
+    }
+  }
+}
+
+template <int C2, bool QC>
+void launch_moments(const MomentsArgs& a, bool blend, bool vec, const dim3& blocks, hipStream_t s) {
+#define DA_MTILE(B_, V_) DA_LAUNCH((vae_moments_tile_blend_kernel<C2, QC, B_, V_>), blocks, dim3(256), 0, s, a)
+  if (blend) { if (vec) DA_MTILE(true, true); else DA_MTILE(true, false); }
+  else { if (vec) DA_MTILE(false, true); else DA_MTILE(false, false); }
+#undef DA_MTILE
+}
+
 }  // namespace
+
+extern "C" int da_vae_moments_tile_blend(const void* src, long long sB, long long sC, long long sP, const void* wq, const void* bq,
+                                         const void* up, int hu, const void* left, int wl, const void* weights, int E, void* fin,
+                                         void* moments, int B, int L, int h, int w, int keep_h, int keep_w, long long moments_h,
+                                         long long moments_w, long long y0, long long x0, void* stream) {
+  if (B > 65535 || (long long)h * w > 0x7fffffffLL) return DA_ERR_INVALID;                      // grid y = B, 32-bit pixel index
+  if (!src || !moments || B <= 0 || L <= 0 || h <= 0 || w <= 0 || E < 0 || sB < 0 || sC < 0 || sP < 0) return DA_ERR_INVALID;
+  if (!wq != !bq) return DA_ERR_INVALID;                                                       // quant_conv: weight and bias, or neither
+  if ((up && hu < E) || (left && wl < E) || (up && hu <= 0) || (left && wl <= 0)) return DA_ERR_INVALID;
+  if (keep_h <= 0 || keep_w <= 0 || keep_h > h || keep_w > w) return DA_ERR_INVALID;
+  if (moments_h <= 0 || moments_w <= 0 || y0 < 0 || x0 < 0 || y0 + keep_h > moments_h || x0 + keep_w > moments_w) return DA_ERR_INVALID;
+  const bool blend = E > 0 && (up || left);
+  if (blend && !weights) return DA_ERR_INVALID;
+  if (L != 4 && !(L == 16 && !wq)) return DA_ERR_UNSUPPORTED;    // as da_vae_posterior_latents: 32 x 32 weights per thread would spill
+  MomentsArgs a;
+  a.src = (const uint16_t*)src, a.sB = sB, a.sC = sC, a.sP = sP;
+  a.wq = (const uint16_t*)wq, a.bq = (const uint16_t*)bq;
+  a.up = up ? (const uint16_t*)up : (const uint16_t*)src;
+  a.left = left ? (const uint16_t*)left : (const uint16_t*)src;
+  a.wt = (const float*)weights;
+  a.fin = (uint16_t*)fin, a.out = (uint16_t*)moments;
+  a.h = h, a.w = w, a.hu = up ? hu : 0, a.wl = left ? wl : 0, a.E = E;
+  a.ev = up ? (hu < h ? (hu < E ? hu : E) : (h < E ? h : E)) : 0;
+  a.eh = left ? (wl < w ? (wl < E ? wl : E) : (w < E ? w : E)) : 0;
+  a.keep_h = keep_h, a.keep_w = keep_w, a.HL = moments_h, a.WL = moments_w, a.y0 = y0, a.x0 = x0;
+  // 16-byte loads: channels-last, every pixel 16-byte aligned; exactly the 2 L channels are read, so nothing past them need exist
+  const bool vec = sC == 1 && sP >= 2 * L && (sP & 7) == 0 && (sB & 7) == 0 && ((uintptr_t)src & 15) == 0;
+  const long long nb = ((long long)h * w + 255) / 256;
+  const dim3 blocks((unsigned)(nb < 65535 * 16 ? nb : 65535 * 16), (unsigned)B);
+  hipStream_t s = (hipStream_t)stream;
+  if (L == 16) launch_moments<32, false>(a, blend, vec, blocks, s);
+  else if (wq) launch_moments<8, true>(a, blend, vec, blocks, s);
+  else launch_moments<8, false>(a, blend, vec, blocks, s);
+  DA_CHECK_LAUNCH();
+  return DA_OK;
+}
 
 extern "C" int da_vae_tile_blend(const void* src, long long sB, long long sC, long long sP, const void* up, int hu, const void* left,
                                  int wl, const void* weights, int E, void* fin, void* image, int B, int C, int h, int w, int keep_h,

@@ -1629,6 +1629,65 @@ def vae_tile_blend(src: torch.Tensor, strides, *, batch: int, channels: int, hei
     return fin
 
 
+def vae_moments_tile_blend(src: torch.Tensor, strides, *, batch: int, latent_channels: int, height: int, width: int,
+                           moments: torch.Tensor, y0: int, x0: int, keep_h: int, keep_w: int, wq: Optional[torch.Tensor] = None,
+                           bq: Optional[torch.Tensor] = None, extent: int = 0, up: Optional[torch.Tensor] = None,
+                           left: Optional[torch.Tensor] = None, want_fin: bool = True):
+    """da_vae_moments_tile_blend (csrc/vae_tile.hip; arithmetic in include/diffusers_amd.h): one tile of a tiled / sliced
+    AutoencoderKL.encode.  ``src``: the tile's conv_out result, 2 L channels, read through ``strides`` = (sB, sC, sP) in elements
+    (conv_thin_out_moments); ``wq`` [2L][2L] / ``bq`` [2L]: quant_conv; ``up`` / ``left``: the finished neighbours, contiguous NCHW
+    bf16 [B][2L][hu][width] / [B][2L][height][wl]; ``extent``: the blend extent in latent pixels.  The rectangle ``keep_h`` x
+    ``keep_w`` of the blended tile is written at (``y0``, ``x0``) of ``moments``, contiguous NCHW bf16 [B][2L][Hl][Wl].  Returns the
+    blended tile, NCHW bf16 (None unless ``want_fin``).  Runs once per tile and has no plan number: refused while a launch plan is
+    being recorded."""
+    if getattr(L._tls, "recorder", None) is not None:
+        raise RuntimeError("vae_moments_tile_blend: not replayable by a launch plan (da_vae_moments_tile_blend has no DA_FN_* number); "
+                           "encode outside the recording")
+    _req(src, "src")
+    B, Lc, h, w, E = int(batch), int(latent_channels), int(height), int(width), int(extent)
+    C = 2 * Lc
+    if min(B, Lc, h, w) < 1 or E < 0:
+        raise ValueError(f"vae_moments_tile_blend: a positive tile and extent >= 0 required, got B = {B}, L = {Lc}, {h} x {w}, "
+                         f"extent = {E}")
+    if (wq is None) != (bq is None):
+        raise ValueError("vae_moments_tile_blend: quant_conv weight [2L][2L] and bias [2L] come together")
+    if Lc != 4 and not (Lc == 16 and wq is None):
+        raise NotImplementedError(f"vae_moments_tile_blend: latent_channels = {Lc}{' with a quant_conv' if wq is not None else ''} "
+                                  "(built: 4 with or without a quant_conv, 16 without)")
+    if wq is not None:
+        _req(wq, "wq"), _req(bq, "bq")
+        if tuple(wq.shape) != (C, C) or tuple(bq.shape) != (C,) or not wq.is_contiguous() or not bq.is_contiguous():
+            raise ValueError(f"vae_moments_tile_blend: quant_conv weight [{C}][{C}] and bias [{C}] required")
+    sB, sC, sP = (int(v) for v in strides)
+    last = (B - 1) * sB + (C - 1) * sC + (h * w - 1) * sP
+    if min(sB, sC, sP) < 0 or last >= src.numel():
+        raise ValueError(f"vae_moments_tile_blend: strides {strides} reach element {last} of a {src.numel()}-element input")
+    hu = wl = 0
+    if up is not None:
+        _req(up, "up")
+        hu = up.shape[2] if up.dim() == 4 else -1
+        if not up.is_contiguous() or up.dim() != 4 or tuple(up.shape) != (B, C, hu, w) or hu < max(E, 1):
+            raise ValueError(f"vae_moments_tile_blend: up must be contiguous [{B}][{C}][>= {E}][{w}], got {tuple(up.shape)}")
+    if left is not None:
+        _req(left, "left")
+        wl = left.shape[3] if left.dim() == 4 else -1
+        if not left.is_contiguous() or left.dim() != 4 or tuple(left.shape) != (B, C, h, wl) or wl < max(E, 1):
+            raise ValueError(f"vae_moments_tile_blend: left must be contiguous [{B}][{C}][{h}][>= {E}], got {tuple(left.shape)}")
+    _req(moments, "moments")
+    if moments.dim() != 4 or not moments.is_contiguous() or moments.shape[0] != B or moments.shape[1] != C:
+        raise ValueError(f"vae_moments_tile_blend: moments must be contiguous NCHW, batch {B}, {C} channels, got {tuple(moments.shape)}")
+    HL, WL = moments.shape[2], moments.shape[3]
+    if not (1 <= keep_h <= h and 1 <= keep_w <= w and 0 <= y0 and 0 <= x0 and y0 + keep_h <= HL and x0 + keep_w <= WL):
+        raise ValueError(f"vae_moments_tile_blend: rectangle {keep_h} x {keep_w} at ({y0}, {x0}) of a {h} x {w} tile in {HL} x {WL} "
+                         "moments")
+    wt = tile_blend_weights(E, src.device) if E > 0 and (up is not None or left is not None) else None
+    fin = torch.empty((B, C, h, w), device=src.device, dtype=bf16) if want_fin else None
+    L.check(L.load().da_vae_moments_tile_blend(src.data_ptr(), sB, sC, sP, _ptr(wq), _ptr(bq), _ptr(up), hu, _ptr(left), wl, _ptr(wt),
+                                               E, _ptr(fin), moments.data_ptr(), B, Lc, h, w, int(keep_h), int(keep_w), HL, WL,
+                                               int(y0), int(x0), _stream()), "da_vae_moments_tile_blend")
+    return fin
+
+
 def vae_posterior_latents(x: torch.Tensor, strides, *, batch: int, hw: int, latent_channels: int, mode: int,
                           wq: Optional[torch.Tensor] = None, bq: Optional[torch.Tensor] = None, eps1: Optional[torch.Tensor] = None,
                           eps2: Optional[torch.Tensor] = None, shift: Optional[float] = None, scale: Optional[float] = None,

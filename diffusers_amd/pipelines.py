@@ -833,6 +833,23 @@ def _randn(shape, generator, device, dtype):
     return torch.randn(tuple(shape), generator=generator, device=gdev, dtype=dtype).to(device)
 
 
+def encode_image_latents(vae, img: torch.Tensor, *, nchw: bool, normalize: bool):
+    """``vae.encode_image`` for the image-reading pipelines.  ``enable_vae_tiling()`` / ``enable_vae_slicing()`` govern it; a tile
+    setting whose assembled latent grid is not the image's size / downscale factor (the reference's crops then sum to another size) is
+    refused here, since the loop's latents, noise and masks are laid out for the image's own grid."""
+    dist = vae.encode_image(img, nchw=nchw, normalize=normalize)
+    if not getattr(vae, "use_tiling", False):
+        return dist
+    H, W_ = (img.shape[2], img.shape[3]) if nchw else (img.shape[1], img.shape[2])
+    f = 2 ** (len(vae.config.block_out_channels) - 1)
+    got, want = tuple(dist.latent_shape[2:]), (H // f, W_ // f)
+    if got != want:
+        raise ValueError(f"the tiled VAE encode of a {H} x {W_} image assembles {got[0]} x {got[1]} latents, the pipeline needs "
+                         f"{want[0]} x {want[1]} (tile_sample_min_size = {vae.tile_sample_min_size}, tile_latent_min_size = "
+                         f"{vae.tile_latent_min_size}, tile_overlap_factor = {vae.tile_overlap_factor})")
+    return dist
+
+
 def prepare_image(image, vae_scale_factor: int, latent_channels: int, device):
     """``image`` as the encoder reads it: ``("latents", NCHW tensor)`` for latents (``latent_channels`` channels: encode is skipped,
     as the reference does), else ``("image", tensor, nchw, normalize)`` for ops.vae_conv_in_image.  VaeImageProcessor.preprocess
@@ -923,7 +940,7 @@ class _Img2ImgMixin:
             _, img, nchw, normalize = prep
             if isinstance(generator, (list, tuple)) and img.shape[0] < batch and batch % img.shape[0] == 0:
                 img = torch.cat([img] * (batch // img.shape[0]), 0)
-            dist = self.vae.encode_image(img, nchw=nchw, normalize=normalize)
+            dist = encode_image_latents(self.vae, img, nchw=nchw, normalize=normalize)
             eps1 = dist.draw_noise(generator, dtype=noise_dtype)
             if dist.latent_shape[0] == batch and add_noise:
                 noise = _randn(dist.latent_shape, generator, dev, bf16)
@@ -1191,7 +1208,7 @@ class _InpaintMixin:
     def _encode_scaled(self, img, generator, noise_dtype):
         """_encode_vae_image: retrieve_latents(vae.encode(image), generator) * scaling_factor, for an fp32 NCHW image in [-1, 1]."""
         vc = self.vae.config
-        dist = self.vae.encode_image(img, nchw=True, normalize=False)
+        dist = encode_image_latents(self.vae, img, nchw=True, normalize=False)
         return dist.latents(dist.draw_noise(generator, dtype=noise_dtype), scale=float(vc.scaling_factor))
 
     def _inpaint_prepare(self, image, mask_image, masked_image_latents, height, width, latents, timestep, batch: int, generator,
@@ -1420,7 +1437,7 @@ class _InstructPix2PixMixin:
             il = prep[1].clone()
         else:
             _, img, nchw, normalize = prep
-            il = self.vae.encode_image(img, nchw=nchw, normalize=normalize).mode()
+            il = encode_image_latents(self.vae, img, nchw=nchw, normalize=normalize).mode()
             if self._scales_image_latents:
                 il = (il * float(vc.scaling_factor)).to(bf16)
         n_lat, n_img, nu = vc.latent_channels, il.shape[1], self.unet.config.in_channels
@@ -2000,7 +2017,7 @@ class FluxImg2ImgPipeline(FluxPipeline):
                 raise ValueError(f"Cannot duplicate `image` of batch size {nimg} to {B} text prompts.")
             if isinstance(generator, (list, tuple)) and nimg < B:
                 img, nimg = torch.cat([img] * (B // nimg), 0), B
-            dist = self.vae.encode_image(img, nchw=nchw, normalize=normalize)
+            dist = encode_image_latents(self.vae, img, nchw=nchw, normalize=normalize)
             eps1 = dist.draw_noise(generator, dtype=bf16)
             noise = self._noise(shape, generator, latents, dev)
             packed = dist.flux_latents(eps1, noise, batch=B, scale=float(vc.scaling_factor),

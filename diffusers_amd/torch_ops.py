@@ -17,6 +17,7 @@ name ends in ``_``).  Registration happens on import of this module (``import di
     x_next = torch.ops.mi355x.euler_step(eps, x, table, step_idx, True, 5.0, 0)
     x_next = torch.ops.mi355x.euler_ancestral_step(eps, x, noise, table, step_idx, True, 5.0, 0, 0)
     x_next, m1 = torch.ops.mi355x.dpmpp_2m_step(eps, x, m1, table, step_idx, begin_idx, True, 5.0, 0)
+    fin, moments = torch.ops.mi355x.vae_moments_tile_blend(raw, sB, sC, sP, wq, bq, up, left, moments, 4, h, w, E, y0, x0, kh, kw)
 """
 from __future__ import annotations
 
@@ -139,4 +140,25 @@ def _(model_output, sample, noise, table, step_idx, cfg, guidance_scale, pred_ty
     return torch.empty_like(sample)
 
 
-OPS = ("gemm", "conv2d_nhwc", "flash_attn", "groupnorm", "layernorm", "euler_step", "dpmpp_2m_step", "euler_ancestral_step")
+@torch.library.custom_op(f"{NAMESPACE}::vae_moments_tile_blend", mutates_args=(), device_types="cuda")
+def vae_moments_tile_blend(src: torch.Tensor, stride_b: int, stride_c: int, stride_p: int, wq: Optional[torch.Tensor],
+                           bq: Optional[torch.Tensor], up: Optional[torch.Tensor], left: Optional[torch.Tensor], moments: torch.Tensor,
+                           latent_channels: int, height: int, width: int, extent: int, y0: int, x0: int, keep_h: int,
+                           keep_w: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """One tile of a tiled AutoencoderKL.encode (da_vae_moments_tile_blend): quant_conv, the blends with the finished upper / left
+    tiles, and the kept rectangle placed at (y0, x0) of the moments.  Returns (blended tile [B][2L][height][width], new moments).
+    Functional form of the in-place kernel: ``moments`` is copied."""
+    out = moments.contiguous().clone()
+    fin = ops.vae_moments_tile_blend(src, (stride_b, stride_c, stride_p), batch=moments.shape[0], latent_channels=latent_channels,
+                                     height=height, width=width, moments=out, y0=y0, x0=x0, keep_h=keep_h, keep_w=keep_w, wq=wq, bq=bq,
+                                     extent=extent, up=up, left=left, want_fin=True)
+    return fin, out
+
+
+@vae_moments_tile_blend.register_fake
+def _(src, stride_b, stride_c, stride_p, wq, bq, up, left, moments, latent_channels, height, width, extent, y0, x0, keep_h, keep_w):
+    return moments.new_empty((moments.shape[0], 2 * latent_channels, height, width)), torch.empty_like(moments)
+
+
+OPS = ("gemm", "conv2d_nhwc", "flash_attn", "groupnorm", "layernorm", "euler_step", "dpmpp_2m_step", "euler_ancestral_step",
+       "vae_moments_tile_blend")

@@ -711,6 +711,37 @@ int da_vae_tile_blend(const void* src, long long sB, long long sC, long long sP,
                       long long image_h, long long image_w, long long y0, long long x0, int mode, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------------
+ * Tiled AutoencoderKL.encode (autoencoder_kl.py _tiled_encode, blend_v, blend_h): the moments of one encoded tile -- quant_conv,
+ * the blends with the finished upper and left tiles, the crop and the placement in the assembled moments -- one launch per tile,
+ * one thread per latent pixel holding its 2 L channels (csrc/vae_tile.hip).
+ *   da_vae_moments_tile_blend   src: the tile's conv_out result, bf16, element (b, c, pixel p = y w + x) at src[b sB + c sC + p sP],
+ *                       B x 2 L x h x w: NCHW, the 16-padded NHWC result of the thin conv_out (sC = 1, sP = 16) or the NHWC result of
+ *                       the 16-channel VAEs' conv_out (sC = 1, sP = 2 L).  Exactly the 2 L channels of a pixel are read (as 16-byte
+ *                       loads where sC == 1 and sP, sB and the base keep every pixel 16-byte aligned).  wq [2L][2L] / bq [2L]: the
+ *                       quant_conv, bf16, both or neither.  up: the finished upper tile, NCHW bf16 [B][2L][hu][w], or NULL.  left:
+ *                       the finished left tile, NCHW bf16 [B][2L][h][wl], or NULL.  weights: fp32 [E][2] as for da_vae_tile_blend;
+ *                       may be NULL when nothing blends.  Per element, fp32 ops that are never contracted, in this order:
+ *                         v = wq ? bf16(bq[c] + sum_k wq[c][k] src[k]) : src[c]       k ascending, fp32 fma, one rounding: the
+ *                                                                                     quant_conv of da_vae_posterior_latents
+ *                         up   and y < min(hu, h, E):  v = bf16(bf16(up[hu - E + y][x] * w[y][0]) + bf16(v * w[y][1]))     blend_v
+ *                         left and x < min(wl, w, E):  v = bf16(bf16(left[y][wl - E + x] * w[x][0]) + bf16(v * w[x][1]))   blend_h
+ *                       with the rounding points and the NaN rule (0x7FC0) of da_vae_tile_blend in both blends; an element no blend
+ *                       touches keeps the bits of the first line.  fin (NCHW bf16 [B][2L][h][w], or NULL when no later tile reads
+ *                       it) <- v.  The rectangle y < keep_h, x < keep_w goes to (y0 + y, x0 + x) of moments, NCHW bf16
+ *                       [B][2L][moments_h][moments_w]; nothing else of it is written.  E == 0 or no neighbour: quant_conv and place.
+ *                       L = 4 (with or without a quant_conv) and L = 16 (without) are built; anything else, a quant_conv at
+ *                       L = 16 included, is DA_ERR_UNSUPPORTED.  DA_ERR_INVALID and no launch for: src or moments NULL, one of wq /
+ *                       bq without the other, weights NULL where something blends, a non-positive size, E < 0, negative strides, a
+ *                       neighbour with hu < E or wl < E, keep_h > h or keep_w > w or either < 1, a rectangle outside moments,
+ *                       B > 65535, h w >= 2^31.  Runs once per tile of an encode, outside any recorded step: no DA_FN_* plan number
+ *                       (DA_ABI_VERSION stays 9).
+ * ------------------------------------------------------------------------------------------------------------------ */
+int da_vae_moments_tile_blend(const void* src, long long sB, long long sC, long long sP, const void* wq, const void* bq,
+                              const void* up, int hu, const void* left, int wl, const void* weights, int E, void* fin, void* moments,
+                              int B, int L, int h, int w, int keep_h, int keep_w, long long moments_h, long long moments_w,
+                              long long y0, long long x0, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------------
  * Launch plans: a recorded sequence of the launch entry points above, owned by the library and replayed by ONE call --
  * the C-ABI form of the denoising step the Python pipelines capture into a HIP graph (the reference's per-step work,
  * pipeline_stable_diffusion_xl.py:1186-1250: scale_model_input, the U-Net forward, the CFG combine, scheduler.step; and the
