@@ -37,10 +37,26 @@ _DEFAULTS = dict(
 )
 
 
+# head sizes da_attention_bf16 has a flash kernel for: csrc/attention.hip / attention2.hip, and csrc/attention_wide.hip for one wide head
+FLASH_HEAD_DIMS = (64, 96, 128, 160, 256, 384, 512)
+# Wide heads (>= 256): where the flash kernel is the default route, measured (profiles/wide_attention_numbers.md, D = 512).  It runs one
+# 64-query workgroup per CU, so its time goes with ceil(rounds) * S for rounds = B * ceil(S / 64) / 256 CUs, the three-launch GEMM
+# path's with B * S^2: the GEMM path wins below one round (S 4096: 0.11 against 0.35 ms) and while the last round is mostly empty
+# (S 24576, 1.5 rounds: 3.75 against 4.25 ms); the flash kernel ties or wins at whole rounds (S 16384: 1.55 against 1.60 ms, S 32768:
+# 5.81 / 6.63, S 65536: 22.8 / 27.4) with 1 / 25 of the memory.  Flash iff rounds >= 1 and ceil(rounds) <= TAIL * rounds.
+WIDE_FLASH_MIN_ROUNDS, WIDE_FLASH_TAIL, _CUS = 1.0, 1.04, 256
+
+
+def wide_flash_pays(B: int, S: int) -> bool:
+    rounds = B * ((S + 63) // 64) / _CUS
+    return rounds >= WIDE_FLASH_MIN_ROUNDS and -(-rounds // 1) <= WIDE_FLASH_TAIL * rounds
+
+
 class VaeAttention:
     """Legacy single-head Attention block of the VAE mid block (attention_processor.py:2696-2787 with a 4-D input:
-    GroupNorm, to_q/k/v WITH bias, residual connection).  head_dim = channels (512 for SD/SDXL): handled as
-    scores = Q K^T (fp32) -> row softmax -> P V with the MFMA GEMM; a flash-kernel head size uses the flash kernel.
+    GroupNorm, to_q/k/v WITH bias, residual connection).  head_dim = channels (512 for SD/SDXL): a flash-kernel head size uses the
+    flash kernel (512: csrc/attention_wide.hip); any other, or ``force_gemm_path``, is handled as
+    scores = Q K^T (fp32) -> row softmax -> P V with the MFMA GEMM.
     The V bias is folded into the output bias (softmax rows sum to 1):  W_o (P (V + 1 b_v^T)) + b_o = W_o P V + (W_o b_v + b_o)."""
 
     def __init__(self, w: Weights, prefix: str, groups: int, eps: float, heads: int = 1):
@@ -71,7 +87,7 @@ class VaeAttention:
         S = H * W_
         res = x.view(B * S, C)
         h = self.group_norm(x).view(B * S, C)
-        if S % 8 and self.head_dim in (64, 96, 128, 160) and not self.force_gemm_path:
+        if S % 8 and self.head_dim in FLASH_HEAD_DIMS and not self.force_gemm_path:
             # a token count that is no multiple of 8 (the one- and two-line edge tiles of a tiled encode): the flash kernel takes whole
             # groups of 8 ALLOCATED keys, so K and V^T go into zero-padded buffers and Skv masks the keys past S
             S8, n = (S + 7) // 8 * 8, self.inner
@@ -85,9 +101,26 @@ class VaeAttention:
                               k_row_stride=n, q_batch_stride=S * 2 * n, k_batch_stride=S8 * n, vt_ld=B * S8, vt_batch_stride=S8,
                               scale=self.scale)
             return ops.linear(o, self.wo, self.bo, residual=res).view(B, H, W_, C)
+        if S % 8:
+            # the GEMM route on such a token count (``force_gemm_path``; the GEMMs take no 25-wide operand): the same three launches
+            # per batch on keys zero-padded to the K granule of 64 -- zero K rows, zero probabilities against zero V^T columns
+            if self.heads != 1:
+                raise ValueError("VaeAttention GEMM path supports a single head")
+            n, Sp = self.inner, (S + 63) // 64 * 64
+            qk = ops.linear(h, self.wqk, self.bqk).view(B, S, 2 * n)
+            v = ops.linear(h, self.wv).view(B, S, n)
+            o = torch.empty((B * S, n), device=x.device, dtype=bf16)
+            k, vt = torch.zeros((Sp, n), device=x.device, dtype=bf16), torch.zeros((n, Sp), device=x.device, dtype=bf16)
+            probs = torch.zeros((S, Sp), device=x.device, dtype=bf16)
+            for b in range(B):
+                k[:S], vt[:, :S] = qk[b, :, n:], v[b].t()
+                scores = ops.linear(qk[b, :, :n], k, alpha=self.scale, out_f32=True)           # [S][Sp] fp32
+                ops.softmax_rows(scores[:, :S], out=probs)
+                ops.linear(probs, vt, out=o[b * S:(b + 1) * S])
+            return ops.linear(o, self.wo, self.bo, residual=res).view(B, H, W_, C)
         # [B*S][2C] and [C][B*S] (V bias folded into self.bo): one paired launch (layers.Attention)
         qk, vt = ops.linear_pair({"x": h, "w": self.wqk, "bias": self.bqk}, {"x": self.wv, "w": h})
-        if self.head_dim in (64, 96, 128, 160) and not self.force_gemm_path:
+        if self.head_dim in FLASH_HEAD_DIMS and not self.force_gemm_path and (self.head_dim < 256 or wide_flash_pays(B, S)):
             o = ops.attention(qk, qk[:, self.inner:], vt, B=B, H=self.heads, D=self.head_dim, Sq=S, Skv=S, Skv_alloc=S,
                               q_row_stride=2 * self.inner, k_row_stride=2 * self.inner,
                               q_batch_stride=S * 2 * self.inner, k_batch_stride=S * 2 * self.inner,
@@ -95,10 +128,12 @@ class VaeAttention:
         else:
             if self.heads != 1:
                 raise ValueError("VaeAttention GEMM path supports a single head")
-            # One head of D = 512: scores GEMM (fp32) -> row softmax -> P.V GEMM, in blocks of QBLK query rows so that the score
-            # matrix held at any time is QBLK x S (268 MB at S = 16 384 instead of 1 GB + 0.5 GB of probabilities).  Measured
-            # (profiles/README.md): the two GEMMs run at ~900 TFLOP/s here; a flash kernel at D = 512 would either recompute Q.K^T per
-            # 128-wide output slice (2.5x the flops) or exchange partial scores between waves every tile -- slower than this path.
+            # One wide head where the flash kernel does not pay (wide_flash_pays above), or on request: scores GEMM (fp32) -> row
+            # softmax -> P.V GEMM, in blocks of QBLK query rows so that the score matrix held at any time is QBLK x S (268 MB at
+            # S = 16 384 instead of 1 GB + 0.5 GB of probabilities).  Measured at D = 512 (profiles/wide_attention_numbers.md): this
+            # path runs at 6.0-6.6 ps per (query, key) pair at every S from 4096 to 65 536 (~330 TFLOP/s with the softmax's traffic);
+            # the flash kernel (one wave owns 16 queries and the whole 512-wide accumulator: no recompute, no exchange) matches it
+            # once its workgroups fill the 256 CUs in whole rounds, and holds S x 1 KB instead of QBLK x S x 6 B.
             o = torch.empty((B * S, C), device=x.device, dtype=bf16)
             QBLK = 4096
             nb = min(QBLK, S)

@@ -15,7 +15,9 @@ every per-frame op) and
   * the temporal upsampler's (3,1,1) conv runs on frames 1.. (the reference's first chunk is "Rep": it bypasses
     time_conv and is not part of its history, :275-296), its 2C output channels are re-laid as frame pairs by one copy
     kernel, and nearest-2x + Conv2d is one fused-gather launch over all frames;
-  * per-frame single-head attention (head_dim = C = 384) is QK^T (fp32) -> row softmax -> PV on the MFMA GEMM.
+  * per-frame single-head attention (head_dim = C = 384) is ONE wide-head flash launch with the frames as its batch
+    (csrc/attention_wide.hip; measured 3.58 against 5.07 ms for the block at 21 x 60 x 104, profiles/wide_attention_numbers.md);
+    narrower test widths keep QK^T (fp32) -> row softmax -> PV on the MFMA GEMM, frame by frame.
 
 Channel counts that are not a multiple of 64 (96 at full size) are zero-padded to the next multiple once, at load:
 padded weights / gammas are zero, so padded channels stay exactly zero through every op.
@@ -128,9 +130,15 @@ class ResidualBlock:
         return self.conv2(self.norm2(y, silu=True), residual=h)
 
 
+# padded channel counts the wide-head flash kernel serves (csrc/attention_wide.hip); narrower ones keep the per-frame loop
+WIDE_HEAD_DIMS = (256, 384, 512)
+
+
 class AttentionBlock:
     """WanAttentionBlock: per-frame, one head of width C.  to_qkv's V bias is folded into the projection bias (softmax
-    rows sum to 1), V is produced directly transposed ([C][positions]) as the PV GEMM's weight operand, and the key
+    rows sum to 1).  A wide head (WIDE_HEAD_DIMS; 384 at full size) whose frame has a multiple of 8 positions runs ONE flash
+    launch over all frames.  Otherwise, or with ``force_gemm_path``, each frame is QK^T (fp32) -> row softmax -> PV on the MFMA
+    GEMM: V is produced directly transposed ([C][positions]) as the PV GEMM's weight operand, and the key
     axis is zero-padded to a multiple of 64 (the GEMM's K granule)."""
 
     def __init__(self, w: Weights, p: str):
@@ -149,12 +157,21 @@ class AttentionBlock:
         self.bo = _pad_to((wo.float() @ bqkv[2 * c:].float() + bo.float()).to(bf16), (cp,))
         self.wo = _pad_to(wo, (cp, cp))
         self.scale = c ** -0.5
+        self.force_gemm_path = False
 
     def __call__(self, x):
         T, H, W_, cp = x.shape
         S = H * W_
         Sp = _pad64(S)
         h = self.norm(x).view(T * S, cp)
+        if cp in WIDE_HEAD_DIMS and S % 8 == 0 and not self.force_gemm_path:
+            # one wide head per frame: Q | K and V^T ([cp][T*S]) of ALL frames from one paired launch, then ONE flash launch with the
+            # frames as its batch (csrc/attention_wide.hip).  Padded channels are zero in Q, K and V^T and stay zero in the output;
+            # the scale is the real channel count's.
+            qk, vt = ops.linear_pair({"x": h, "w": self.wqk, "bias": self.bqk}, {"x": self.wv, "w": h})
+            o = ops.attention(qk, qk[:, cp:], vt, B=T, H=1, D=cp, Sq=S, Skv=S, Skv_alloc=S, q_row_stride=2 * cp, k_row_stride=2 * cp,
+                              q_batch_stride=S * 2 * cp, k_batch_stride=S * 2 * cp, vt_ld=T * S, vt_batch_stride=S, scale=self.scale)
+            return ops.linear(o, self.wo, self.bo, residual=x.view(T * S, cp)).view(T, H, W_, cp)
         qk = ops.linear(h, self.wqk, self.bqk)                               # [T*S][2 cp]
         o = torch.empty((T * S, cp), device=x.device, dtype=bf16)
         vt = torch.zeros((cp, Sp), device=x.device, dtype=bf16)              # zero key padding, reused per frame

@@ -19,6 +19,9 @@ CSRC = PKG_DIR / "csrc"
 OUT_DIR = PKG_DIR / "_C"
 LIB_PATH = OUT_DIR / "libdiffusers_amd.so"
 ARCH = "gfx950"
+# extra flags of single translation units.  attention_wide.hip: no packed fp32 VALU forms (v_pk_mul_f32 and kin) for the accumulator
+# rescale -- plain v_mul_f32, as the device-side code generator is told through its target feature.
+UNIT_FLAGS = {"attention_wide.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
 
 
 def _hipcc() -> str:
@@ -75,10 +78,12 @@ def build_extension(force: bool = False, verbose: bool = False) -> Path:
         f"-I{ROOT / 'include'}", f"-I{CSRC}",
     ]
     objs = []
+    base_flags = flags
 
     def compile_one(src: Path) -> Path:
         # per-object stamp: the source, the headers it includes (transitively) and the flags -- an unchanged translation unit is
         # not recompiled (the two GEMM families take minutes)
+        flags = base_flags + UNIT_FLAGS.get(src.name, [])
         obj = OUT_DIR / (src.stem + ".o")
         ostamp = OUT_DIR / (src.stem + ".o.stamp")
         ofp = _unit_fingerprint(src, flags)

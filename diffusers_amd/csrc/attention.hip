@@ -27,6 +27,7 @@
 #include "common.cuh"
 
 int da_attn2_dispatch(const da_attention_params& p, hipStream_t s);   // attention2.hip
+int da_attn_wide_dispatch(const da_attention_params& p, hipStream_t s);   // attention_wide.hip
 
 namespace {
 
@@ -715,6 +716,8 @@ extern "C" int da_attention_bf16(const da_attention_params* pp, void* stream) {
     return DA_ERR_UNSUPPORTED;
   if ((p.q_batch_stride & 7) || (p.k_batch_stride & 7) || (p.o_batch_stride & 3)) return DA_ERR_UNSUPPORTED;
   hipStream_t s = (hipStream_t)stream;
+  // one wide head (VAE mid blocks): a kernel of its own, unmasked and without variants
+  if (p.D == 256 || p.D == 384 || p.D == 512) return da_attn_wide_dispatch(p, s);
   // second generation (attention2.hip) unless the caller pinned the first one or one of its variants
   const bool pinned_v1 = p.algo == 1 || (p.algo == 0 && (p.ring_slots == 2 || p.q_block == 64 || p.pv_delay != 0));
   if (!pinned_v1 && (p.o_row_stride & 3) == 0) {

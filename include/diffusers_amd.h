@@ -301,7 +301,10 @@ int da_gemm_tune(const da_gemm_params* p, const da_gemm_params* pair, void* stre
  *   out element (b, s, h, d) at out + b*o_batch_stride + s*o_row_stride + h*D + d
  *   Skv = number of keys attended; Skv_alloc (multiple of 8, >= Skv) = keys present in memory per batch.
  *   Keys [Skv, Skv_alloc) of K and V^T may hold any finite value and do not influence the result.
- *   D in {64, 96, 128, 160} (SD1.5's head dims 40 / 80 are zero-padded to 64 / 96 by the host-side weight packing).
+ *   D in {64, 96, 128, 160} (SD1.5's head dims 40 / 80 are zero-padded to 64 / 96 by the host-side weight packing), and the
+ *   wide heads D in {256, 384, 512} (attention_wide.hip: the single-head mid-block attention of the VAEs, vae.py /
+ *   autoencoder_kl_wan.py:389-431).  A wide head has ONE kernel: unmasked, with ring_slots, q_block, pv_delay and algo all 0 (anything
+ *   else: DA_ERR_UNSUPPORTED); kv_split / split_ws are ignored there.
  *   All strides in elements, multiples of 8 (o: 4).
  * ------------------------------------------------------------------------------------------------------------------ */
 typedef struct da_attention_params {
