@@ -107,6 +107,8 @@ PASS_THROUGH = {
     "da_vae_tile_blend": "runs once per tile of a tiled decode, outside any recorded step; ops.vae_tile_blend refuses under a recording",
     "da_vae_moments_tile_blend": "runs once per tile of a tiled / sliced encode, outside any recorded step; ops.vae_moments_tile_blend "
                                  "refuses under a recording",
+    "da_freeu_nhwc_bf16": "part of a U-Net step with FreeU enabled, which runs eagerly or as a captured HIP graph: a plan number belongs "
+                          "to a later ABI bump; ops.freeu refuses under a recording",
 }
 
 
@@ -176,6 +178,8 @@ SIGNATURES = {
                                _vp]),
     "da_vae_moments_tile_blend": (_i, [_vp, _ll, _ll, _ll, _vp, _vp, _vp, _i, _vp, _i, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _ll,
                                        _ll, _ll, _ll, _vp]),
+    "da_freeu_workspace_bytes": (C.c_size_t, [_i, _i, _i, _i, _i]),
+    "da_freeu_nhwc_bf16": (_i, [_vp, _vp, _vp, _vp, _vp, _ll, _i, _i, _i, _i, _i, _f, _f, _i, _vp]),
     "da_plan_create": (_i, [C.POINTER(PlanOp), _i, C.POINTER(C.c_void_p)]),
     "da_plan_launch": (_i, [_vp, _vp, C.POINTER(C.c_int)]),
     "da_plan_relocate": (_i, [_vp, _i, C.POINTER(C.c_void_p), C.POINTER(C.c_ulonglong), C.POINTER(C.c_void_p),
@@ -190,6 +194,7 @@ SIGNATURES = {
 IMAGE_F32_NCHW, IMAGE_F32_NHWC, IMAGE_U8_NHWC = 0, 1, 2
 POSTERIOR_MOMENTS, POSTERIOR_MEAN, POSTERIOR_SAMPLE, POSTERIOR_NOISE = 0, 1, 2, 3
 LATENTS_SHIFT, LATENTS_SCALE = 1, 2
+FREEU_AUTO, FREEU_RESIDENT, FREEU_TWO_LAUNCH = 0, 1, 2   # da_freeu_nhwc_bf16 `path`
 
 ABI_VERSION = 9              # include/diffusers_amd.h DA_ABI_VERSION
 _lib = None

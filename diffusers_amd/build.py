@@ -21,7 +21,8 @@ LIB_PATH = OUT_DIR / "libdiffusers_amd.so"
 ARCH = "gfx950"
 # extra flags of single translation units.  attention_wide.hip: no packed fp32 VALU forms (v_pk_mul_f32 and kin) for the accumulator
 # rescale -- plain v_mul_f32, as the device-side code generator is told through its target feature.
-UNIT_FLAGS = {"attention_wide.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
+_NO_PACKED_FP32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
+UNIT_FLAGS = {"attention_wide.hip": _NO_PACKED_FP32, "freeu.hip": _NO_PACKED_FP32}
 
 
 def _hipcc() -> str:

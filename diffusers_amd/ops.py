@@ -1688,6 +1688,50 @@ def vae_moments_tile_blend(src: torch.Tensor, strides, *, batch: int, latent_cha
     return fin
 
 
+# ---- FreeU (csrc/freeu.hip) --------------------------------------------------------------------------------------------------
+_freeu_twiddle_cache = {}
+
+
+def freeu_twiddles(height: int, width: int, device) -> torch.Tensor:
+    """fp32 [2H + 2W] = cos(2 pi h / H) | sin(2 pi h / H) | cos(2 pi w / W) | sin(2 pi w / W), evaluated in float64 and rounded: the
+    twiddles of the four low DFT bins da_freeu_nhwc_bf16 projects on.  Cached per (H, W, device)."""
+    H, W_, device = int(height), int(width), torch.device(device)
+    key = (H, W_, device)
+    t = _freeu_twiddle_cache.get(key)
+    if t is None:
+        th = 2 * torch.pi * torch.arange(H, dtype=torch.float64) / H
+        pw = 2 * torch.pi * torch.arange(W_, dtype=torch.float64) / W_
+        t = _freeu_twiddle_cache[key] = torch.cat([th.cos(), th.sin(), pw.cos(), pw.sin()]).float().to(device)
+    return t
+
+
+def freeu(hidden: torch.Tensor, skip: torch.Tensor, *, s: float, b: float, path: int = L.FREEU_AUTO) -> torch.Tensor:
+    """da_freeu_nhwc_bf16 (csrc/freeu.hip; arithmetic in include/diffusers_amd.h): the reference's apply_freeu on the channels-last
+    pair an up-block resnet reads.  ``hidden`` [B][H][W][Cx]: its first Cx / 2 channels are scaled by ``b`` IN PLACE; ``skip``
+    [B][H][W][Cs] is read only and its Fourier-filtered copy (the four lowest bins scaled by ``s``) is returned.  ``path``:
+    L.FREEU_AUTO / FREEU_RESIDENT / FREEU_TWO_LAUNCH.  The entry has no plan number: refused while a launch plan is being recorded."""
+    if getattr(L._tls, "recorder", None) is not None:
+        raise RuntimeError("freeu: not replayable by a launch plan (da_freeu_nhwc_bf16 has no DA_FN_* number); run a step with FreeU "
+                           "eagerly or as a captured HIP graph")
+    _req(hidden, "hidden"), _req(skip, "skip")
+    if hidden.dim() != 4 or skip.dim() != 4 or not hidden.is_contiguous() or not skip.is_contiguous() or hidden.shape[:3] != skip.shape[:3]:
+        raise ValueError(f"freeu: contiguous NHWC tensors of one batch and size required, got hidden {tuple(hidden.shape)} and skip "
+                         f"{tuple(skip.shape)}")
+    B, H, W_, Cx = hidden.shape
+    Cs = skip.shape[3]
+    if H < 2 or W_ < 2:
+        raise ValueError(f"freeu: a {H} x {W_} plane has no four distinct low-frequency bins (height and width must be >= 2)")
+    if Cx % 16 or Cs % 8:
+        raise NotImplementedError(f"freeu: hidden channels % 16 == 0 and skip channels % 8 == 0 required, got {Cx} and {Cs}")
+    lib = L.load()
+    nbytes = int(lib.da_freeu_workspace_bytes(B, H, W_, Cs, int(path)))
+    ws = torch.empty(nbytes // 4, device=skip.device, dtype=torch.float32) if nbytes else None
+    out = torch.empty_like(skip)
+    L.check(lib.da_freeu_nhwc_bf16(hidden.data_ptr(), skip.data_ptr(), out.data_ptr(), freeu_twiddles(H, W_, skip.device).data_ptr(),
+                                   _ptr(ws), nbytes, B, H, W_, Cx, Cs, float(b), float(s), int(path), _stream()), "da_freeu_nhwc_bf16")
+    return out
+
+
 def vae_posterior_latents(x: torch.Tensor, strides, *, batch: int, hw: int, latent_channels: int, mode: int,
                           wq: Optional[torch.Tensor] = None, bq: Optional[torch.Tensor] = None, eps1: Optional[torch.Tensor] = None,
                           eps2: Optional[torch.Tensor] = None, shift: Optional[float] = None, scale: Optional[float] = None,

@@ -254,12 +254,19 @@ def _weights_token(model) -> int:
     return model._weights_generation
 
 
+def _model_token(model):
+    """The model's entry of a graph key: the generation of its weights, followed -- where the model's forward takes more by value
+    (``UNet2DConditionModel.graph_token``: FreeU's four floats) -- by those values."""
+    extra = model.graph_token() if hasattr(model, "graph_token") else ()
+    return (_weights_token(model),) + tuple(extra) if extra else _weights_token(model)
+
+
 def _key_tail(scheduler, model, sample) -> tuple:
     """The part of every ``_make_graph_key`` that names the scheduler's and the model's side of a captured step: the addresses of
     the coefficient table and of the device step counter, the generation of the packed weights, the scheduler's further device
     state (DPM-Solver++: the loop's begin word and the x0 history; UniPC: coefficients and history) and what the step takes
     from the scheduler by value (the sampler kernel, scale_model_input, pred_type)."""
-    return (scheduler.device_table.data_ptr(), scheduler.device_step.data_ptr(), _weights_token(model),
+    return (scheduler.device_table.data_ptr(), scheduler.device_step.data_ptr(), _model_token(model),
             scheduler.graph_buffers(sample), scheduler.graph_token())
 
 
@@ -425,6 +432,20 @@ class _LatentDiffusionBase(_VaeTilingMixin, _StepCallbacks, _CapturedStepLoop, P
     def set_progress_bar_config(self, **kw):
         pass
 
+    # ---- FreeU (pipeline_stable_diffusion_xl.py enable_freeu / disable_freeu) -----------------------------------------------
+    def enable_freeu(self, s1: float, s2: float, b1: float, b2: float):
+        """FreeU on the U-Net's first two up blocks (``UNet2DConditionModel.enable_freeu``; SDXL's usual values: s1 = 0.9, s2 = 0.2,
+        b1 = 1.3, b2 = 1.4).  Runs eagerly and under the captured HIP graph (the values are part of the graph key: the next call
+        recaptures); ``use_graph="plan"`` is refused while it is on."""
+        if not hasattr(self, "unet") or self.unet is None:
+            raise ValueError("The pipeline must have `unet` for using FreeU.")
+        self.unet.enable_freeu(s1=s1, s2=s2, b1=b1, b2=b2)
+
+    def disable_freeu(self):
+        if not hasattr(self, "unet") or self.unet is None:
+            raise ValueError("The pipeline must have `unet` for using FreeU.")
+        self.unet.disable_freeu()
+
     # ---- the captured step -------------------------------------------------------------------------------------
     def _model_input(self, latents, do_cfg):
         """scale_model_input + CFG batch doubling: what the denoiser (and a ControlNet next to it) reads in one step."""
@@ -527,8 +548,12 @@ class _LatentDiffusionBase(_VaeTilingMixin, _StepCallbacks, _CapturedStepLoop, P
         return decode_postprocessed(self.vae, latents, output_type, latents_div=float(vc.scaling_factor))
 
     # ---- the parts of a call the six SD / SDXL pipelines share (the flavours add _prompt_inputs and _conditioning) ------------
-    def _arm(self, guidance_scale, guidance_rescale, callback_on_step_end, callback_on_step_end_tensor_inputs) -> bool:
+    def _arm(self, guidance_scale, guidance_rescale, callback_on_step_end, callback_on_step_end_tensor_inputs,
+             use_graph=True) -> bool:
         """What every call sets before anything reads it; returns ``do_cfg``."""
+        if use_graph == "plan" and self.unet.graph_token():
+            raise NotImplementedError('use_graph="plan" with FreeU enabled: da_freeu_nhwc_bf16 has no launch-plan number; call '
+                                      "with use_graph=True (captured HIP graph) or False, or disable_freeu() first")
         self._guidance_rescale = float(guidance_rescale)    # pipeline_stable_diffusion_xl.py:849, :1227-1229
         self._arm_callback(callback_on_step_end, callback_on_step_end_tensor_inputs)
         self._guidance_scale = float(guidance_scale)
@@ -712,7 +737,7 @@ class StableDiffusionXLPipeline(_LatentDiffusionBase):
                  callback_on_step_end_tensor_inputs=None, timesteps=None, sigmas=None, denoising_end: Optional[float] = None,
                  original_inference_steps: Optional[int] = None):
         self._original_inference_steps = original_inference_steps
-        do_cfg = self._arm(guidance_scale, guidance_rescale, callback_on_step_end, callback_on_step_end_tensor_inputs)
+        do_cfg = self._arm(guidance_scale, guidance_rescale, callback_on_step_end, callback_on_step_end_tensor_inputs, use_graph)
         embeds = self._prompt_inputs(prompt, prompt_2, negative_prompt, negative_prompt_2, num_images_per_prompt, prompt_embeds,
                                      negative_prompt_embeds, pooled_prompt_embeds, negative_pooled_prompt_embeds, clip_skip, do_cfg)
         height = height or self.default_sample_size * self.vae_scale_factor
@@ -777,7 +802,7 @@ class StableDiffusionPipeline(_LatentDiffusionBase):
                  output_type: str = "pt", return_dict: bool = True, generator=None, use_graph: bool = True,
                  negative_prompt=None, num_images_per_prompt: int = 1, clip_skip=None, guidance_rescale: float = 0.0,
                  callback_on_step_end=None, callback_on_step_end_tensor_inputs=None):
-        do_cfg = self._arm(guidance_scale, guidance_rescale, callback_on_step_end, callback_on_step_end_tensor_inputs)
+        do_cfg = self._arm(guidance_scale, guidance_rescale, callback_on_step_end, callback_on_step_end_tensor_inputs, use_graph)
         embeds = self._prompt_inputs(prompt, negative_prompt, num_images_per_prompt, prompt_embeds, negative_prompt_embeds, clip_skip,
                                      do_cfg)
         height = height or self.unet.config.sample_size * self.vae_scale_factor
@@ -1034,7 +1059,7 @@ class StableDiffusionXLImg2ImgPipeline(_Img2ImgMixin, StableDiffusionXLPipeline)
         if denoising_start is not None and _denoising_value_valid(denoising_end) and denoising_start >= denoising_end:
             raise ValueError(f"`denoising_start`: {denoising_start} cannot be larger than or equal to `denoising_end`: "
                              f"{denoising_end} when using type float.")
-        do_cfg = self._arm(guidance_scale, guidance_rescale, callback_on_step_end, callback_on_step_end_tensor_inputs)
+        do_cfg = self._arm(guidance_scale, guidance_rescale, callback_on_step_end, callback_on_step_end_tensor_inputs, use_graph)
         embeds = self._prompt_inputs(prompt, prompt_2, negative_prompt, negative_prompt_2, num_images_per_prompt, prompt_embeds,
                                      negative_prompt_embeds, pooled_prompt_embeds, negative_pooled_prompt_embeds, clip_skip, do_cfg)
         B = embeds[0].shape[0]
@@ -1090,7 +1115,7 @@ class StableDiffusionImg2ImgPipeline(_Img2ImgMixin, StableDiffusionPipeline):
         _refuse_tiny_vae(self.vae, type(self).__name__)
         if image is None:
             raise ValueError("`image` input cannot be undefined.")
-        do_cfg = self._arm(guidance_scale, guidance_rescale, callback_on_step_end, callback_on_step_end_tensor_inputs)
+        do_cfg = self._arm(guidance_scale, guidance_rescale, callback_on_step_end, callback_on_step_end_tensor_inputs, use_graph)
         embeds = self._prompt_inputs(prompt, negative_prompt, num_images_per_prompt, prompt_embeds, negative_prompt_embeds, clip_skip,
                                      do_cfg)
         B = embeds[0].shape[0]
@@ -1402,7 +1427,7 @@ class _InstructPix2PixMixin:
                                       "pipelines (`controlnet` must be None)")
 
     def _arm_pix2pix(self, guidance_scale, image_guidance_scale, guidance_rescale, ip_adapter_image, ip_adapter_image_embeds,
-                     padding_mask_crop, callback_on_step_end, callback_on_step_end_tensor_inputs) -> bool:
+                     padding_mask_crop, callback_on_step_end, callback_on_step_end_tensor_inputs, use_graph=True) -> bool:
         """The refusals of a call and what every call sets first; returns ``do_cfg``: the reference's
         ``guidance_scale > 1.0 and image_guidance_scale >= 1.0`` -- otherwise the batch is not tripled and nothing is combined."""
         who = type(self).__name__
@@ -1417,7 +1442,7 @@ class _InstructPix2PixMixin:
         if _time_cond_dim(self.unet) is not None:
             raise NotImplementedError(f"{who}: a U-Net with `time_cond_proj_dim` (guidance-scale embedding of the distilled LCM "
                                       "checkpoints) has no InstructPix2Pix checkpoint and no engine path here")
-        self._arm(guidance_scale, 0.0, callback_on_step_end, callback_on_step_end_tensor_inputs)
+        self._arm(guidance_scale, 0.0, callback_on_step_end, callback_on_step_end_tensor_inputs, use_graph)
         self._image_guidance_scale = float(image_guidance_scale)
         return guidance_scale > 1.0 and image_guidance_scale >= 1.0
 
@@ -1512,7 +1537,7 @@ class StableDiffusionInstructPix2PixPipeline(_InstructPix2PixMixin, StableDiffus
                  callback_on_step_end=None, callback_on_step_end_tensor_inputs=None, clip_skip=None, height: Optional[int] = None,
                  width: Optional[int] = None, padding_mask_crop=None, guidance_rescale: float = 0.0, use_graph: bool = True):
         do_cfg = self._arm_pix2pix(guidance_scale, image_guidance_scale, guidance_rescale, ip_adapter_image, ip_adapter_image_embeds,
-                                   padding_mask_crop, callback_on_step_end, callback_on_step_end_tensor_inputs)
+                                   padding_mask_crop, callback_on_step_end, callback_on_step_end_tensor_inputs, use_graph)
         embeds = self._prompt_inputs(prompt, negative_prompt, num_images_per_prompt, prompt_embeds, negative_prompt_embeds, clip_skip,
                                      do_cfg)
         self._set_schedule(num_inference_steps, None, None)
@@ -1560,7 +1585,7 @@ class StableDiffusionXLInstructPix2PixPipeline(_InstructPix2PixMixin, StableDiff
                  clip_skip=None, callback_on_step_end=None, callback_on_step_end_tensor_inputs=None, padding_mask_crop=None,
                  use_graph: bool = True):
         do_cfg = self._arm_pix2pix(guidance_scale, image_guidance_scale, guidance_rescale, ip_adapter_image, ip_adapter_image_embeds,
-                                   padding_mask_crop, callback_on_step_end, callback_on_step_end_tensor_inputs)
+                                   padding_mask_crop, callback_on_step_end, callback_on_step_end_tensor_inputs, use_graph)
         embeds = self._prompt_inputs(prompt, prompt_2, negative_prompt, negative_prompt_2, num_images_per_prompt, prompt_embeds,
                                      negative_prompt_embeds, pooled_prompt_embeds, negative_pooled_prompt_embeds, clip_skip, do_cfg)
         self._set_schedule(num_inference_steps, None, None)

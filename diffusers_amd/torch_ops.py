@@ -18,6 +18,7 @@ name ends in ``_``).  Registration happens on import of this module (``import di
     x_next = torch.ops.mi355x.euler_ancestral_step(eps, x, noise, table, step_idx, True, 5.0, 0, 0)
     x_next, m1 = torch.ops.mi355x.dpmpp_2m_step(eps, x, m1, table, step_idx, begin_idx, True, 5.0, 0)
     fin, moments = torch.ops.mi355x.vae_moments_tile_blend(raw, sB, sC, sP, wq, bq, up, left, moments, 4, h, w, E, y0, x0, kh, kw)
+    hidden, skip = torch.ops.mi355x.freeu(hidden, skip, 0.9, 1.3)  # apply_freeu, channels-last
 """
 from __future__ import annotations
 
@@ -160,5 +161,19 @@ def _(src, stride_b, stride_c, stride_p, wq, bq, up, left, moments, latent_chann
     return moments.new_empty((moments.shape[0], 2 * latent_channels, height, width)), torch.empty_like(moments)
 
 
+@torch.library.custom_op(f"{NAMESPACE}::freeu", mutates_args=(), device_types="cuda")
+def freeu(hidden: torch.Tensor, skip: torch.Tensor, s: float, b: float) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The reference's apply_freeu on channels-last [B][H][W][C] tensors (da_freeu_nhwc_bf16): returns (hidden with its first half of
+    the channels scaled by ``b``, skip with its four lowest Fourier bins scaled by ``s``).  Functional form of the kernel, which
+    scales ``hidden`` in place: ``hidden`` is copied."""
+    h = hidden.contiguous().clone()
+    return h, ops.freeu(h, skip.contiguous(), s=s, b=b)
+
+
+@freeu.register_fake
+def _(hidden, skip, s, b):
+    return torch.empty_like(hidden), torch.empty_like(skip)
+
+
 OPS = ("gemm", "conv2d_nhwc", "flash_attn", "groupnorm", "layernorm", "euler_step", "dpmpp_2m_step", "euler_ancestral_step",
-       "vae_moments_tile_blend")
+       "vae_moments_tile_blend", "freeu")

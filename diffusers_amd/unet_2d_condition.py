@@ -108,6 +108,32 @@ class UNet2DConditionModel(PretrainedMixin):
         self._built = False
 
     # ------------------------------------------------------------------------------------------------------------
+    # FreeU (unet_2d_condition.py enable_freeu / disable_freeu; unet_2d_blocks.py: up blocks with resolution_idx 0 and 1)
+    # ------------------------------------------------------------------------------------------------------------
+    _freeu = None      # (s1, s2, b1, b2) as given, or None
+
+    def enable_freeu(self, s1: float, s2: float, b1: float, b2: float):
+        """FreeU (https://arxiv.org/abs/2309.11497): in the first two up blocks, scale the first half of the backbone channels by
+        ``b1`` / ``b2`` and the four lowest Fourier bins of every skip connection by ``s1`` / ``s2`` (ops.freeu, one fused launch per
+        resnet).  As in the reference a stage is on when all four values are truthy.  The values are kernel arguments of a captured
+        step: they are part of the pipelines' graph keys (``graph_token``)."""
+        self._freeu = (s1, s2, b1, b2)
+
+    def disable_freeu(self):
+        self._freeu = None
+
+    def _freeu_stage(self, resolution_idx: int):
+        """(s, b) of up block ``resolution_idx``, or None: the reference's ``is_freeu_enabled`` and apply_freeu's two branches."""
+        f = self._freeu
+        if f is None or resolution_idx > 1 or not all(f):
+            return None
+        return (float(f[0]), float(f[2])) if resolution_idx == 0 else (float(f[1]), float(f[3]))
+
+    def graph_token(self) -> tuple:
+        """What ``forward`` bakes into a captured step by value, besides the weights: FreeU's four floats while a stage is on."""
+        return () if self._freeu_stage(0) is None else ("freeu",) + tuple(float(v) for v in self._freeu)
+
+    # ------------------------------------------------------------------------------------------------------------
     # weights
     # ------------------------------------------------------------------------------------------------------------
     def load_state_dict(self, state_dict: Dict[str, torch.Tensor], device="cuda", strict: bool = True):
@@ -432,9 +458,14 @@ class UNet2DConditionModel(PretrainedMixin):
             controlnet_handoff(skips, x)
 
         # 5. up (skip concat fused into the resnets)
-        for st in self.up:
+        for i, st in enumerate(self.up):
+            freeu = self._freeu_stage(i)
             for j, rn in enumerate(st["resnets"]):
                 skip = skips.pop()
+                if freeu is not None:
+                    # apply_freeu, in front of the (fused) concat: x is this walk's own tensor, scaled in place; the skip list's
+                    # tensor stays as it is
+                    skip = ops.freeu(x, skip, s=freeu[0], b=freeu[1])
                 x = rn(x, emb, skip=skip)
                 if st["attns"]:
                     x = st["attns"][j](x, kvs[ki])

@@ -745,6 +745,39 @@ int da_vae_moments_tile_blend(const void* src, long long sB, long long sC, long 
                               long long y0, long long x0, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------------
+ * FreeU (unet_2d_blocks.py up blocks with resolution_idx 0 / 1, torch_utils.py apply_freeu / fourier_filter with threshold = 1) on
+ * the channels-last (hidden, skip) pair a resnet of an up block reads in place of the reference's concat (csrc/freeu.hip).
+ *   da_freeu_nhwc_bf16  hidden: NHWC bf16 [B][H][W][Cx]; its first Cx / 2 channels are scaled IN PLACE, h = bf16(float(h) * b): one
+ *                       fp32 multiply, one rounding (a bf16 tensor times a Python float); the other half is not touched.  skip: NHWC
+ *                       bf16 [B][H][W][Cs], read only.  skip_out: the same shape, every element written.  The reference scales the
+ *                       2 x 2 box [H/2 - 1, H/2] x [W/2 - 1, W/2] of the shifted spectrum by s; fftshift puts frequency k at k + H/2
+ *                       (even and odd H alike), so those are the bins {-1, 0} x {-1, 0} and no FFT is run: with t_h = 2 pi h / H,
+ *                       p_w = 2 pi w / W, per (image, channel) plane x, fp32 throughout:
+ *                         S0 = sum x    Ac = sum x cos t_h    As = sum x sin t_h    Bc = sum x cos p_w    Bs = sum x sin p_w
+ *                         Cc = sum x cos(t_h + p_w)           Cs = sum x sin(t_h + p_w)
+ *                         y = bf16(x + (s - 1) / (H W) (S0 + Ac cos t_h + As sin t_h + Bc cos p_w + Bs sin p_w
+ *                                                       + Cc cos(t_h + p_w) + Cs sin(t_h + p_w)))           one rounding, at the end
+ *                       evaluated separably (per row r0 / rc / rs = sum_w x (1, cos p_w, sin p_w), folded with the row's cos t_h / sin
+ *                       t_h; per row P + Qc cos p_w + Qs sin p_w); (s - 1) / (H W) is evaluated in double.  s == 1 and b == 1 return
+ *                       both tensors' bits (finite sums).  Sums run in a fixed order (no atomics): a result depends on the inputs
+ *                       and on (B, H, W, Cs, path) alone.  twiddles: fp32 [2H + 2W] = cos t_h (H) | sin t_h (H) | cos p_w (W) |
+ *                       sin p_w (W), evaluated in double on the host and rounded.  path: 0 = automatic, 1 = one launch with the
+ *                       (image, channel slab) plane resident in LDS (DA_ERR_UNSUPPORTED where it does not fit 144 KiB), 2 = two launches
+ *                       (per-band partial sums [B][bands][7][Cs] fp32 in the workspace, summed in ascending band order by the second).
+ *                       workspace: da_freeu_workspace_bytes(B, H, W, Cs, path) bytes = 4 * B * bands * 7 * Cs on the two-launch
+ *                       path (bands <= 32 row bands, cut so that a launch has >= 256 workgroups), 0 (the pointer may be NULL) on
+ *                       the resident one; the bytes are scratch.  H = 2 (frequency -1 is Nyquist) needs no special case.
+ *                       DA_ERR_INVALID and no launch for: hidden, skip, skip_out or twiddles NULL, a workspace that is NULL or
+ *                       smaller than needed, a non-positive size, H W >= 2^31, a base not 16-byte aligned (twiddles: 4), s or b not
+ *                       finite, a path outside 0 .. 2.  DA_ERR_UNSUPPORTED for Cs % 8 != 0, Cx % 16 != 0, H == 1 or W == 1 (the two
+ *                       bins coincide), H + W > 4096.  The entry has no DA_FN_* plan number (DA_ABI_VERSION stays 9): a step with
+ *                       FreeU runs eagerly or as a captured HIP graph, not as a launch plan.
+ * ------------------------------------------------------------------------------------------------------------------ */
+size_t da_freeu_workspace_bytes(int B, int H, int W, int Cs, int path);
+int da_freeu_nhwc_bf16(void* hidden, const void* skip, void* skip_out, const void* twiddles, void* workspace,
+                       long long workspace_bytes, int B, int H, int W, int Cx, int Cs, float b, float s, int path, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------------
  * Launch plans: a recorded sequence of the launch entry points above, owned by the library and replayed by ONE call --
  * the C-ABI form of the denoising step the Python pipelines capture into a HIP graph (the reference's per-step work,
  * pipeline_stable_diffusion_xl.py:1186-1250: scale_model_input, the U-Net forward, the CFG combine, scheduler.step; and the
