@@ -109,6 +109,10 @@ PASS_THROUGH = {
                                  "refuses under a recording",
     "da_freeu_nhwc_bf16": "part of a U-Net step with FreeU enabled, which runs eagerly or as a captured HIP graph: a plan number belongs "
                           "to a later ABI bump; ops.freeu refuses under a recording",
+    "da_resample_u8": "resizes an input image once per call, in front of the encoder and outside any recorded step; ops.resample_u8 "
+                      "refuses under a recording",
+    "da_gather_resize": "resizes an input tensor once per call, in front of the encoder and outside any recorded step; "
+                        "ops.gather_resize refuses under a recording",
 }
 
 
@@ -180,6 +184,9 @@ SIGNATURES = {
                                        _ll, _ll, _ll, _vp]),
     "da_freeu_workspace_bytes": (C.c_size_t, [_i, _i, _i, _i, _i]),
     "da_freeu_nhwc_bf16": (_i, [_vp, _vp, _vp, _vp, _vp, _ll, _i, _i, _i, _i, _i, _f, _f, _i, _vp]),
+    "da_resample_u8_route": (_i, [_i, _i, _i, _i, _i, _i, _i, _i, _i, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_longlong)]),
+    "da_resample_u8": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _vp, _ll, _i, _i, _i, _i, _i, _i, _i, _vp]),
+    "da_gather_resize": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "da_plan_create": (_i, [C.POINTER(PlanOp), _i, C.POINTER(C.c_void_p)]),
     "da_plan_launch": (_i, [_vp, _vp, C.POINTER(C.c_int)]),
     "da_plan_relocate": (_i, [_vp, _i, C.POINTER(C.c_void_p), C.POINTER(C.c_ulonglong), C.POINTER(C.c_void_p),
@@ -195,6 +202,7 @@ IMAGE_F32_NCHW, IMAGE_F32_NHWC, IMAGE_U8_NHWC = 0, 1, 2
 POSTERIOR_MOMENTS, POSTERIOR_MEAN, POSTERIOR_SAMPLE, POSTERIOR_NOISE = 0, 1, 2, 3
 LATENTS_SHIFT, LATENTS_SCALE = 1, 2
 FREEU_AUTO, FREEU_RESIDENT, FREEU_TWO_LAUNCH = 0, 1, 2   # da_freeu_nhwc_bf16 `path`
+RESAMPLE_AUTO, RESAMPLE_ONE_LAUNCH, RESAMPLE_TWO_LAUNCH = 0, 1, 2   # da_resample_u8 `route`
 
 ABI_VERSION = 9              # include/diffusers_amd.h DA_ABI_VERSION
 _lib = None

@@ -6,6 +6,8 @@ gfx950 kernel in ``csrc/``.  Nothing in this module has a CPU or PyTorch fallbac
 from __future__ import annotations
 
 import ctypes as C
+import functools
+import math
 import os
 import threading
 import weakref
@@ -1730,6 +1732,138 @@ def freeu(hidden: torch.Tensor, skip: torch.Tensor, *, s: float, b: float, path:
     L.check(lib.da_freeu_nhwc_bf16(hidden.data_ptr(), skip.data_ptr(), out.data_ptr(), freeu_twiddles(H, W_, skip.device).data_ptr(),
                                    _ptr(ws), nbytes, B, H, W_, Cx, Cs, float(b), float(s), int(path), _stream()), "da_freeu_nhwc_bf16")
     return out
+
+
+# ---- image resizing (csrc/resample.hip) ------------------------------------------------------------------------------------------
+def _lanczos(x: float) -> float:
+    if not -3.0 <= x < 3.0:
+        return 0.0
+    if x == 0.0:
+        return 1.0
+    a, b = x * math.pi, x / 3 * math.pi
+    return math.sin(a) / a * (math.sin(b) / b)
+
+
+def _bicubic(x: float) -> float:
+    x, a = abs(x), -0.5
+    if x < 1.0:
+        return ((a + 2.0) * x - (a + 3.0)) * x * x + 1
+    return (((x - 5) * x + 8) * x - 4) * a if x < 2.0 else 0.0
+
+
+def _bilinear(x: float) -> float:
+    x = abs(x)
+    return 1.0 - x if x < 1.0 else 0.0
+
+
+RESAMPLE_FILTERS = {"lanczos": (_lanczos, 3.0), "bicubic": (_bicubic, 2.0), "bilinear": (_bilinear, 1.0)}
+
+
+@functools.lru_cache(maxsize=64)
+def resample_tables(in_size: int, out_size: int, filter: str = "lanczos"):
+    """Pillow's ``precompute_coeffs`` + ``normalize_coeffs_8bpc`` (Resample.c) for one axis, in Python floats (doubles) with libm's
+    ``sin``: ``(coef int32 [out][ksize], bounds int32 [out][2] = (xmin, xcount), ksize)`` as da_resample_u8 reads them (CPU tensors,
+    cached: treat them as read-only)."""
+    if filter not in RESAMPLE_FILTERS:
+        raise ValueError(f"`resample` must be one of 'lanczos', 'bicubic', 'bilinear', got {filter!r}")
+    in_size, out_size = int(in_size), int(out_size)
+    if in_size < 1 or out_size < 1:
+        raise ValueError(f"resample_tables: sizes must be positive, got {in_size} -> {out_size}")
+    f, s = RESAMPLE_FILTERS[filter]
+    scale = in_size / out_size
+    fscale = max(scale, 1.0)
+    support = s * fscale
+    ksize = math.ceil(support) * 2 + 1
+    ss = 1.0 / fscale
+    coef = [[0] * ksize for _ in range(out_size)]
+    bounds = []
+    for o in range(out_size):
+        center = (o + 0.5) * scale
+        xmin = max(0, int(center - support + 0.5))
+        n = min(in_size, int(center + support + 0.5)) - xmin
+        w = [f((i + xmin - center + 0.5) * ss) for i in range(n)]
+        ww = 0.0
+        for v in w:
+            ww += v
+        if ww != 0.0:
+            w = [v / ww for v in w]
+        coef[o][:n] = [int(-0.5 + v * (1 << 22)) if v < 0 else int(0.5 + v * (1 << 22)) for v in w]
+        bounds.append((xmin, n))
+    return torch.tensor(coef, dtype=torch.int32), torch.tensor(bounds, dtype=torch.int32), ksize
+
+
+@functools.lru_cache(maxsize=64)
+def _resample_tables_on(in_size: int, out_size: int, filter: str, device):
+    coef, bounds, ksize = resample_tables(in_size, out_size, filter)
+    return coef.to(device), bounds.to(device), ksize
+
+
+def resample_route(batch: int, in_hw, out_hw, channels: int, filter: str = "lanczos", route: int = L.RESAMPLE_AUTO):
+    """da_resample_u8_route (host only): ``(route, (TH, TW), workspace bytes)`` da_resample_u8 takes for this shape -- route
+    L.RESAMPLE_ONE_LAUNCH with its output tile, or L.RESAMPLE_TWO_LAUNCH with the bytes of the intermediate image."""
+    (hi, wi), (ho, wo) = in_hw, out_hw
+    ksh = 0 if wi == wo else resample_tables(wi, wo, filter)[2]
+    ksv = 0 if hi == ho else resample_tables(hi, ho, filter)[2]
+    th, tw, ws = C.c_int(0), C.c_int(0), C.c_longlong(0)
+    r = L.load().da_resample_u8_route(int(batch), hi, wi, ho, wo, int(channels), ksh, ksv, int(route), C.byref(th), C.byref(tw),
+                                      C.byref(ws))
+    L.check(-r if r < 0 else 0, "da_resample_u8_route")
+    return r, (th.value, tw.value), ws.value
+
+
+def _refuse_recording(what: str, entry: str) -> None:
+    if getattr(L._tls, "recorder", None) is not None:
+        raise RuntimeError(f"{what}: not replayable by a launch plan ({entry} has no DA_FN_* number); it runs once per call, in front "
+                           "of the recorded step")
+
+
+def resample_u8(src: torch.Tensor, size, filter: str = "lanczos", *, route: int = L.RESAMPLE_AUTO) -> torch.Tensor:
+    """da_resample_u8 (csrc/resample.hip): ``PIL.Image.resize(size, resample=filter)`` of packed uint8 images [B][H][W][C] (C = 1 or 3)
+    to ``size = (height, width)``, to the bit.  ``filter``: 'lanczos', 'bicubic' or 'bilinear'."""
+    _refuse_recording("resample_u8", "da_resample_u8")
+    _req(src, "src", torch.uint8)
+    if src.dim() != 4 or not src.is_contiguous() or src.shape[3] not in (1, 3):
+        raise ValueError(f"resample_u8: a contiguous uint8 [B][H][W][C] image with C = 1 or 3 is required, got {tuple(src.shape)}")
+    B, hi, wi, ch = src.shape
+    ho, wo = int(size[0]), int(size[1])
+    _, _, nbytes = resample_route(B, (hi, wi), (ho, wo), ch, filter, route)
+    hc, hb, ksh = _resample_tables_on(wi, wo, filter, src.device) if wi != wo else (None, None, 0)
+    vc, vb, ksv = _resample_tables_on(hi, ho, filter, src.device) if hi != ho else (None, None, 0)
+    ws = torch.empty(nbytes, device=src.device, dtype=torch.uint8) if nbytes else None
+    dst = torch.empty((B, ho, wo, ch), device=src.device, dtype=torch.uint8)
+    L.check(L.load().da_resample_u8(src.data_ptr(), dst.data_ptr(), _ptr(hc), _ptr(hb), ksh, _ptr(vc), _ptr(vb), ksv, _ptr(ws), nbytes,
+                                    B, hi, wi, ho, wo, ch, int(route), _stream()), "da_resample_u8")
+    return dst
+
+
+@functools.lru_cache(maxsize=64)
+def nearest_indices(in_size: int, out_size: int) -> torch.Tensor:
+    """F.interpolate(mode="nearest")'s source index of every output index: ``min(int(floorf(o * float32(in / out))), in - 1)``
+    (int32 CPU tensor, cached)."""
+    scale = torch.tensor(in_size, dtype=torch.float32) / torch.tensor(out_size, dtype=torch.float32)
+    idx = torch.floor(torch.arange(out_size, dtype=torch.float32) * scale).to(torch.int32)
+    return idx.clamp_(max=in_size - 1)
+
+
+@functools.lru_cache(maxsize=64)
+def _nearest_indices_on(in_size: int, out_size: int, device):
+    return nearest_indices(in_size, out_size).to(device)
+
+
+def gather_resize(src: torch.Tensor, size, *, nchw: bool) -> torch.Tensor:
+    """da_gather_resize (csrc/resample.hip): ``F.interpolate(src, size)`` (nearest) of a contiguous fp32 or uint8 image batch, NCHW
+    ([B][C][H][W]) or NHWC ([B][H][W][C]): a gather through nearest_indices, bit-identical."""
+    _refuse_recording("gather_resize", "da_gather_resize")
+    require_hip(src, "src", dtypes=(torch.float32, torch.uint8))
+    if src.dim() != 4 or not src.is_contiguous():
+        raise ValueError(f"gather_resize: a contiguous 4-D image batch is required, got {tuple(src.shape)}")
+    B, ch, hi, wi = src.shape if nchw else (src.shape[0], src.shape[3], src.shape[1], src.shape[2])
+    ho, wo = int(size[0]), int(size[1])
+    dst = torch.empty((B, ch, ho, wo) if nchw else (B, ho, wo, ch), device=src.device, dtype=src.dtype)
+    L.check(L.load().da_gather_resize(src.data_ptr(), dst.data_ptr(), _nearest_indices_on(hi, ho, src.device).data_ptr(),
+                                      _nearest_indices_on(wi, wo, src.device).data_ptr(), B, ch, hi, wi, ho, wo, src.element_size(),
+                                      int(bool(nchw)), _stream()), "da_gather_resize")
+    return dst
 
 
 def vae_posterior_latents(x: torch.Tensor, strides, *, batch: int, hw: int, latent_channels: int, mode: int,

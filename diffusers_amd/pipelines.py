@@ -875,12 +875,71 @@ def encode_image_latents(vae, img: torch.Tensor, *, nchw: bool, normalize: bool)
     return dist
 
 
-def prepare_image(image, vae_scale_factor: int, latent_channels: int, device):
+class _ImageResizeMixin:
+    """``enable_image_resize`` / ``disable_image_resize`` of the image-reading pipelines: VaeImageProcessor.preprocess's resize
+    (image_processor.py resize / get_default_height_width), off by default.  On: every input image (mask, control image) is brought to
+    the call's ``height`` x ``width`` -- or, where none is given, to its own size rounded down to a multiple of the VAE scale factor
+    (FLUX: twice that) -- before anything else reads it: PIL images by da_resample_u8 (``Image.resize(..., resample)`` to the bit),
+    tensors and arrays by da_gather_resize (nearest, as the reference's F.interpolate).  Host state outside the captured step:
+    switching recaptures nothing, and images of any size that resize to one target replay one captured step."""
+
+    _image_resize = None      # the filter's name while the switch is on
+    _resize_multiple = 1      # target sizes are multiples of this many VAE scale factors (FLUX packs latents 2 x 2: 2)
+
+    def enable_image_resize(self, resample: str = "lanczos"):
+        if resample not in ops.RESAMPLE_FILTERS:
+            raise ValueError(f"`resample` must be one of 'lanczos', 'bicubic', 'bilinear', got {resample!r}")
+        self._image_resize = resample
+
+    def disable_image_resize(self):
+        self._image_resize = None
+
+    def _resize_spec(self, height, width):
+        """The ``resize`` argument of prepare_image / prepare_control_image: None while the switch is off."""
+        if self._image_resize is None:
+            return None
+        return (self._image_resize, height, width, self._resize_multiple * self.vae_scale_factor)
+
+
+def _resize_target(resize, H: int, W_: int) -> Tuple[int, int]:
+    """The size an ``H`` x ``W_`` input is resized to under ``resize = (filter, height, width, multiple)``."""
+    _, height, width, multiple = resize
+    for name, v in (("height", height), ("width", width)):
+        if v is not None and (v < multiple or v % multiple):
+            raise ValueError(f"`{name}` = {v}: with image resizing on, height and width must be positive multiples of {multiple}")
+    th, tw = (height if height is not None else H - H % multiple), (width if width is not None else W_ - W_ % multiple)
+    if th < 1 or tw < 1:
+        raise ValueError(f"`image` is {H} x {W_}: smaller than {multiple} pixels a side, nothing to round down to")
+    return th, tw
+
+
+def _pil_resized(images, to_array, target, resample: str, device) -> torch.Tensor:
+    """PIL images, each uploaded as it is and resized on the device: uint8 NHWC [n][height][width][C]."""
+    outs = []
+    for im in images:
+        a = to_array(im)
+        a = a[None, :, :, None] if a.ndim == 2 else a[None]
+        outs.append(ops.resample_u8(torch.from_numpy(np.ascontiguousarray(a)).to(device), target, resample))
+    return outs[0] if len(outs) == 1 else torch.cat(outs, 0)
+
+
+def _is_pil(x) -> bool:
+    return hasattr(x, "convert") and not torch.is_tensor(x) and not isinstance(x, np.ndarray)
+
+
+def prepare_image(image, vae_scale_factor: int, latent_channels: int, device, resize=None):
     """``image`` as the encoder reads it: ``("latents", NCHW tensor)`` for latents (``latent_channels`` channels: encode is skipped,
     as the reference does), else ``("image", tensor, nchw, normalize)`` for ops.vae_conv_in_image.  VaeImageProcessor.preprocess
     (image_processor.py:581-715): a torch tensor is NCHW in [0, 1] -- or already in [-1, 1] (its minimum < 0), then it is not
     normalised again; a numpy array is NHWC (float in [0, 1], or uint8 read as x / 255 like a PIL image); a PIL image is taken via
-    numpy.  The engine does not resize: sizes that are not a multiple of the VAE's scale factor are refused."""
+    numpy.  The engine does not resize: sizes that are not a multiple of the VAE's scale factor are refused -- unless ``resize``
+    (``_ImageResizeMixin._resize_spec``) is given: then PIL images are resampled and tensors / arrays gathered (nearest) to its
+    target, and latents are refused."""
+    if resize is not None:
+        pil = list(image) if isinstance(image, (list, tuple)) else [image]
+        if pil and all(_is_pil(i) for i in pil):
+            target = _resize_target(resize, pil[0].height, pil[0].width)
+            return ("image", _pil_resized(pil, lambda i: np.array(_pil_rgb(i)), target, resize[0], device), False, True)
     if isinstance(image, (list, tuple)):
         if not image:
             raise ValueError("`image` is an empty list")
@@ -899,6 +958,9 @@ def prepare_image(image, vae_scale_factor: int, latent_channels: int, device):
         if t.dim() != 4:
             raise ValueError(f"`image` tensor must be NCHW or CHW, got shape {tuple(image.shape)}")
         if t.shape[1] == latent_channels:
+            if resize is not None:
+                raise ValueError(f"`image` has {latent_channels} channels and is taken as latents, which are not resized: pass them "
+                                 "with image resizing off (disable_image_resize())")
             return ("latents", t.to(device=device, dtype=bf16).contiguous())
         if t.shape[1] != 3:
             raise ValueError(f"`image` tensor has {t.shape[1]} channels: 3 (an image) or {latent_channels} (latents) expected")
@@ -912,18 +974,26 @@ def prepare_image(image, vae_scale_factor: int, latent_channels: int, device):
             a = a.astype(np.float32)
         H, W_, nchw = a.shape[1], a.shape[2], False
         t = torch.from_numpy(np.ascontiguousarray(a)).to(device)
-    if H % vae_scale_factor or W_ % vae_scale_factor:
+    if resize is not None:
+        t = _gathered(t, _resize_target(resize, H, W_), nchw)
+    elif H % vae_scale_factor or W_ % vae_scale_factor:
         raise ValueError(f"`image` is {H} x {W_}: height and width must be multiples of the VAE scale factor {vae_scale_factor} "
                          "(the engine does not resize images)")
     normalize = t.dtype == torch.uint8 or not bool(t.min() < 0)
     return ("image", t, nchw, normalize)
 
 
+def _gathered(t: torch.Tensor, target, nchw: bool) -> torch.Tensor:
+    """A tensor or array input at the target size: the reference's F.interpolate (nearest) -- nothing where the size is right."""
+    have = tuple(t.shape[2:]) if nchw else tuple(t.shape[1:3])
+    return t if have == tuple(target) else ops.gather_resize(t, target, nchw=nchw)
+
+
 def _pil_rgb(img):
     return img.convert("RGB") if hasattr(img, "mode") and img.mode != "RGB" else img
 
 
-class _Img2ImgMixin:
+class _Img2ImgMixin(_ImageResizeMixin):
     """prepare_latents of the img2img pipelines: encode (or take latents), sample the posterior, scale, repeat to the batch, add noise --
     the posterior, scaling and add_noise fused into one kernel when the batch needs no repetition."""
 
@@ -957,7 +1027,7 @@ class _Img2ImgMixin:
             raise NotImplementedError("AutoencoderKL configs with latents_mean / latents_std are not supported by the engine "
                                       "pipelines (pass `image` as latents you normalised yourself)")
         dev = self.device
-        prep = prepare_image(image, self.vae_scale_factor, self.unet.config.in_channels, dev)
+        prep = prepare_image(image, self.vae_scale_factor, self.unet.config.in_channels, dev, self._resize_spec(None, None))
         if prep[0] == "latents":
             init = prep[1].clone()        # (the loop updates its latents in place: never the caller's tensor)
             dist = None
@@ -1142,16 +1212,17 @@ class StableDiffusionImg2ImgPipeline(_Img2ImgMixin, StableDiffusionPipeline):
 # ----------------------------------------------------------------------------------------------------------------------
 # inpainting (pipeline_stable_diffusion_inpaint.py, pipeline_stable_diffusion_xl_inpaint.py)
 # ----------------------------------------------------------------------------------------------------------------------
-def prepare_mask(mask_image, vae_scale_factor: int, device):
+def prepare_mask(mask_image, vae_scale_factor: int, device, resize=None):
     """``mask_image`` as the reference's mask processor leaves it (VaeImageProcessor(do_normalize=False, do_binarize=True,
     do_convert_grayscale=True).preprocess): fp32 ``[n][1][H][W]`` of zeros and ones, 1 where ``v >= 0.5`` -- 1 repaints, 0 keeps.
     Accepted: a torch tensor [H][W], [1][H][W] or [n][1][H][W] in [0, 1]; a numpy array HW, HW1 or nHW1, float in [0, 1] or uint8
     (read as x / 255); a PIL image (converted to "L", x / 255); a list of one kind.  The engine does not resize: sizes that are not
-    a multiple of the VAE's scale factor are refused, as images are."""
+    a multiple of the VAE's scale factor are refused, as images are -- unless ``resize = (filter, height, width)`` is given: then the
+    mask is brought to that size BEFORE it is binarised, a PIL mask by da_resample_u8, a tensor or array by da_gather_resize."""
     if isinstance(mask_image, (list, tuple)):
         if not mask_image:
             raise ValueError("`mask_image` is an empty list")
-        return torch.cat([prepare_mask(m, vae_scale_factor, device) for m in mask_image], 0)
+        return torch.cat([prepare_mask(m, vae_scale_factor, device, resize) for m in mask_image], 0)
     if torch.is_tensor(mask_image):
         t = mask_image
         if t.dim() == 2:
@@ -1171,13 +1242,18 @@ def prepare_mask(mask_image, vae_scale_factor: int, device):
             raise ValueError(f"`mask_image` array must be HW, HW1 or BHW1, got shape {tuple(mask_image.shape)}")
         v = torch.from_numpy(np.ascontiguousarray(a)).permute(0, 3, 1, 2)
         v = v.to(torch.float32) / 255.0 if a.dtype == np.uint8 else v.to(torch.float32)
+    elif hasattr(mask_image, "convert") and resize:         # PIL.Image, resized on the device
+        u8 = _pil_resized([mask_image], lambda i: np.array(i.convert("L")), resize[1:], resize[0], device)
+        v = u8.permute(0, 3, 1, 2).to(torch.float32) / 255.0
     elif hasattr(mask_image, "convert"):                    # PIL.Image
         v = torch.from_numpy(np.array(mask_image.convert("L"))).to(torch.float32)[None, None] / 255.0
     else:
         raise ValueError(f"`mask_image` has to be of type `torch.Tensor`, `np.ndarray`, `PIL.Image.Image` or a list of them, "
                          f"but is {type(mask_image)}")
     H, W_ = v.shape[-2], v.shape[-1]
-    if H % vae_scale_factor or W_ % vae_scale_factor:
+    if resize:
+        v = _gathered(v.to(device).contiguous(), resize[1:], True)
+    elif H % vae_scale_factor or W_ % vae_scale_factor:
         raise ValueError(f"`mask_image` is {H} x {W_}: height and width must be multiples of the VAE scale factor {vae_scale_factor} "
                          "(the engine does not resize masks)")
     return (v >= 0.5).to(device=device, dtype=torch.float32).contiguous()
@@ -1252,7 +1328,7 @@ class _InpaintMixin:
                                       "pipelines")
         dev, f = self.device, self.vae_scale_factor
         nu = self._check_inpaint_unet(4 if masked_image_latents is None else int(masked_image_latents.shape[1]))
-        prep = prepare_image(image, f, vc.latent_channels, dev)
+        prep = prepare_image(image, f, vc.latent_channels, dev, self._resize_spec(height, width))
         if prep[0] == "latents":
             img = None
             image_latents = prep[1].clone()
@@ -1262,7 +1338,7 @@ class _InpaintMixin:
             H, W_ = img.shape[-2], img.shape[-1]
         if (height is not None and height != H) or (width is not None and width != W_):
             raise ValueError(f"`height` x `width` = {height} x {width} but `image` is {H} x {W_} (the engine does not resize)")
-        mask = prepare_mask(mask_image, f, dev)
+        mask = prepare_mask(mask_image, f, dev, self._image_resize and (self._image_resize, H, W_))
         if tuple(mask.shape[-2:]) != (H, W_):
             raise ValueError(f"`mask_image` is {mask.shape[-2]} x {mask.shape[-1]} but `image` is {H} x {W_} (the engine does not "
                              "resize masks)")
@@ -1406,7 +1482,7 @@ class StableDiffusionXLInpaintPipeline(_InpaintMixin, StableDiffusionXLImg2ImgPi
 # ----------------------------------------------------------------------------------------------------------------------
 # InstructPix2Pix (pipeline_stable_diffusion_instruct_pix2pix.py, pipeline_stable_diffusion_xl_instruct_pix2pix.py)
 # ----------------------------------------------------------------------------------------------------------------------
-class _InstructPix2PixMixin:
+class _InstructPix2PixMixin(_ImageResizeMixin):
     """Instruction-based image editing on top of the text-to-image pipelines (timbrooks/instruct-pix2pix; SDXL-edit, CosXL-edit): an
     8-channel U-Net reads the latents and the UNSCALED mode of the image's posterior, and guidance runs over a batch of three --
     (text, image, unconditional), the last with a zero image -- with two scales.  The reference builds ``torch.cat([latents] * 3)``,
@@ -1457,7 +1533,7 @@ class _InstructPix2PixMixin:
         if vc.get("latents_mean") is not None or vc.get("latents_std") is not None:
             raise NotImplementedError("AutoencoderKL configs with latents_mean / latents_std are not supported by the engine pipelines")
         dev, f = self.device, self.vae_scale_factor
-        prep = prepare_image(image, f, vc.latent_channels, dev)
+        prep = prepare_image(image, f, vc.latent_channels, dev, self._resize_spec(height, width))
         if prep[0] == "latents":
             il = prep[1].clone()
         else:
@@ -1601,17 +1677,21 @@ class StableDiffusionXLInstructPix2PixPipeline(_InstructPix2PixMixin, StableDiff
 # ----------------------------------------------------------------------------------------------------------------------
 # ControlNet (pipelines/controlnet/pipeline_controlnet.py, pipeline_controlnet_sd_xl.py)
 # ----------------------------------------------------------------------------------------------------------------------
-def prepare_control_image(image, vae_scale_factor: int, device):
+def prepare_control_image(image, vae_scale_factor: int, device, resize=None):
     """The control image as ``ControlNetModel.precompute_conditioning`` reads it: ``(tensor, nchw)``.  VaeImageProcessor.preprocess
     with ``do_normalize=False`` (pipeline_controlnet.py:232-234): pixels stay in [0, 1].  A torch tensor is NCHW (or CHW) in [0, 1];
     a numpy array is NHWC / HWC (float in [0, 1], or uint8 read as x / 255 like a PIL image); a PIL image is taken via numpy.  The
-    engine does not resize: sides that are not a multiple of the VAE's scale factor are refused.  One image or one batch -- a list
-    (of images, or of images per ControlNet) is refused."""
+    engine does not resize: sides that are not a multiple of the VAE's scale factor are refused -- unless ``resize``
+    (``_ImageResizeMixin._resize_spec``) is given: then the image is brought to the output size as prepare_image does it.  One
+    image or one batch -- a list (of images, or of images per ControlNet) is refused."""
     if isinstance(image, (list, tuple)):
         raise NotImplementedError("`image` as a list (several control images, or one per ControlNet of a MultiControlNetModel) is not "
                                   "supported: pass one image, or a batch as one tensor / array")
     if image is None:
         raise ValueError("`image` (the control image) is required")
+    if resize is not None and _is_pil(image):
+        target = _resize_target(resize, image.height, image.width)
+        return _pil_resized([image], lambda i: np.array(_pil_rgb(i)), target, resize[0], device), False
     if not torch.is_tensor(image) and not isinstance(image, np.ndarray):
         if hasattr(image, "convert"):                       # PIL.Image
             image = np.asarray(_pil_rgb(image))
@@ -1631,7 +1711,9 @@ def prepare_control_image(image, vae_scale_factor: int, device):
             a = a.astype(np.float32)
         H, W_, nchw = a.shape[1], a.shape[2], False
         t = torch.from_numpy(np.ascontiguousarray(a)).to(device)
-    if H % vae_scale_factor or W_ % vae_scale_factor:
+    if resize is not None:
+        t = _gathered(t, _resize_target(resize, H, W_), nchw)
+    elif H % vae_scale_factor or W_ % vae_scale_factor:
         raise ValueError(f"`image` is {H} x {W_}: height and width must be multiples of the VAE scale factor {vae_scale_factor} "
                          "(the engine does not resize images)")
     return t, nchw
@@ -1651,7 +1733,7 @@ def control_image_batch(image: torch.Tensor, batch: int, num_images_per_prompt: 
     return torch.cat([image] * 2, 0).contiguous() if do_cfg else image.contiguous()
 
 
-class _ControlNetMixin:
+class _ControlNetMixin(_ImageResizeMixin):
     """The ControlNet pipelines on top of the text-to-image ones: every step runs ``controlnet.features`` on the U-Net's own
     (scaled, CFG-doubled) input, and the U-Net forward takes the zero convs as its ``controlnet_handoff`` -- launches of the
     engine only, so the step captures into a HIP graph or a strict launch plan like the base pipelines' steps.  Once per call:
@@ -1689,7 +1771,7 @@ class _ControlNetMixin:
                                       "ControlNet runs in every step)")
         if isinstance(controlnet_conditioning_scale, (list, tuple)) or torch.is_tensor(controlnet_conditioning_scale):
             raise NotImplementedError("`controlnet_conditioning_scale` is one float (several ControlNets are not supported)")
-        t, nchw = prepare_control_image(image, self.vae_scale_factor, self.device)
+        t, nchw = prepare_control_image(image, self.vae_scale_factor, self.device, self._resize_spec(height, width))
         H, W_ = (t.shape[2], t.shape[3]) if nchw else (t.shape[1], t.shape[2])
         if (height is not None and height != H) or (width is not None and width != W_):
             raise ValueError(f"`image` is {H} x {W_} but height x width = {height} x {width} was asked for (the engine does not "
@@ -1961,7 +2043,7 @@ def flux_get_timesteps(scheduler, num_inference_steps: int, strength: float):
     return scheduler.timesteps[begin:], num_inference_steps - t_start, begin
 
 
-class FluxImg2ImgPipeline(FluxPipeline):
+class FluxImg2ImgPipeline(_ImageResizeMixin, FluxPipeline):
     """pipelines/flux/pipeline_flux_img2img.py on the engine (FLUX.1-schnell protocol, as FluxPipeline): same components, the same
     captured step, packing, ids and decode; the loop starts at the scheduler's begin index.  The front of the call is ONE kernel
     (ops.flux_prepare_latents): the encoder's conv_out result -> posterior sample -> (z - shift_factor) * scaling_factor ->
@@ -1970,6 +2052,8 @@ class FluxImg2ImgPipeline(FluxPipeline):
     bf16 -- the FLUX pipelines run the VAE in the pipeline dtype and never upcast it.  ``latents=`` (B, 16, h, w) are taken as the
     noise: moved, not re-drawn.  Not built: resizing (the image's sides set height / width), ``padding_mask_crop``, the Fill and
     dev (guidance-embedding) checkpoints."""
+
+    _resize_multiple = 2
 
     def get_timesteps(self, num_inference_steps, strength, device=None):
         ts, n, _ = flux_get_timesteps(self.scheduler, num_inference_steps, strength)
@@ -2008,7 +2092,7 @@ class FluxImg2ImgPipeline(FluxPipeline):
         if nch != vc.latent_channels:
             raise NotImplementedError(f"a transformer with in_channels = {self.transformer.config.in_channels} does not read the "
                                       f"{vc.latent_channels}-channel latents of this VAE packed 2 x 2")
-        prep = prepare_image(image, f, nch, dev)
+        prep = prepare_image(image, f, nch, dev, self._resize_spec(height, width))
         if prep[0] == "latents":
             lh, lw = prep[1].shape[-2], prep[1].shape[-1]
         else:
@@ -2103,7 +2187,7 @@ class FluxInpaintPipeline(FluxImg2ImgPipeline):
     def _prepare_mask(self, mask_image, H, W_, lh, lw, batch):
         if mask_image is None:
             raise ValueError("`mask_image` input cannot be undefined.")
-        mask = prepare_mask(mask_image, self.vae_scale_factor, self.device)
+        mask = prepare_mask(mask_image, self.vae_scale_factor, self.device, self._image_resize and (self._image_resize, H, W_))
         if tuple(mask.shape[-2:]) != (H, W_):
             raise ValueError(f"`mask_image` is {mask.shape[-2]} x {mask.shape[-1]} but `image` is {H} x {W_} (the engine does not "
                              "resize masks)")

@@ -19,6 +19,8 @@ name ends in ``_``).  Registration happens on import of this module (``import di
     x_next, m1 = torch.ops.mi355x.dpmpp_2m_step(eps, x, m1, table, step_idx, begin_idx, True, 5.0, 0)
     fin, moments = torch.ops.mi355x.vae_moments_tile_blend(raw, sB, sC, sP, wq, bq, up, left, moments, 4, h, w, E, y0, x0, kh, kw)
     hidden, skip = torch.ops.mi355x.freeu(hidden, skip, 0.9, 1.3)  # apply_freeu, channels-last
+    small = torch.ops.mi355x.resample_u8(img_u8_nhwc, 768, 1024, "lanczos")   # PIL.Image.resize, to the bit
+    small = torch.ops.mi355x.gather_resize(img, 768, 1024, True)              # F.interpolate (nearest), NCHW
 """
 from __future__ import annotations
 
@@ -175,5 +177,29 @@ def _(hidden, skip, s, b):
     return torch.empty_like(hidden), torch.empty_like(skip)
 
 
+@torch.library.custom_op(f"{NAMESPACE}::resample_u8", mutates_args=(), device_types="cuda")
+def resample_u8(src: torch.Tensor, height: int, width: int, resample: str) -> torch.Tensor:
+    """PIL.Image.resize((width, height), resample) of packed uint8 [B][H][W][C] images, C = 1 or 3, to the bit (da_resample_u8);
+    ``resample``: 'lanczos', 'bicubic' or 'bilinear'."""
+    return ops.resample_u8(src.contiguous(), (height, width), resample)
+
+
+@resample_u8.register_fake
+def _(src, height, width, resample):
+    return src.new_empty((src.shape[0], height, width, src.shape[3]))
+
+
+@torch.library.custom_op(f"{NAMESPACE}::gather_resize", mutates_args=(), device_types="cuda")
+def gather_resize(src: torch.Tensor, height: int, width: int, nchw: bool) -> torch.Tensor:
+    """F.interpolate(src, (height, width)) (nearest) of an fp32 or uint8 image batch, NCHW or NHWC (da_gather_resize)."""
+    return ops.gather_resize(src.contiguous(), (height, width), nchw=nchw)
+
+
+@gather_resize.register_fake
+def _(src, height, width, nchw):
+    B = src.shape[0]
+    return src.new_empty((B, src.shape[1], height, width) if nchw else (B, height, width, src.shape[3]))
+
+
 OPS = ("gemm", "conv2d_nhwc", "flash_attn", "groupnorm", "layernorm", "euler_step", "dpmpp_2m_step", "euler_ancestral_step",
-       "vae_moments_tile_blend", "freeu")
+       "vae_moments_tile_blend", "freeu", "resample_u8", "gather_resize")

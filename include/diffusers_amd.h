@@ -778,6 +778,46 @@ int da_freeu_nhwc_bf16(void* hidden, const void* skip, void* skip_out, const voi
                        long long workspace_bytes, int B, int H, int W, int Cx, int Cs, float b, float s, int path, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------------
+ * Image resizing in front of the image-reading pipelines (image_processor.py VaeImageProcessor.resize; csrc/resample.hip).
+ *   da_resample_u8      Pillow's 8-bit Image.resize (Resample.c, horizontal then vertical pass) to the bit.  src: packed uint8
+ *                       [B][Hin][Win][C], dst: packed uint8 [B][Hout][Wout][C], C = 1 or 3, every byte of dst written once; offsets
+ *                       are long long.  Per axis two device tables (ops.resample_tables, Pillow's precompute_coeffs and
+ *                       normalize_coeffs_8bpc): coef int32 [out][ksize] in 22-bit fixed point, bounds int32 [out][2] = (xmin, xcount).
+ *                       One output sample along an axis is
+ *                         clip8((2^21 + sum_{i < xcount} in[xmin + i] * coef[o][i]) >> 22)
+ *                       int32 sum, arithmetic shift, clip8 clamps to 0 .. 255.  The horizontal pass (hcoef, hbounds, ksize_h; Win ->
+ *                       Wout) runs first and rounds to uint8, the vertical pass (vcoef, vbounds, ksize_v; Hin -> Hout) reads those
+ *                       bytes.  A pass whose input size equals its output size is skipped and its tables may be NULL.  Integer sums
+ *                       are order-independent: every split of the work -- either route, any tile -- gives the same bytes.
+ *                       route: 0 = automatic; 1 = one launch (a workgroup owns a TH x TW output tile, stages the input row segments
+ *                       its vertical bounds name into LDS as whole 16-byte lines, runs the horizontal pass into an LDS uint8 tile and
+ *                       the vertical pass out of it) or DA_ERR_UNSUPPORTED where no tile of {32 x 64, 16 x 32, 8 x 16} fits 64 KiB of
+ *                       LDS; 2 = the horizontal pass into `workspace` [B][Hin][Wout][C] (Pillow's temporary image), then the vertical
+ *                       pass out of it (one launch and no workspace where a pass is skipped).  Automatic takes 1 where a tile fits:
+ *                       every upscale, any moderate downscale.  What the tables name is clamped to the image: no table content makes
+ *                       the kernels read outside src.  DA_ERR_UNSUPPORTED and no launch for: C outside {1, 3}, a size <= 0, a table
+ *                       of a pass that runs NULL or its ksize <= 0, a workspace NULL or smaller than da_resample_u8_route reports,
+ *                       more than 2^31 - 1 bytes in one image.  DA_ERR_INVALID for src or dst NULL, a route outside 0 .. 2, a
+ *                       table not 4-byte aligned, and -- one-launch route -- src not 16-byte aligned.
+ *   da_resample_u8_route  host only: the route da_resample_u8 takes for this shape (1 or 2; -DA_ERR_* where it would refuse), the tile
+ *                       (0 x 0 on route 2) and the workspace bytes it needs (0 on route 1 and where a pass is skipped).
+ *   da_gather_resize    nearest-neighbour resize (F.interpolate's default: the reference's route for tensors and arrays) as a gather
+ *                       through one int32 source-index table per axis: dst[.., y, x] = src[.., yidx[y], xidx[x]] for elements of
+ *                       elem_bytes = 4 (fp32) or 1 (uint8), nchw != 0: [B][C][H][W], else [B][H][W][C].  A copy: bit-identical by
+ *                       construction; indices are clamped to the image.  DA_ERR_INVALID for a NULL pointer or misaligned fp32;
+ *                       DA_ERR_UNSUPPORTED for a size <= 0 or another elem_bytes.
+ * Both run once per call in front of the VAE / ControlNet input path, outside any recorded step: no DA_FN_* plan number
+ * (DA_ABI_VERSION stays 9); their wrappers refuse inside a plan recording.
+ * ------------------------------------------------------------------------------------------------------------------ */
+int da_resample_u8_route(int B, int Hin, int Win, int Hout, int Wout, int C, int ksize_h, int ksize_v, int route, int* tile_h,
+                         int* tile_w, long long* workspace_bytes);
+int da_resample_u8(const void* src, void* dst, const int* hcoef, const int* hbounds, int ksize_h, const int* vcoef, const int* vbounds,
+                   int ksize_v, void* workspace, long long workspace_bytes, int B, int Hin, int Win, int Hout, int Wout, int C, int route,
+                   void* stream);
+int da_gather_resize(const void* src, void* dst, const int* yidx, const int* xidx, int B, int C, int Hin, int Win, int Hout, int Wout,
+                     int elem_bytes, int nchw, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------------
  * Launch plans: a recorded sequence of the launch entry points above, owned by the library and replayed by ONE call --
  * the C-ABI form of the denoising step the Python pipelines capture into a HIP graph (the reference's per-step work,
  * pipeline_stable_diffusion_xl.py:1186-1250: scale_model_input, the U-Net forward, the CFG combine, scheduler.step; and the
