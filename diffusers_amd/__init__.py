@@ -14,6 +14,10 @@ __version__ = "0.1.0"
 _EXPORTS = {
     "UNet2DConditionModel": "unet_2d_condition",
     "ControlNetModel": "controlnet",
+    "MotionAdapter": "motion_adapter",
+    "MotionModule": "motion_adapter",
+    "UNetMotionModel": "motion_adapter",
+    "AnimateDiffPipeline": "pipelines",
     "AutoencoderKL": "autoencoder_kl",
     "AutoencoderKLWan": "autoencoder_kl_wan",
     "AutoencoderTiny": "autoencoder_tiny",

@@ -81,6 +81,15 @@ class AttentionParams(C.Structure):
 ATTN_SPLIT_COUNTER_BYTES = 16384      # DA_ATTN_SPLIT_COUNTER_BYTES
 
 
+class AttentionTemporalParams(C.Structure):
+    _fields_ = [
+        ("q", C.c_void_p), ("k", C.c_void_p), ("v", C.c_void_p), ("out", C.c_void_p),
+        ("B", C.c_int), ("F", C.c_int), ("HW", C.c_int), ("H", C.c_int), ("D", C.c_int),
+        ("q_row_stride", C.c_int), ("k_row_stride", C.c_int), ("v_row_stride", C.c_int), ("o_row_stride", C.c_int),
+        ("scale", C.c_float),
+    ]
+
+
 # ---- launch plans (include/diffusers_amd.h "launch plans"; csrc/plan.hip) ----
 PLAN_MAX_ARGS = 16
 FN_IDS = {name: i + 1 for i, name in enumerate((
@@ -109,6 +118,8 @@ PASS_THROUGH = {
                                  "refuses under a recording",
     "da_freeu_nhwc_bf16": "part of a U-Net step with FreeU enabled, which runs eagerly or as a captured HIP graph: a plan number belongs "
                           "to a later ABI bump; ops.freeu refuses under a recording",
+    "da_attention_temporal_bf16": "part of a U-Net step with AnimateDiff motion modules, which runs eagerly or as a captured HIP graph: "
+                                  "a plan number belongs to a later ABI bump; ops.temporal_attention refuses under a recording",
     "da_resample_u8": "resizes an input image once per call, in front of the encoder and outside any recorded step; ops.resample_u8 "
                       "refuses under a recording",
     "da_gather_resize": "resizes an input tensor once per call, in front of the encoder and outside any recorded step; "
@@ -139,6 +150,7 @@ SIGNATURES = {
                           C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_float)]),
     "da_attention_bf16": (_i, [C.POINTER(AttentionParams), _vp]),
     "da_attention_split_plan": (_ll, [C.POINTER(AttentionParams), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "da_attention_temporal_bf16": (_i, [C.POINTER(AttentionTemporalParams), _vp]),
     "da_groupnorm_workspace_bytes": (C.c_size_t, [_i, _i, _i, _i]),
     "da_groupnorm_sync_bytes": (C.c_size_t, []),
     "da_groupnorm_nhwc_bf16": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _i, _vp, _vp]),

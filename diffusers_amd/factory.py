@@ -8,7 +8,8 @@ from .autoencoder_kl import AutoencoderKL
 from .autoencoder_kl_wan import AutoencoderKLWan
 from .autoencoder_tiny import AutoencoderTiny
 from .controlnet import ControlNetModel
-from .pipelines import (DDPMPipeline, FluxImg2ImgPipeline, FluxInpaintPipeline, FluxPipeline, StableDiffusionControlNetPipeline,
+from .motion_adapter import MotionAdapter, motion_adapter_param_shapes
+from .pipelines import (AnimateDiffPipeline, DDPMPipeline,FluxImg2ImgPipeline, FluxInpaintPipeline, FluxPipeline, StableDiffusionControlNetPipeline,
                         StableDiffusionImg2ImgPipeline, StableDiffusionInpaintPipeline, StableDiffusionInstructPix2PixPipeline,
                         StableDiffusionPipeline, StableDiffusionXLInstructPix2PixPipeline,
                         StableDiffusionXLControlNetPipeline, StableDiffusionXLImg2ImgPipeline, StableDiffusionXLInpaintPipeline,
@@ -86,6 +87,17 @@ def build_controlnet(unet_config: dict, seed: int = 3, device="cuda", init_devic
                     v.zero_()
     cn.load_state_dict(state_dict, device=device)
     return cn, state_dict
+
+
+def build_motion_adapter(unet_config: dict, seed: int = 4, device="cuda", init_device: Optional[str] = None, state_dict=None,
+                         **config_overrides):
+    """The MotionAdapter that goes with an SD 1.5 ``unet_config`` (its ``block_out_channels``) with seeded random weights.  The
+    reference zero-initialises every module's ``proj_out``, so a fresh adapter changes nothing; here it is random like every other
+    weight, so that the modules have an effect."""
+    ad = MotionAdapter(block_out_channels=tuple(unet_config["block_out_channels"]), **config_overrides)
+    if state_dict is None:
+        state_dict = dinit.random_state_dict(motion_adapter_param_shapes(ad.config), seed=seed, device=init_device or "cpu")
+    return MotionAdapter.from_state_dict(state_dict, device=device, **ad.config), state_dict
 
 
 def build_vae(cfg: dict, seed: int = 1, device="cuda", init_device: Optional[str] = None, state_dict=None,
@@ -216,6 +228,26 @@ def build_sd15_pipeline(device="cuda", tiny: bool = False, seed: int = 0, init_d
         return StableDiffusionInstructPix2PixPipeline(vae=vae, unet=unet, scheduler=sch)
     cls = StableDiffusionInpaintPipeline if inpaint else StableDiffusionImg2ImgPipeline if img2img else StableDiffusionPipeline
     return cls(vae=vae, unet=unet, scheduler=sch)
+
+
+def build_animatediff_pipeline(device="cuda", tiny: bool = False, seed: int = 0, init_device: Optional[str] = None,
+                               scheduler: Optional[str] = None, zero_proj_out: bool = False):
+    """SD 1.5 (or ``init.TINY_ANIMATEDIFF_UNET``) with a seeded MotionAdapter (seed + 4) in an AnimateDiffPipeline; the U-Net and
+    the VAE are those ``build_sd15_pipeline`` builds from the same seed.  ``zero_proj_out``: every motion module's ``proj_out`` at
+    zero, as the reference initialises it -- the modules then add nothing."""
+    ucfg = dinit.TINY_ANIMATEDIFF_UNET if tiny else dinit.SD15_UNET
+    idev = init_device or ("cpu" if tiny else str(device))
+    unet, _ = build_unet(ucfg, seed=seed, device=device, init_device=idev)
+    vae, _ = build_vae(dinit.TINY_VAE if tiny else dinit.SD_VAE, seed=seed + 1, device=device, init_device=idev)
+    mcfg = dict(block_out_channels=tuple(ucfg["block_out_channels"]), motion_layers_per_block=ucfg["layers_per_block"])
+    sd = dinit.random_state_dict(motion_adapter_param_shapes(dict(MotionAdapter.DEFAULTS, **mcfg)), seed=seed + 4, device=idev)
+    if zero_proj_out:
+        for k, v in sd.items():
+            if ".proj_out." in k:
+                v.zero_()
+    adapter = MotionAdapter.from_state_dict(sd, device=device, **mcfg)
+    sch = _scheduler_for(scheduler, lambda: DDIMScheduler(**SD15_SCHEDULER))
+    return AnimateDiffPipeline(vae=vae, unet=unet, scheduler=sch, motion_adapter=adapter)
 
 
 def build_flux_transformer(cfg: dict, seed: int = 5, device="cuda", init_device: Optional[str] = None, state_dict=None):

@@ -508,6 +508,9 @@ TINY_SD15_UNET = dict(sample_size=16, in_channels=4, out_channels=4, block_out_c
                       layers_per_block=1, cross_attention_dim=64, attention_head_dim=(1, 2),
                       down_block_types=("CrossAttnDownBlock2D", "DownBlock2D"),
                       up_block_types=("UpBlock2D", "CrossAttnUpBlock2D"))
+# AnimateDiff's tiny sibling: the motion modules' temporal attention has head sizes 40 / 80 / 160 over 8 heads, so the two levels are
+# SD 1.5's first two widths
+TINY_ANIMATEDIFF_UNET = dict(TINY_SD15_UNET, block_out_channels=(320, 640), attention_head_dim=8)
 SDXL_CONTROLNET = controlnet_config(SDXL_UNET)
 SD15_CONTROLNET = controlnet_config(SD15_UNET)
 # the tiny VAE has scale factor 2: one stride-2 stage in the conditioning embedding (32 x 32 control image, 16 x 16 latents)

@@ -700,6 +700,12 @@ def linear_small_m(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor
         raise ValueError("linear_small_m: weight must be contiguous [N][K]")
     if out is None:
         out = torch.empty((M, N), device=x.device, dtype=bf16)
+    if M > 8:
+        # the kernel keeps at most 8 rows in registers; a longer embedding batch (AnimateDiff: one row per frame) goes 8 rows a launch
+        for i in range(0, M, 8):
+            linear_small_m(x[i:i + 8], w, bias, act_in=act_in, act_out=act_out,
+                           residual=None if residual is None else residual[i:i + 8], out=out[i:i + 8])
+        return out
     L.check(L.load().da_linear_small_m_bf16(
         x.data_ptr(), w.data_ptr(), _ptr(bias), _ptr(residual), out.data_ptr(), M, N, K, _rows2d(x, "x"),
         _rows2d(out, "out"), _rows2d(residual, "residual") if residual is not None else 0, act_in, act_out, _stream()),
@@ -774,6 +780,39 @@ def attention(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, *, B: int, H: 
         p.bias_head_stride = bias.stride(1) if bias.shape[1] > 1 else 0
         p.bias_row_stride = bias.stride(2) if bias.shape[2] > 1 else 0   # one row for every query (key-padding mask)
     L.check(L.load().da_attention_bf16(C.byref(p), _stream()), "da_attention_bf16")
+    return out
+
+
+def temporal_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, *, B: int, F: int, HW: int, H: int, D: int,
+                       scale: Optional[float] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """da_attention_temporal_bf16 (csrc/attention_temporal.hip): self-attention over the frame axis of frame-major token matrices.
+    ``q`` / ``k`` / ``v``: [B*F*HW][H*D] bf16 views with a free row stride each (the column blocks of one fused Q|K|V projection
+    output), row (b*F + f)*HW + p = frame f of pixel p; V is token-major.  Returns ``out`` [B*F*HW][H*D], which may be a column block
+    of a wider buffer.  1 <= F <= 32 and D in {40, 80, 160} (anything else: DA_ERR_UNSUPPORTED from the library); row strides that are
+    no multiple of 8 elements and bases that are not 16-byte aligned are refused here by name.  The entry has no plan number: refused
+    while a launch plan is being recorded."""
+    if getattr(L._tls, "recorder", None) is not None:
+        raise RuntimeError("temporal_attention: not replayable by a launch plan (da_attention_temporal_bf16 has no DA_FN_* number); "
+                           "run a step with motion modules eagerly or as a captured HIP graph")
+    _req(q, "q"), _req(k, "k"), _req(v, "v")
+    rows, width = B * F * HW, H * D
+    if out is None:
+        out = torch.empty((rows, width), device=q.device, dtype=bf16)
+    else:
+        _req(out, "out")
+    p = L.AttentionTemporalParams()
+    for name, t in (("q", q), ("k", k), ("v", v), ("out", out)):
+        ld = _rows2d(t, name)
+        if tuple(t.shape) != (rows, width):
+            raise ValueError(f"temporal_attention: {name} must be [B*F*HW][H*D] = [{rows}][{width}], got {tuple(t.shape)}")
+        if ld % 8 or t.data_ptr() % 16:
+            raise ValueError(f"temporal_attention: {name} needs a row stride that is a multiple of 8 elements and a 16-byte aligned "
+                             f"base (16-byte loads and stores), got row stride {ld} and address % 16 = {t.data_ptr() % 16}")
+        setattr(p, name, t.data_ptr())
+        setattr(p, ("o" if name == "out" else name) + "_row_stride", ld)
+    p.B, p.F, p.HW, p.H, p.D = B, F, HW, H, D
+    p.scale = (D ** -0.5) if scale is None else scale
+    L.check(L.load().da_attention_temporal_bf16(C.byref(p), _stream()), "da_attention_temporal_bf16")
     return out
 
 

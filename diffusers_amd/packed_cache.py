@@ -29,6 +29,7 @@ FORMAT = "diffusers_amd.packed/1"
 _SHAPES: Dict[str, Callable] = {
     "UNet2DConditionModel": dinit.unet_param_shapes,
     "ControlNetModel": dinit.controlnet_param_shapes,
+    "MotionAdapter": lambda cfg: _motion_adapter_shapes(cfg),
     "AutoencoderKL": dinit.vae_decoder_param_shapes,
     "AutoencoderKLWan": dinit.wan_vae_decoder_param_shapes,
     "AutoencoderTiny": lambda cfg: dinit.tiny_vae_param_shapes(cfg, halves=("decoder",)),
@@ -41,6 +42,11 @@ _OPTIONAL_SHAPES: Dict[str, Tuple[str, Callable]] = {
     "AutoencoderKL": ("encoder.", dinit.vae_encoder_param_shapes),
     "AutoencoderTiny": ("encoder.", lambda cfg: dinit.tiny_vae_param_shapes(cfg, halves=("encoder",))),
 }
+
+
+def _motion_adapter_shapes(cfg):
+    from .motion_adapter import motion_adapter_param_shapes      # (that module imports the loading side, which imports this one)
+    return motion_adapter_param_shapes(cfg)
 
 
 def _walk(obj, path: str, visit, seen: set) -> None:
@@ -58,7 +64,7 @@ def _walk(obj, path: str, visit, seen: set) -> None:
         items = list(enumerate(obj))
         get = lambda k: obj[k]                      # noqa: E731
     elif hasattr(obj, "__dict__"):
-        items = [(k, v) for k, v in vars(obj).items() if k not in ("config", "_rope_cache", "_graph", "_static", "_cond_cache", "_source", "_lora")]
+        items = [(k, v) for k, v in vars(obj).items() if k not in ("config", "_rope_cache", "_rowvec", "_graph", "_static", "_cond_cache", "_source", "_lora")]
         get = lambda k: getattr(obj, k)             # noqa: E731
     else:
         return

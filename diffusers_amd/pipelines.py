@@ -819,6 +819,105 @@ class StableDiffusionPipeline(_LatentDiffusionBase):
 
 
 # ----------------------------------------------------------------------------------------------------------------------
+# AnimateDiff text-to-video (pipelines/animatediff/pipeline_animatediff.py)
+# ----------------------------------------------------------------------------------------------------------------------
+class AnimateDiffPipeline(StableDiffusionPipeline):
+    """SD 1.5 text-to-video: the SD pipeline's call body and captured-step loop on a ``UNetMotionModel``.  The loop's latents are
+    the video with its frames folded into the batch, [B F][4][h][w] (what the U-Net's conv_in reads and every scheduler, being
+    elementwise, steps as a batch; a step callback sees them so); they are drawn as the reference's [B][4][F][h][w] from the
+    ``generator``, taken and -- ``output_type="latent"`` -- returned in that shape.  ``num_frames`` is part of the graph key.  The
+    VAE decodes ``decode_chunk_size`` frames at a time; ``"pt"`` / ``"np"`` results are [B][F]...  Not built, refused by name: launch plans, more
+    than 32 frames (context windows, FreeNoise), video-to-video, SparseCtrl / ControlNet, FreeU, IP-Adapter, motion LoRA, SDXL."""
+    _UNBUILT = {"video": "video-to-video", "conditioning_frames": "SparseCtrl / ControlNet with AnimateDiff",
+                "controlnet_conditioning_scale": "SparseCtrl / ControlNet with AnimateDiff", "ip_adapter_image": "IP-Adapter with AnimateDiff",
+                "ip_adapter_image_embeds": "IP-Adapter with AnimateDiff", "context_length": "context windows", "strength": "video-to-video"}
+
+    def __init__(self, vae, unet, scheduler, motion_adapter=None, text_encoder=None, tokenizer=None, feature_extractor=None,
+                 image_encoder=None, controlnet=None):
+        from .motion_adapter import UNetMotionModel
+        if controlnet is not None or image_encoder is not None:
+            raise NotImplementedError("AnimateDiffPipeline: SparseCtrl / ControlNet and IP-Adapter with AnimateDiff are not built")
+        if not isinstance(unet, UNetMotionModel):
+            unet = UNetMotionModel.from_unet2d(unet, motion_adapter)       # (refuses an SDXL U-Net by name)
+        super().__init__(vae, unet, scheduler, text_encoder, tokenizer)
+        self.motion_adapter, self._num_frames, self._decode_chunk = unet.motion_adapter, 16, 16
+
+    def enable_freeu(self, *args, **kwargs):
+        raise NotImplementedError("FreeU with AnimateDiff is not built")
+
+    def enable_free_noise(self, *args, **kwargs):
+        raise NotImplementedError("FreeNoise (and context windows: more than 32 frames) is not built")
+
+    def load_lora_weights(self, *args, **kwargs):
+        raise NotImplementedError("motion LoRA is not built")
+
+    def _arm(self, guidance_scale, guidance_rescale, callback_on_step_end, callback_on_step_end_tensor_inputs, use_graph=True) -> bool:
+        if use_graph == "plan":
+            raise NotImplementedError('use_graph="plan" with AnimateDiff: da_attention_temporal_bf16 has no launch-plan number; call '
+                                      "with use_graph=True (captured HIP graph) or False")
+        return super()._arm(guidance_scale, guidance_rescale, callback_on_step_end, callback_on_step_end_tensor_inputs, use_graph)
+
+    def _noise_latents(self, latents, generator, batch: int, height: int, width: int):
+        F = self._num_frames
+        if latents is None:
+            shape = (batch, self._num_channels_latents(), F, height // self.vae_scale_factor, width // self.vae_scale_factor)
+            gdev = generator.device if generator is not None else torch.device("cpu")
+            latents = torch.randn(shape, generator=generator, device=gdev, dtype=bf16)
+        if latents.dim() != 5 or latents.shape[2] != F:
+            raise ValueError(f"`latents` must be [batch][channels][num_frames={F}][h][w], got {tuple(latents.shape)}")
+        _check_latents_batch(latents, batch)
+        folded = latents.to(device=self.device, dtype=bf16).permute(0, 2, 1, 3, 4).reshape(batch * F, latents.shape[1], *latents.shape[3:])
+        return ops.mul_scalar(folded.contiguous(), float(self.scheduler.init_noise_sigma))
+
+    def _unet_conditioning(self, pe, added):
+        tc = self._timestep_cond(pe.shape[0])
+        return self.unet.precompute_conditioning(pe, added, num_frames=self._num_frames, **({} if tc is None else {"timestep_cond": tc}))
+
+    def _predict_noise(self, latents, cond, do_cfg):
+        sch = self.scheduler
+        return self.unet(self._model_input(latents, do_cfg), None, None, conditioning=cond, sampler_table=sch.device_table,
+                         step_idx=sch.device_step, num_frames=self._num_frames, return_dict=False)[0]
+
+    def _make_graph_key(self, latents, cond, guidance_scale, do_cfg):
+        return super()._make_graph_key(latents, cond, guidance_scale, do_cfg) + (self._num_frames,)
+
+    def _decode(self, latents, output_type):
+        F = self._num_frames
+        B = latents.shape[0] // F
+        if output_type == "latent":
+            return latents.view(B, F, *latents.shape[1:]).permute(0, 2, 1, 3, 4).contiguous()
+        if output_type not in ("pt", "np"):
+            raise ValueError(f"output_type={output_type!r}: AnimateDiffPipeline returns 'pt', 'np' ([batch][frames]...) or 'latent'")
+        n = self._decode_chunk
+        parts = [super(AnimateDiffPipeline, self)._decode(latents[i:i + n], output_type) for i in range(0, latents.shape[0], n)]
+        frames = torch.cat(parts) if output_type == "pt" else np.concatenate(parts)
+        return frames.reshape(B, F, *frames.shape[1:])
+
+    @torch.no_grad()
+    def __call__(self, prompt=None, num_frames: int = 16, height: Optional[int] = None, width: Optional[int] = None,
+                 num_inference_steps: int = 50, guidance_scale: float = 7.5, negative_prompt=None, num_videos_per_prompt: int = 1,
+                 eta: float = 0.0, generator=None, latents: Optional[torch.Tensor] = None, prompt_embeds=None,
+                 negative_prompt_embeds=None, output_type: str = "pt", return_dict: bool = True, callback_on_step_end=None,
+                 callback_on_step_end_tensor_inputs=None, clip_skip=None, decode_chunk_size: int = 16, use_graph: bool = True,
+                 guidance_rescale: float = 0.0, **unbuilt):
+        for k, v in unbuilt.items():
+            if k not in self._UNBUILT:
+                raise TypeError(f"AnimateDiffPipeline.__call__() got an unexpected keyword argument {k!r}")
+            if v is not None:
+                raise NotImplementedError(f"AnimateDiffPipeline: `{k}` ({self._UNBUILT[k]}) is not built")
+        if isinstance(num_frames, bool) or not isinstance(num_frames, int) or not 1 <= num_frames <= 32:
+            raise NotImplementedError(f"num_frames must be an integer in 1 .. 32: longer videos need context windows / FreeNoise, which "
+                                      f"are not built (got {num_frames!r})")
+        if decode_chunk_size < 1:
+            raise ValueError("decode_chunk_size must be >= 1")
+        self._num_frames, self._decode_chunk = num_frames, int(decode_chunk_size)
+        return super().__call__(prompt, height, width, num_inference_steps, guidance_scale, eta, latents, prompt_embeds,
+                                negative_prompt_embeds, output_type, return_dict, generator, use_graph, negative_prompt,
+                                num_videos_per_prompt, clip_skip, guidance_rescale, callback_on_step_end,
+                                callback_on_step_end_tensor_inputs)
+
+
+# ----------------------------------------------------------------------------------------------------------------------
 # image-to-image (pipeline_stable_diffusion_xl_img2img.py, pipeline_stable_diffusion_img2img.py)
 # ----------------------------------------------------------------------------------------------------------------------
 def get_timesteps(scheduler, num_inference_steps: int, strength: float, denoising_start: Optional[float] = None):

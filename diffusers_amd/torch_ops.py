@@ -19,6 +19,7 @@ name ends in ``_``).  Registration happens on import of this module (``import di
     x_next, m1 = torch.ops.mi355x.dpmpp_2m_step(eps, x, m1, table, step_idx, begin_idx, True, 5.0, 0)
     fin, moments = torch.ops.mi355x.vae_moments_tile_blend(raw, sB, sC, sP, wq, bq, up, left, moments, 4, h, w, E, y0, x0, kh, kw)
     hidden, skip = torch.ops.mi355x.freeu(hidden, skip, 0.9, 1.3)  # apply_freeu, channels-last
+    o = torch.ops.mi355x.temporal_attn(q, k, v, 16, 8, None)      # attention over the frame axis of [B, F, HW, C] tokens, in place
     small = torch.ops.mi355x.resample_u8(img_u8_nhwc, 768, 1024, "lanczos")   # PIL.Image.resize, to the bit
     small = torch.ops.mi355x.gather_resize(img, 768, 1024, True)              # F.interpolate (nearest), NCHW
 """
@@ -177,6 +178,34 @@ def _(hidden, skip, s, b):
     return torch.empty_like(hidden), torch.empty_like(skip)
 
 
+@torch.library.custom_op(f"{NAMESPACE}::temporal_attn", mutates_args=(), device_types="cuda")
+def temporal_attn(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, num_frames: int, heads: int, scale: Optional[float]) -> torch.Tensor:
+    """Self-attention over the frame axis (da_attention_temporal_bf16): ``q`` / ``k`` / ``v`` are [B*F][HW][C] bf16, frame-major
+    (row (b*F + f)*HW + p), last dim contiguous and the first two dims mergeable (stride(0) == HW * stride(1)) -- the column blocks of
+    one fused projection output are taken as they are; nothing is copied.  Every (pixel, head) attends over its ``num_frames`` frames.
+    A 2-D token matrix does not say what HW is and is refused; so is an operand that would need a copy.  Returns a contiguous tensor
+    of q's shape."""
+    if q.dim() != 3 or q.shape[0] % num_frames or q.shape[2] % heads:
+        raise ValueError(f"temporal_attn: q must be [B*{num_frames}][HW][{heads}*D] (3-D: a 2-D token matrix does not carry HW), got "
+                         f"{tuple(q.shape)}")
+    BF, HW, C_ = q.shape
+
+    def flat(t, name):
+        if tuple(t.shape) != (BF, HW, C_) or t.stride(2) != 1 or (HW > 1 and BF > 1 and t.stride(0) != HW * t.stride(1)):
+            raise ValueError(f"temporal_attn: {name} must be a [{BF}][{HW}][{C_}] view with a contiguous last dim and stride(0) == HW * "
+                             f"stride(1) (it is not copied), got shape {tuple(t.shape)} strides {t.stride()}")
+        ld = t.stride(1) if HW > 1 else (t.stride(0) if BF > 1 else C_)
+        return t.as_strided((BF * HW, C_), (ld, 1), t.storage_offset())
+    out = ops.temporal_attention(flat(q, "q"), flat(k, "k"), flat(v, "v"), B=BF // num_frames, F=num_frames, HW=HW, H=heads,
+                                 D=C_ // heads, scale=scale)
+    return out.view(q.shape)
+
+
+@temporal_attn.register_fake
+def _(q, k, v, num_frames, heads, scale):
+    return q.new_empty(q.shape)
+
+
 @torch.library.custom_op(f"{NAMESPACE}::resample_u8", mutates_args=(), device_types="cuda")
 def resample_u8(src: torch.Tensor, height: int, width: int, resample: str) -> torch.Tensor:
     """PIL.Image.resize((width, height), resample) of packed uint8 [B][H][W][C] images, C = 1 or 3, to the bit (da_resample_u8);
@@ -202,4 +231,4 @@ def _(src, height, width, nchw):
 
 
 OPS = ("gemm", "conv2d_nhwc", "flash_attn", "groupnorm", "layernorm", "euler_step", "dpmpp_2m_step", "euler_ancestral_step",
-       "vae_moments_tile_blend", "freeu", "resample_u8", "gather_resize")
+       "vae_moments_tile_blend", "freeu", "temporal_attn", "resample_u8", "gather_resize")

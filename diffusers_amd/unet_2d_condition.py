@@ -133,6 +133,10 @@ class UNet2DConditionModel(PretrainedMixin):
         """What ``forward`` bakes into a captured step by value, besides the weights: FreeU's four floats while a stage is on."""
         return () if self._freeu_stage(0) is None else ("freeu",) + tuple(float(v) for v in self._freeu)
 
+    # AnimateDiff: ``(MotionAdapter, num_frames)`` while a ``motion_adapter.UNetMotionModel`` forward runs -- a motion module after
+    # every (resnet, attention) pair of the down and up blocks and after the mid block's attention; None for the plain U-Net
+    _motion = None
+
     # ------------------------------------------------------------------------------------------------------------
     # weights
     # ------------------------------------------------------------------------------------------------------------
@@ -438,7 +442,8 @@ class UNet2DConditionModel(PretrainedMixin):
             x = ops.conv_thin_in(sample.contiguous(), self.conv_in_w, self.conv_in_b, ksize=3, in_nchw=True)
 
         # 3. down
-        x, skips, ki = walk_down(self.down, x, emb, kvs)
+        motion = self._motion
+        x, skips, ki = walk_down(self.down, x, emb, kvs, motion=motion)
 
         if down_block_additional_residuals is not None:
             # ControlNet (:1191-1200): one residual per skip connection, NCHW like every reference activation; the sum is a
@@ -449,7 +454,7 @@ class UNet2DConditionModel(PretrainedMixin):
             skips = [s_ + self._nhwc(r, s_) for s_, r in zip(skips, down_block_additional_residuals)]
 
         # 4. mid
-        x, ki = walk_mid(self.mid, x, emb, kvs, ki)
+        x, ki = walk_mid(self.mid, x, emb, kvs, ki, motion=motion)
         if mid_block_additional_residual is not None:
             x = x + self._nhwc(mid_block_additional_residual, x)             # :1220-1222
         if controlnet_handoff is not None:
@@ -470,6 +475,8 @@ class UNet2DConditionModel(PretrainedMixin):
                 if st["attns"]:
                     x = st["attns"][j](x, kvs[ki])
                     ki += 1
+                if motion is not None:
+                    x = motion[0].up[i][j](x, motion[1])
             if st["up"] is not None:
                 x = st["up"](x)
 

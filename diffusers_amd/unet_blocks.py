@@ -48,16 +48,20 @@ def build_mid_block(w: Weights, c) -> dict:
     }
 
 
-def walk_down(down: List[dict], x, emb, kvs, ki: int = 0) -> Tuple[object, list, int]:
+def walk_down(down: List[dict], x, emb, kvs, ki: int = 0, motion=None) -> Tuple[object, list, int]:
     """The down blocks on ``x`` (channels-last): returns the output, the skip list (``x`` itself first, then one entry per
-    resnet / attention pair and per downsampler) and the index of the next unused cross-attention K / V^T of ``kvs``."""
+    resnet / attention pair and per downsampler) and the index of the next unused cross-attention K / V^T of ``kvs``.
+    ``motion = (MotionAdapter, num_frames)``: AnimateDiff (unet_motion_model.py DownBlockMotion / CrossAttnDownBlockMotion) -- a
+    motion module after every (resnet, attention) pair, in front of the skip."""
     skips = [x]
-    for st in down:
+    for i, st in enumerate(down):
         for j, rn in enumerate(st["resnets"]):
             x = rn(x, emb)
             if st["attns"]:
                 x = st["attns"][j](x, kvs[ki])
                 ki += 1
+            if motion is not None:
+                x = motion[0].down[i][j](x, motion[1])
             skips.append(x)
         if st["down"] is not None:
             x = st["down"](x)
@@ -65,8 +69,12 @@ def walk_down(down: List[dict], x, emb, kvs, ki: int = 0) -> Tuple[object, list,
     return x, skips, ki
 
 
-def walk_mid(mid: dict, x, emb, kvs, ki: int) -> Tuple[object, int]:
+def walk_mid(mid: dict, x, emb, kvs, ki: int, motion=None) -> Tuple[object, int]:
+    """resnet, (attention, [UNetMidBlockCrossAttnMotion: motion module,] resnet)."""
     x = mid["resnets"][0](x, emb)
     x = mid["attns"][0](x, kvs[ki])
+    if motion is not None:
+        for m in motion[0].mid:
+            x = m(x, motion[1])
     x = mid["resnets"][1](x, emb)
     return x, ki + 1

@@ -372,6 +372,31 @@ long long da_attention_split_plan(const da_attention_params* p, int* full_blocks
 int da_attention_bf16(const da_attention_params* p, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------------
+ * Temporal self-attention (attention_temporal.hip): attention over the FRAME axis of a frame-major channels-last token matrix, the
+ * two attentions of an AnimateDiff motion module (unet_motion_model.py AnimateDiffTransformer3D; attention.py BasicTransformerBlock
+ * with double_self_attention), without the reference's permute to (B HW, F, C) and back.
+ *   element (b, f, p, h, d) of q / k / v / out is at  ptr + ((b*F + f)*HW + p)*row_stride + h*D + d   (its own row stride each)
+ *   q, k, v may be column blocks of one fused projection output, out a column block of a wider buffer.  V is read token-major: no
+ *   transposed operand, no key padding.  out[b, f, p, h, :] = softmax_f'(scale * q[b, f, p, h] . k[b, f', p, h]) v[b, f', p, h, :].
+ *   Supported: 1 <= F <= 32, D in {40, 80, 160}, any H, HW, B >= 1 (B*F*HW < 2^31); strides in elements, multiples of 8 and
+ *   >= H*D, bases 16-byte aligned (16-byte loads and stores).  Anything else: DA_ERR_UNSUPPORTED and no launch; a NULL pointer:
+ *   DA_ERR_INVALID.  Bytes outside columns [0, H*D) of an out row are not written; nothing outside the B*F*HW x H*D blocks is read.
+ *   Softmax in fp32; P is rounded to bf16 once and the row sum is taken from the rounded P.  No workspace; the result depends on the
+ *   inputs alone.  The entry has no DA_FN_* plan number (DA_ABI_VERSION stays 9): a step with motion modules runs eagerly or as a
+ *   captured HIP graph, not as a launch plan.
+ * ------------------------------------------------------------------------------------------------------------------ */
+typedef struct da_attention_temporal_params {
+  const void* q;
+  const void* k;
+  const void* v;
+  void* out;
+  int B, F, HW, H, D;
+  int q_row_stride, k_row_stride, v_row_stride, o_row_stride;
+  float scale;
+} da_attention_temporal_params;
+int da_attention_temporal_bf16(const da_attention_temporal_params* p, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------------
  * Normalisation (norm.hip)
  *   da_groupnorm_nhwc_bf16   nn.GroupNorm(G, C, eps) [+ SiLU when act == DA_ACT_SILU] on channels-last [B][HW][C].
  *                            Replaces resnet.py:326-327,:350,:362, transformer_2d.py:466, unet_2d_condition.py:1228-1229,
