@@ -90,6 +90,22 @@ class AttentionTemporalParams(C.Structure):
     ]
 
 
+IP_MAX_ADAPTERS = 4                   # DA_IP_MAX_ADAPTERS
+
+
+class AttentionIPParams(C.Structure):
+    _fields_ = [
+        ("q", C.c_void_p), ("out", C.c_void_p),
+        ("k", C.c_void_p * IP_MAX_ADAPTERS), ("v", C.c_void_p * IP_MAX_ADAPTERS),
+        ("n", C.c_int * IP_MAX_ADAPTERS), ("n_alloc", C.c_int * IP_MAX_ADAPTERS),
+        ("k_row_stride", C.c_int * IP_MAX_ADAPTERS), ("v_row_stride", C.c_int * IP_MAX_ADAPTERS),
+        ("scale", C.c_float * IP_MAX_ADAPTERS),
+        ("A", C.c_int), ("B", C.c_int), ("H", C.c_int), ("D", C.c_int), ("Sq", C.c_int),
+        ("q_row_stride", C.c_int), ("o_row_stride", C.c_int),
+        ("sm_scale", C.c_float),
+    ]
+
+
 # ---- launch plans (include/diffusers_amd.h "launch plans"; csrc/plan.hip) ----
 PLAN_MAX_ARGS = 16
 FN_IDS = {name: i + 1 for i, name in enumerate((
@@ -120,6 +136,8 @@ PASS_THROUGH = {
                           "to a later ABI bump; ops.freeu refuses under a recording",
     "da_attention_temporal_bf16": "part of a U-Net step with AnimateDiff motion modules, which runs eagerly or as a captured HIP graph: "
                                   "a plan number belongs to a later ABI bump; ops.temporal_attention refuses under a recording",
+    "da_attention_ip_bf16": "part of a U-Net step with an IP-Adapter loaded, which runs eagerly or as a captured HIP graph: a plan number "
+                            "belongs to a later ABI bump; ops.ip_attention_accumulate refuses under a recording",
     "da_resample_u8": "resizes an input image once per call, in front of the encoder and outside any recorded step; ops.resample_u8 "
                       "refuses under a recording",
     "da_gather_resize": "resizes an input tensor once per call, in front of the encoder and outside any recorded step; "
@@ -151,6 +169,7 @@ SIGNATURES = {
     "da_attention_bf16": (_i, [C.POINTER(AttentionParams), _vp]),
     "da_attention_split_plan": (_ll, [C.POINTER(AttentionParams), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "da_attention_temporal_bf16": (_i, [C.POINTER(AttentionTemporalParams), _vp]),
+    "da_attention_ip_bf16": (_i, [C.POINTER(AttentionIPParams), _vp]),
     "da_groupnorm_workspace_bytes": (C.c_size_t, [_i, _i, _i, _i]),
     "da_groupnorm_sync_bytes": (C.c_size_t, []),
     "da_groupnorm_nhwc_bf16": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _i, _vp, _vp]),

@@ -100,6 +100,24 @@ def build_motion_adapter(unet_config: dict, seed: int = 4, device="cuda", init_d
     return MotionAdapter.from_state_dict(state_dict, device=device, **ad.config), state_dict
 
 
+def build_ip_adapter_state_dict(unet_config: dict, num_tokens: int = 4, seed: int = 6, image_embed_dim: int = 1024,
+                                init_device: str = "cpu"):
+    """A seeded plain IP-Adapter checkpoint for ``unet_config`` in the reference's ``{"image_proj": ..., "ip_adapter": ...}`` form
+    (``to_k_ip`` / ``to_v_ip`` of every cross-attention, numbered as loaders/unet.py numbers them)."""
+    from .ip_adapter import ip_adapter_param_shapes, nest
+    return nest(dinit.random_state_dict(ip_adapter_param_shapes(unet_config, num_tokens, image_embed_dim), seed=seed, device=init_device))
+
+
+def _with_ip_adapter(pipe, ip_adapter, unet_config, seed: int):
+    """The factories' ``ip_adapter=`` switch: False, True (one adapter of 4 tokens) or a list of token counts, one adapter each;
+    CLIP image embeddings are 64 wide for the tiny U-Nets (cross_attention_dim 64), 1024 otherwise."""
+    if ip_adapter:
+        tokens = [4] if ip_adapter is True else list(ip_adapter)
+        emb = 64 if unet_config["cross_attention_dim"] <= 64 else 1024
+        pipe.load_ip_adapter([build_ip_adapter_state_dict(unet_config, t, seed + 6 + i, emb) for i, t in enumerate(tokens)])
+    return pipe
+
+
 def build_vae(cfg: dict, seed: int = 1, device="cuda", init_device: Optional[str] = None, state_dict=None,
               with_encoder: bool = False):
     """``with_encoder``: the encoder half (+ quant_conv) as well, for ``encode`` (random_state_dict seeds per key: the decoder
@@ -168,7 +186,7 @@ def _controlnet_for(ucfg: dict, tiny: bool, seed: int, device, idev, controlnet)
 def build_sdxl_pipeline(device="cuda", tiny: bool = False, seed: int = 0, init_device: Optional[str] = None,
                         with_encoder: bool = False, img2img: bool = False, inpaint: bool = False, unet_in_channels: int = 4,
                         controlnet=False, scheduler: Optional[str] = None, time_cond_proj_dim: Optional[int] = None,
-                        tiny_vae: bool = False, pix2pix: bool = False):
+                        tiny_vae: bool = False, pix2pix: bool = False, ip_adapter=False):
     """SDXL-base (BASELINE config 3) or its tiny sibling.  Full size: weights are generated on ``init_device``
     (default: the HIP device, ~2.6 B parameters in seconds) and freed after packing.  ``with_encoder``: the VAE's encoder as
     well; ``img2img``: the same components in a StableDiffusionXLImg2ImgPipeline, ``inpaint``: in a
@@ -193,18 +211,19 @@ def build_sdxl_pipeline(device="cuda", tiny: bool = False, seed: int = 0, init_d
     if controlnet:
         if img2img or inpaint:
             raise ValueError("controlnet= builds the text-to-image ControlNet pipeline (no ControlNet img2img / inpainting pipeline)")
-        return StableDiffusionXLControlNetPipeline(vae=vae, unet=unet, scheduler=sch,
-                                                   controlnet=_controlnet_for(ucfg, tiny, seed, device, idev, controlnet))
+        return _with_ip_adapter(StableDiffusionXLControlNetPipeline(vae=vae, unet=unet, scheduler=sch,
+                                                                    controlnet=_controlnet_for(ucfg, tiny, seed, device, idev, controlnet)),
+                                ip_adapter, ucfg, seed)
     if pix2pix:
         return StableDiffusionXLInstructPix2PixPipeline(vae=vae, unet=unet, scheduler=sch)
     cls = StableDiffusionXLInpaintPipeline if inpaint else StableDiffusionXLImg2ImgPipeline if img2img else StableDiffusionXLPipeline
-    return cls(vae=vae, unet=unet, scheduler=sch)
+    return _with_ip_adapter(cls(vae=vae, unet=unet, scheduler=sch), ip_adapter, ucfg, seed)
 
 
 def build_sd15_pipeline(device="cuda", tiny: bool = False, seed: int = 0, init_device: Optional[str] = None,
                         with_encoder: bool = False, img2img: bool = False, inpaint: bool = False, unet_in_channels: int = 4,
                         controlnet=False, scheduler: Optional[str] = None, time_cond_proj_dim: Optional[int] = None,
-                        tiny_vae: bool = False, pix2pix: bool = False):
+                        tiny_vae: bool = False, pix2pix: bool = False, ip_adapter=False):
     """SD1.5 or its tiny sibling, as ``build_sdxl_pipeline`` (DDIM by default; ``tiny_vae``: TAESD; ``pix2pix``: a
     StableDiffusionInstructPix2PixPipeline)."""
     ucfg = dinit.TINY_SD15_UNET if tiny else dinit.SD15_UNET
@@ -222,12 +241,13 @@ def build_sd15_pipeline(device="cuda", tiny: bool = False, seed: int = 0, init_d
     if controlnet:
         if img2img or inpaint:
             raise ValueError("controlnet= builds the text-to-image ControlNet pipeline (no ControlNet img2img / inpainting pipeline)")
-        return StableDiffusionControlNetPipeline(vae=vae, unet=unet, scheduler=sch,
-                                                 controlnet=_controlnet_for(ucfg, tiny, seed, device, idev, controlnet))
+        return _with_ip_adapter(StableDiffusionControlNetPipeline(vae=vae, unet=unet, scheduler=sch,
+                                                                  controlnet=_controlnet_for(ucfg, tiny, seed, device, idev, controlnet)),
+                                ip_adapter, ucfg, seed)
     if pix2pix:
         return StableDiffusionInstructPix2PixPipeline(vae=vae, unet=unet, scheduler=sch)
     cls = StableDiffusionInpaintPipeline if inpaint else StableDiffusionImg2ImgPipeline if img2img else StableDiffusionPipeline
-    return cls(vae=vae, unet=unet, scheduler=sch)
+    return _with_ip_adapter(cls(vae=vae, unet=unet, scheduler=sch), ip_adapter, ucfg, seed)
 
 
 def build_animatediff_pipeline(device="cuda", tiny: bool = False, seed: int = 0, init_device: Optional[str] = None,

@@ -220,12 +220,13 @@ class Upsample2D:
 class CrossKV:
     """Step-invariant cross-attention keys / transposed values of one attention layer (hoisted out of the loop)."""
 
-    __slots__ = ("k", "vt", "skv", "skv_alloc", "batch", "bias", "buf")
+    __slots__ = ("k", "vt", "skv", "skv_alloc", "batch", "bias", "buf", "ip")
 
     def __init__(self, k, vt, skv, skv_alloc, batch, bias=None, buf=None):
         self.k, self.vt, self.skv, self.skv_alloc, self.batch = k, vt, skv, skv_alloc, batch
         self.buf = buf     # the ONE allocation that holds k then vt (a prefetch hint covers both), or None
         self.bias = bias   # [batch][1][1][ceil64(skv)] additive key mask (encoder_attention_mask), or None
+        self.ip = None     # IP-Adapter: [(k, v, N, N_alloc)] per adapter (Attention.precompute_ip_kv), or None
 
 
 KERNEL_HEAD_DIMS = (64, 96, 128, 160)  # head sizes of the flash kernel (csrc/attention.hip)
@@ -297,6 +298,45 @@ class Attention:
         vt = ops.linear(self.wv, ehs_pad, out=buf[rows * inner:].view(inner, rows))  # [inner][batch*skv_alloc] = V^T
         return CrossKV(k, vt, skv, skv_alloc, batch, bias, buf)
 
+    # ---- IP-Adapter (attention_processor.py IPAdapterAttnProcessor2_0): the decoupled image branch of a cross-attention ----
+    ip_w = None        # per adapter: to_k_ip | to_v_ip stacked [2*inner][cross_dim], head rows padded like to_k / to_v
+    ip_scales = ()     # per adapter: the processor's `scale`; read by value in __call__ (part of the pipelines' graph keys)
+
+    def attach_ip(self, weights) -> None:
+        """``weights``: one ``(to_k_ip.weight, to_v_ip.weight)`` per adapter, [heads*head_dim][cross_dim] each.  Packs each pair as ONE
+        stacked weight so that an adapter's keys and values come from one GEMM; scales start at 1.0.  ``attach_ip(None)`` detaches."""
+        if not self.cross:
+            raise ValueError("attach_ip: IP-Adapter weights belong to cross-attention layers")
+        if not weights:
+            self.ip_w, self.ip_scales = None, ()
+            return
+        if len(weights) > L.IP_MAX_ADAPTERS:
+            raise NotImplementedError(f"more than {L.IP_MAX_ADAPTERS} IP-Adapters on one layer (got {len(weights)})")
+        d, dp, dev = self.head_dim, self.kdim, self.wq.device
+        packed = []
+        for wk, wv in weights:
+            if wk.shape != wv.shape or wk.shape[0] != self.heads * d or wk.shape[1] != self.wk.shape[1]:
+                raise ValueError(f"attach_ip: to_k_ip / to_v_ip must be [{self.heads * d}][{self.wk.shape[1]}], got "
+                                 f"{tuple(wk.shape)} / {tuple(wv.shape)}")
+            packed.append(torch.cat([pad_head_rows(t.to(device=dev, dtype=bf16), self.heads, d, dp) for t in (wk, wv)], dim=0).contiguous())
+        self.ip_w, self.ip_scales = packed, (1.0,) * len(packed)
+
+    def precompute_ip_kv(self, tokens, batch: int):
+        """Step-invariant image keys / values, next to :meth:`precompute_kv`: ``tokens`` is one ``(padded [batch*N_alloc][cross_dim],
+        N, N_alloc)`` per adapter (pad_encoder_states of the projected image embeddings); one ``ops.linear`` per adapter gives
+        [batch*N_alloc][2*inner], whose column halves are K and (token-major) V.  Returns ``[(k, v, N, N_alloc)]`` for ``CrossKV.ip``.
+        Every call allocates: a captured step holds the buffers of the call it was captured in by address, and a later call's are
+        copied into those (the pipelines' ``_refresh_static``), as for ``CrossKV.k`` / ``vt``."""
+        if self.ip_w is None or len(tokens) != len(self.ip_w):
+            raise ValueError(f"precompute_ip_kv: {len(tokens)} image prompts for {0 if self.ip_w is None else len(self.ip_w)} adapters")
+        out = []
+        for (t, n, n_alloc), w in zip(tokens, self.ip_w):
+            if n > 32:
+                raise NotImplementedError(f"IP-Adapter with {n} image tokens: the image-prompt kernel takes at most 32")
+            kv = ops.linear(t, w)
+            out.append((kv[:, :self.inner], kv[:, self.inner:], n, n_alloc))
+        return out
+
     def fold_norm(self, norm: "LayerNorm") -> None:
         """Cross-attention only: fold the LayerNorm in front of the block (attention.py:1030) into to_q."""
         self.wq_ln, self.fold = ops.fold_layernorm(self.wq, norm.weight, norm.bias, norm.eps)
@@ -315,7 +355,9 @@ class Attention:
         cross-attention whose norm was folded into to_q; returns to_out(attn) + residual (``stats_out``: the row statistics
         of that result, for the next folded norm)."""
         Hh, D = self.heads, self.kdim
-        if self.cross and ops.XATTN and kv.bias is None and ops.xattn_eligible(x.shape[0], self.inner, seq, D, kv.skv_alloc) \
+        # IP-Adapter: image keys / values are present and some scale is non-zero -- q must exist, so the fused launch is not taken
+        ip = [(k, v, n, na, s) for (k, v, n, na), s in zip(kv.ip, self.ip_scales)] if self.cross and kv.ip and any(self.ip_scales) else None
+        if ip is None and self.cross and ops.XATTN and kv.bias is None and ops.xattn_eligible(x.shape[0], self.inner, seq, D, kv.skv_alloc) \
                 and kv.k.shape[1] == self.inner:
             # to_q and the 77-key attention in ONE launch (da_gemm_params.xa_*): the wave that finishes 32 queries x one head of q
             # runs that head's softmax(q k^T) v on its own registers -- no attention launch, no q round trip
@@ -328,6 +370,9 @@ class Attention:
                               q_row_stride=self.inner, k_row_stride=self.inner,
                               q_batch_stride=seq * self.inner, k_batch_stride=kv.skv_alloc * self.inner,
                               vt_ld=batch * kv.skv_alloc, vt_batch_stride=kv.skv_alloc, scale=self.scale, bias=kv.bias)
+            if ip is not None:
+                # hidden_states + scale * ip_hidden_states of every adapter, in place on the text attention's output, one launch
+                ops.ip_attention_accumulate(o, q, ip, B=batch, H=Hh, D=D, Sq=seq, scale=self.scale)
         else:
             if stats is not None:
                 # norm1 folded: x is the UN-normalised residual stream, `stats` its row statistics (written by the GEMM that

@@ -212,6 +212,9 @@ class UNetMotionModel(UNet2DConditionModel):
     def graph_token(self) -> tuple:
         return ("motion", self.motion_adapter._weights_generation)
 
+    def _load_ip_adapter_weights(self, state_dicts):
+        raise NotImplementedError("IP-Adapter with AnimateDiff is not built (image keys / values are made per sample, not per frame)")
+
     def precompute_conditioning(self, encoder_hidden_states, added_cond_kwargs=None, encoder_attention_mask=None, timestep_cond=None,
                                 num_frames=None):
         """As the U-Net's, for per-SAMPLE inputs: each row is repeated ``num_frames`` times (the frames of a sample adjacent)."""

@@ -816,6 +816,46 @@ def temporal_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, *, B: 
     return out
 
 
+def ip_attention_accumulate(out: torch.Tensor, q: torch.Tensor, adapters, *, B: int, H: int, D: int, Sq: int,
+                            scale: Optional[float] = None) -> torch.Tensor:
+    """da_attention_ip_bf16 (csrc/attention_ip.hip): the image branch of IP-Adapter's decoupled cross-attention, added in place onto
+    ``out`` (what the text cross-attention wrote): ``out += sum_a scale_a * softmax(scale * q k_a^T) v_a``, one rounding.
+    ``out`` / ``q``: [B*Sq][H*D] bf16 views with a free row stride each, head h at columns h*D .. h*D + D (the operands of
+    :func:`attention`).  ``adapters``: a list of up to 4 ``(k, v, N, N_alloc, scale)``; k / v are token-major [B*N_alloc][H*D] views,
+    the first ``N`` <= 32 tokens of each batch valid, V not transposed.  D in {64, 96, 160}.  An adapter with scale 0 is skipped; with
+    every scale 0 nothing launches.  Unsupported shapes are DA_ERR_UNSUPPORTED from the library; row strides that are no multiple of 8
+    elements and bases that are not 16-byte aligned are refused here by name.  The entry has no plan number: refused while a launch
+    plan is being recorded.  Returns ``out``."""
+    if getattr(L._tls, "recorder", None) is not None:
+        raise RuntimeError("ip_attention_accumulate: not replayable by a launch plan (da_attention_ip_bf16 has no DA_FN_* number); "
+                           "run a step with an IP-Adapter eagerly or as a captured HIP graph")
+    adapters = list(adapters)
+    if len(adapters) > L.IP_MAX_ADAPTERS:
+        L.check(DA_ERR_UNSUPPORTED, f"da_attention_ip_bf16 ({len(adapters)} adapters, at most {L.IP_MAX_ADAPTERS} a launch)")
+    rows, width = B * Sq, H * D
+    p = L.AttentionIPParams()
+
+    def view(t, name, shape):
+        _req(t, name)
+        ld = _rows2d(t, name)
+        if tuple(t.shape) != shape:
+            raise ValueError(f"ip_attention_accumulate: {name} must be {list(shape)}, got {tuple(t.shape)}")
+        if ld % 8 or t.data_ptr() % 16:
+            raise ValueError(f"ip_attention_accumulate: {name} needs a row stride that is a multiple of 8 elements and a 16-byte "
+                             f"aligned base (16-byte loads and stores), got row stride {ld} and address % 16 = {t.data_ptr() % 16}")
+        return t.data_ptr(), ld
+    p.q, p.q_row_stride = view(q, "q", (rows, width))
+    p.out, p.o_row_stride = view(out, "out", (rows, width))
+    for a, (k, v, n, n_alloc, s) in enumerate(adapters):
+        p.k[a], p.k_row_stride[a] = view(k, f"k[{a}]", (B * n_alloc, width))
+        p.v[a], p.v_row_stride[a] = view(v, f"v[{a}]", (B * n_alloc, width))
+        p.n[a], p.n_alloc[a], p.scale[a] = n, n_alloc, s
+    p.A, p.B, p.H, p.D, p.Sq = len(adapters), B, H, D, Sq
+    p.sm_scale = (D ** -0.5) if scale is None else scale
+    L.check(L.load().da_attention_ip_bf16(C.byref(p), _stream()), "da_attention_ip_bf16")
+    return out
+
+
 def softmax_rows(scores: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Row softmax of fp32 scores [M][N] -> bf16.  ``out`` may be wider than N (row stride free): columns >= N are left
     untouched, so a zero-initialised [M][ceil64(N)] buffer is a valid K-padded GEMM operand.  Any N; the row strides of

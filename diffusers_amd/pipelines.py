@@ -523,7 +523,14 @@ class _LatentDiffusionBase(_VaeTilingMixin, _StepCallbacks, _CapturedStepLoop, P
         by_value = float(guidance_scale) if cond.get("timestep_cond") is None else 0.0
         return (tuple(latents.shape), by_value, bool(do_cfg), cond["kvs"][0][0].skv if cond["kvs"] else 0,
                 self._noise_table.data_ptr() if self._noise_table is not None else 0, float(self._eta),
-                float(self._guidance_rescale)) + _key_tail(sch, self.unet, latents)
+                float(self._guidance_rescale)) + _key_tail(sch, self.unet, latents) + self._ip_tokens(cond)
+
+    @staticmethod
+    def _ip_tokens(cond) -> tuple:
+        """IP-Adapter: the image-token counts (valid, allocated) per adapter -- kernel arguments of a captured step; the scales are
+        in the U-Net's ``graph_token``."""
+        ip = cond["kvs"][0][0].ip if cond["kvs"] else None
+        return tuple((n, na) for _, _, n, na in ip) if ip else ()
 
     def _refresh_static(self, captured, new):
         old, cond = captured[0], new[0]
@@ -531,6 +538,9 @@ class _LatentDiffusionBase(_VaeTilingMixin, _StepCallbacks, _CapturedStepLoop, P
             for a, b in zip(kv_old, kv_new):
                 a.k.copy_(b.k)
                 a.vt.copy_(b.vt)
+                for ip_old, ip_new in zip(a.ip or (), b.ip or ()):
+                    ip_old[0].copy_(ip_new[0])
+                    ip_old[1].copy_(ip_new[1])
         if old["aug_emb"] is not None:
             old["aug_emb"].copy_(cond["aug_emb"])
         if old.get("timestep_cond") is not None:
@@ -551,6 +561,9 @@ class _LatentDiffusionBase(_VaeTilingMixin, _StepCallbacks, _CapturedStepLoop, P
     def _arm(self, guidance_scale, guidance_rescale, callback_on_step_end, callback_on_step_end_tensor_inputs,
              use_graph=True) -> bool:
         """What every call sets before anything reads it; returns ``do_cfg``."""
+        if use_graph == "plan" and self._ip_loaded():
+            raise NotImplementedError('use_graph="plan" with an IP-Adapter loaded: da_attention_ip_bf16 has no launch-plan number; '
+                                      "call with use_graph=True (captured HIP graph) or False, or unload_ip_adapter() first")
         if use_graph == "plan" and self.unet.graph_token():
             raise NotImplementedError('use_graph="plan" with FreeU enabled: da_freeu_nhwc_bf16 has no launch-plan number; call '
                                       "with use_graph=True (captured HIP graph) or False, or disable_freeu() first")
@@ -558,7 +571,79 @@ class _LatentDiffusionBase(_VaeTilingMixin, _StepCallbacks, _CapturedStepLoop, P
         self._arm_callback(callback_on_step_end, callback_on_step_end_tensor_inputs)
         self._guidance_scale = float(guidance_scale)
         # pipeline_stable_diffusion_xl.py:831-832: a U-Net that takes the guidance scale as an embedding runs without the CFG batch
-        return guidance_scale > 1.0 and _time_cond_dim(self.unet) is None
+        self._do_cfg = guidance_scale > 1.0 and _time_cond_dim(self.unet) is None
+        return self._do_cfg
+
+    # ---- IP-Adapter (loaders/ip_adapter.py IPAdapterMixin; diffusers_amd/ip_adapter.py) ---------------------------------------
+    image_encoder = None     # optional caller-side torch module with ``.image_embeds`` (CLIPVisionModelWithProjection), for ip_adapter_image=
+    _ip_call = None          # this call's image embeddings, one [2 or 1][num_images][emb] tensor per adapter
+    _do_cfg = False
+
+    def _ip_loaded(self) -> bool:
+        return getattr(self.unet, "_ip", None) is not None
+
+    def load_ip_adapter(self, pretrained_model_name_or_path_or_dict, subfolder=None, weight_name=None, **kwargs):
+        """One IP-Adapter or a list of them (at most four): a checkpoint dict, or a local ``.safetensors`` file with ``image_proj.`` /
+        ``ip_adapter.`` keys.  The image encoder is not loaded: pass ``ip_adapter_image_embeds=``, or put a torch encoder into
+        ``pipe.image_encoder``."""
+        from .ip_adapter import read_ip_adapter
+        if kwargs:
+            raise TypeError(f"load_ip_adapter: unexpected arguments {sorted(kwargs)} (local files only: no hub options)")
+        srcs = list(pretrained_model_name_or_path_or_dict) if isinstance(pretrained_model_name_or_path_or_dict, (list, tuple)) \
+            else [pretrained_model_name_or_path_or_dict]
+        subs = list(subfolder) if isinstance(subfolder, (list, tuple)) else [subfolder] * len(srcs)
+        names = list(weight_name) if isinstance(weight_name, (list, tuple)) else [weight_name] * len(srcs)
+        if not len(srcs) == len(subs) == len(names):
+            raise ValueError("`weight_name`, `subfolder` and the checkpoints must have the same length")
+        self.unet._load_ip_adapter_weights([read_ip_adapter(*a) for a in zip(srcs, subs, names)])
+
+    def set_ip_adapter_scale(self, scale):
+        """One float for every adapter or a list with one per adapter; a new value re-captures the step."""
+        self.unet.set_ip_adapter_scale(scale)
+
+    def unload_ip_adapter(self):
+        self.unet._unload_ip_adapter()
+
+    def _arm_ip(self, ip_adapter_image, ip_adapter_image_embeds, ip_adapter_masks=None):
+        """The image prompt of a call -> ``_ip_call`` (read by ``_unet_conditioning``)."""
+        self._ip_call = None
+        if ip_adapter_masks is not None:
+            raise NotImplementedError("`ip_adapter_masks` (IPAdapterMaskProcessor: one region per image) are not built: the image-prompt "
+                                      "kernel attends every query to every image token")
+        if ip_adapter_image is None and ip_adapter_image_embeds is None:
+            if self._ip_loaded():
+                raise ValueError("an IP-Adapter is loaded: pass `ip_adapter_image_embeds` (or unload_ip_adapter())")
+            return
+        if not self._ip_loaded():
+            raise ValueError("`ip_adapter_image` / `ip_adapter_image_embeds` need an IP-Adapter: call load_ip_adapter() first")
+        if ip_adapter_image_embeds is None:
+            if self.image_encoder is None:
+                raise NotImplementedError("`ip_adapter_image`: the pipeline has no `image_encoder` (CLIP vision runs outside this engine); "
+                                          "pass `ip_adapter_image_embeds`")
+            images = ip_adapter_image if isinstance(ip_adapter_image, (list, tuple)) else [ip_adapter_image]
+            ip_adapter_image_embeds = []
+            for img in images:                       # once per call, outside the step, in torch
+                e = self.image_encoder(img).image_embeds[None]
+                ip_adapter_image_embeds.append(torch.cat([torch.zeros_like(e), e]))
+        embeds = [ip_adapter_image_embeds] if torch.is_tensor(ip_adapter_image_embeds) else list(ip_adapter_image_embeds)
+        if len(embeds) != len(self.unet._ip) or any(not torch.is_tensor(e) or e.dim() != 3 for e in embeds):
+            raise ValueError(f"`ip_adapter_image_embeds` must be a list of {len(self.unet._ip)} tensors [2 or 1][num_images][emb] "
+                             "(negative first with classifier-free guidance)")
+        self._ip_call = embeds
+
+    def _image_embeds(self, batch: int):
+        """prepare_ip_adapter_image_embeds: per adapter [batch][num_images][emb], the negative half in front with CFG."""
+        out = []
+        for e in self._ip_call:
+            if self._do_cfg:
+                if e.shape[0] != 2:
+                    raise ValueError("with classifier-free guidance `ip_adapter_image_embeds` tensors are [2][num_images][emb]: "
+                                     "negative, then positive")
+                e = torch.cat([e[:1].repeat(batch // 2, 1, 1), e[1:].repeat(batch // 2, 1, 1)])
+            else:
+                e = e[-1:].repeat(batch, 1, 1)
+            out.append(e.to(device=self.device, dtype=bf16).contiguous())
+        return out
 
     def _timestep_cond(self, batch: int) -> Optional[torch.Tensor]:
         """pipeline_stable_diffusion_xl.py:1188-1193: the embedding of ``guidance_scale - 1``, one row per sample, bf16 -- for a
@@ -571,6 +656,10 @@ class _LatentDiffusionBase(_VaeTilingMixin, _StepCallbacks, _CapturedStepLoop, P
 
     def _unet_conditioning(self, pe, added):
         tc = self._timestep_cond(pe.shape[0])
+        if self._ip_loaded():
+            if self._ip_call is None:
+                raise ValueError("an IP-Adapter is loaded: pass `ip_adapter_image_embeds` (or unload_ip_adapter())")
+            added = dict(added or {}, image_embeds=self._image_embeds(pe.shape[0]))
         return self.unet.precompute_conditioning(pe, added, **({} if tc is None else {"timestep_cond": tc}))
 
     def _takes_custom_schedule(self) -> bool:
@@ -735,7 +824,9 @@ class StableDiffusionXLPipeline(_LatentDiffusionBase):
                  prompt_2=None, negative_prompt=None, negative_prompt_2=None, num_images_per_prompt: int = 1,
                  clip_skip=None, guidance_rescale: float = 0.0, callback_on_step_end=None,
                  callback_on_step_end_tensor_inputs=None, timesteps=None, sigmas=None, denoising_end: Optional[float] = None,
-                 original_inference_steps: Optional[int] = None):
+                 original_inference_steps: Optional[int] = None, ip_adapter_image=None, ip_adapter_image_embeds=None,
+                 ip_adapter_masks=None):
+        self._arm_ip(ip_adapter_image, ip_adapter_image_embeds, ip_adapter_masks)
         self._original_inference_steps = original_inference_steps
         do_cfg = self._arm(guidance_scale, guidance_rescale, callback_on_step_end, callback_on_step_end_tensor_inputs, use_graph)
         embeds = self._prompt_inputs(prompt, prompt_2, negative_prompt, negative_prompt_2, num_images_per_prompt, prompt_embeds,
@@ -755,11 +846,13 @@ class StableDiffusionXLPipeline(_LatentDiffusionBase):
 
 class StableDiffusionPipeline(_LatentDiffusionBase):
     def __init__(self, vae, unet, scheduler, text_encoder=None, tokenizer=None, safety_checker=None,
-                 feature_extractor=None, requires_safety_checker: bool = False):
+                 feature_extractor=None, requires_safety_checker: bool = False, image_encoder=None):
         super().__init__(vae, unet, scheduler)
         if safety_checker is not None:
             raise NotImplementedError("the safety checker is outside this engine: post-filter the returned images")
         self.text_encoder, self.tokenizer = text_encoder, tokenizer   # optional caller-side transformers modules
+        if image_encoder is not None:
+            self.image_encoder = image_encoder                        # IP-Adapter: a torch CLIP vision model for `ip_adapter_image=`
 
     def encode_prompt(self, prompt, device=None, num_images_per_prompt: int = 1, do_classifier_free_guidance: bool = True,
                       negative_prompt=None, clip_skip=None):
@@ -801,7 +894,9 @@ class StableDiffusionPipeline(_LatentDiffusionBase):
                  latents: Optional[torch.Tensor] = None, prompt_embeds=None, negative_prompt_embeds=None,
                  output_type: str = "pt", return_dict: bool = True, generator=None, use_graph: bool = True,
                  negative_prompt=None, num_images_per_prompt: int = 1, clip_skip=None, guidance_rescale: float = 0.0,
-                 callback_on_step_end=None, callback_on_step_end_tensor_inputs=None):
+                 callback_on_step_end=None, callback_on_step_end_tensor_inputs=None, ip_adapter_image=None,
+                 ip_adapter_image_embeds=None, ip_adapter_masks=None):
+        self._arm_ip(ip_adapter_image, ip_adapter_image_embeds, ip_adapter_masks)
         do_cfg = self._arm(guidance_scale, guidance_rescale, callback_on_step_end, callback_on_step_end_tensor_inputs, use_graph)
         embeds = self._prompt_inputs(prompt, negative_prompt, num_images_per_prompt, prompt_embeds, negative_prompt_embeds, clip_skip,
                                      do_cfg)
@@ -844,6 +939,9 @@ class AnimateDiffPipeline(StableDiffusionPipeline):
 
     def enable_freeu(self, *args, **kwargs):
         raise NotImplementedError("FreeU with AnimateDiff is not built")
+
+    def load_ip_adapter(self, *args, **kwargs):
+        raise NotImplementedError("IP-Adapter with AnimateDiff is not built")
 
     def enable_free_noise(self, *args, **kwargs):
         raise NotImplementedError("FreeNoise (and context windows: more than 32 frames) is not built")
@@ -1262,7 +1360,9 @@ class StableDiffusionXLImg2ImgPipeline(_Img2ImgMixin, StableDiffusionXLPipeline)
                  negative_crops_coords_top_left: Tuple[int, int] = (0, 0), negative_target_size: Optional[Tuple[int, int]] = None,
                  aesthetic_score: float = 6.0, negative_aesthetic_score: float = 2.5, clip_skip=None,
                  callback_on_step_end=None, callback_on_step_end_tensor_inputs=None, use_graph: bool = True,
-                 original_inference_steps: Optional[int] = None):
+                 original_inference_steps: Optional[int] = None, ip_adapter_image=None, ip_adapter_image_embeds=None,
+                 ip_adapter_masks=None):
+        self._arm_ip(ip_adapter_image, ip_adapter_image_embeds, ip_adapter_masks)
         self._original_inference_steps = original_inference_steps
         return self._image_call(prompt, prompt_2, image, None, None, None, None, None, strength, num_inference_steps, timesteps,
                                 sigmas, denoising_start, denoising_end, guidance_scale, negative_prompt, negative_prompt_2,
@@ -1300,7 +1400,10 @@ class StableDiffusionImg2ImgPipeline(_Img2ImgMixin, StableDiffusionPipeline):
                  sigmas=None, guidance_scale: float = 7.5, negative_prompt=None, num_images_per_prompt: int = 1,
                  eta: float = 0.0, generator=None, prompt_embeds=None, negative_prompt_embeds=None, output_type: str = "pt",
                  return_dict: bool = True, clip_skip=None, guidance_rescale: float = 0.0, callback_on_step_end=None,
-                 callback_on_step_end_tensor_inputs=None, use_graph: bool = True, original_inference_steps: Optional[int] = None):
+                 callback_on_step_end_tensor_inputs=None, use_graph: bool = True, original_inference_steps: Optional[int] = None,
+                 ip_adapter_image=None, ip_adapter_image_embeds=None,
+                 ip_adapter_masks=None):
+        self._arm_ip(ip_adapter_image, ip_adapter_image_embeds, ip_adapter_masks)
         self._original_inference_steps = original_inference_steps
         return self._image_call(prompt, image, None, None, None, None, None, strength, num_inference_steps, timesteps, sigmas,
                                 guidance_scale, negative_prompt, num_images_per_prompt, eta, generator, None, prompt_embeds,
@@ -1492,11 +1595,12 @@ class _InpaintMixin:
         st["table"] = self.scheduler.add_noise_table(bf16) if nu == 4 else None
         return start.contiguous()
 
-    def _check_inpaint_inputs(self, image, ip_adapter_image, ip_adapter_image_embeds):
+    def _check_inpaint_inputs(self, image, ip_adapter_image, ip_adapter_image_embeds, ip_adapter_masks=None):
         if image is None:
             raise ValueError("`image` input cannot be undefined.")
-        if ip_adapter_image is not None or ip_adapter_image_embeds is not None:
+        if (ip_adapter_image is not None or ip_adapter_image_embeds is not None) and not self._ip_loaded():
             raise NotImplementedError("`ip_adapter_image` / `ip_adapter_image_embeds`: IP-Adapter is outside this engine")
+        self._arm_ip(ip_adapter_image, ip_adapter_image_embeds, ip_adapter_masks)
 
     def _start_latents(self, *args, **kw):
         return self._inpaint_prepare(*args, **kw)
@@ -1538,8 +1642,9 @@ class StableDiffusionInpaintPipeline(_InpaintMixin, StableDiffusionImg2ImgPipeli
                  eta: float = 0.0, generator=None, latents: Optional[torch.Tensor] = None, prompt_embeds=None,
                  negative_prompt_embeds=None, ip_adapter_image=None, ip_adapter_image_embeds=None, output_type: str = "pt",
                  return_dict: bool = True, clip_skip=None, guidance_rescale: float = 0.0, callback_on_step_end=None,
-                 callback_on_step_end_tensor_inputs=None, use_graph: bool = True, original_inference_steps: Optional[int] = None):
-        self._check_inpaint_inputs(image, ip_adapter_image, ip_adapter_image_embeds)
+                 callback_on_step_end_tensor_inputs=None, use_graph: bool = True, original_inference_steps: Optional[int] = None,
+                 ip_adapter_masks=None):
+        self._check_inpaint_inputs(image, ip_adapter_image, ip_adapter_image_embeds, ip_adapter_masks)
         self._original_inference_steps = original_inference_steps
         return self._image_call(prompt, image, mask_image, masked_image_latents, height, width, padding_mask_crop, strength,
                                 num_inference_steps, timesteps, sigmas, guidance_scale, negative_prompt, num_images_per_prompt, eta,
@@ -1566,8 +1671,9 @@ class StableDiffusionXLInpaintPipeline(_InpaintMixin, StableDiffusionXLImg2ImgPi
                  negative_original_size: Optional[Tuple[int, int]] = None, negative_crops_coords_top_left: Tuple[int, int] = (0, 0),
                  negative_target_size: Optional[Tuple[int, int]] = None, aesthetic_score: float = 6.0,
                  negative_aesthetic_score: float = 2.5, clip_skip=None, callback_on_step_end=None,
-                 callback_on_step_end_tensor_inputs=None, use_graph: bool = True, original_inference_steps: Optional[int] = None):
-        self._check_inpaint_inputs(image, ip_adapter_image, ip_adapter_image_embeds)
+                 callback_on_step_end_tensor_inputs=None, use_graph: bool = True, original_inference_steps: Optional[int] = None,
+                 ip_adapter_masks=None):
+        self._check_inpaint_inputs(image, ip_adapter_image, ip_adapter_image_embeds, ip_adapter_masks)
         self._original_inference_steps = original_inference_steps
         return self._image_call(prompt, prompt_2, image, mask_image, masked_image_latents, height, width, padding_mask_crop, strength,
                                 num_inference_steps, timesteps, sigmas, denoising_start, denoising_end, guidance_scale,
@@ -1595,6 +1701,9 @@ class _InstructPix2PixMixin(_ImageResizeMixin):
     _pix2pix = None                 # static input of the captured step: {"image_latents"}
     _image_guidance_scale = 1.5
     _scales_image_latents = False   # SDXL with is_cosxl_edit: image latents * vae.config.scaling_factor
+
+    def load_ip_adapter(self, *args, **kwargs):
+        raise NotImplementedError("IP-Adapter with InstructPix2Pix is not built (three-way guidance has no image-prompt batch)")
 
     def _check_pix2pix_components(self, controlnet=None):
         if controlnet is not None:
@@ -1992,6 +2101,9 @@ class FluxPipeline(_VaeTilingMixin, _StepCallbacks, _CapturedStepLoop, PipelineL
     @property
     def device(self):
         return self.transformer.device
+
+    def load_ip_adapter(self, *args, **kwargs):
+        raise NotImplementedError("IP-Adapter for FLUX is not built (the image-prompt kernel serves the SD / SDXL cross-attentions)")
 
     def set_progress_bar_config(self, **kw):
         pass

@@ -20,12 +20,13 @@ name ends in ``_``).  Registration happens on import of this module (``import di
     fin, moments = torch.ops.mi355x.vae_moments_tile_blend(raw, sB, sC, sP, wq, bq, up, left, moments, 4, h, w, E, y0, x0, kh, kw)
     hidden, skip = torch.ops.mi355x.freeu(hidden, skip, 0.9, 1.3)  # apply_freeu, channels-last
     o = torch.ops.mi355x.temporal_attn(q, k, v, 16, 8, None)      # attention over the frame axis of [B, F, HW, C] tokens, in place
+    torch.ops.mi355x.ip_attn(o, q, [k_ip], [v_ip], [4], [0.6], 20, None)      # IP-Adapter image branch, added onto `o` in place
     small = torch.ops.mi355x.resample_u8(img_u8_nhwc, 768, 1024, "lanczos")   # PIL.Image.resize, to the bit
     small = torch.ops.mi355x.gather_resize(img, 768, 1024, True)              # F.interpolate (nearest), NCHW
 """
 from __future__ import annotations
 
-from typing import Optional, Tuple
+from typing import Optional, Sequence, Tuple
 
 import torch
 
@@ -206,6 +207,35 @@ def _(q, k, v, num_frames, heads, scale):
     return q.new_empty(q.shape)
 
 
+@torch.library.custom_op(f"{NAMESPACE}::ip_attn", mutates_args=("out",), device_types="cuda")
+def ip_attn(out: torch.Tensor, q: torch.Tensor, ks: Sequence[torch.Tensor], vs: Sequence[torch.Tensor], num_tokens: Sequence[int],
+            scales: Sequence[float], heads: int, scale: Optional[float]) -> None:
+    """The image branch of IP-Adapter's decoupled cross-attention (da_attention_ip_bf16), added onto ``out`` IN PLACE:
+    ``out += sum_a scales[a] * softmax(scale * q ks[a]^T) vs[a]``.  ``out`` / ``q``: [B][Sq][heads*D] bf16 with a contiguous last dim
+    and mergeable leading dims; ``ks[a]`` / ``vs[a]``: [B][N_alloc_a][heads*D], token-major, the first ``num_tokens[a]`` tokens of a
+    batch valid.  Nothing is copied: an operand that would need a copy is refused.  The one op of this module that mutates an
+    argument (``IN_PLACE_OPS``); its schema says so."""
+    if q.dim() != 3 or out.shape != q.shape or q.shape[2] % heads or not len(ks) == len(vs) == len(num_tokens) == len(scales):
+        raise ValueError(f"ip_attn: out / q must be [B][Sq][{heads}*D] and ks / vs / num_tokens / scales of one length, got "
+                         f"{tuple(out.shape)} / {tuple(q.shape)} and {len(ks)} / {len(vs)} / {len(num_tokens)} / {len(scales)}")
+    B, Sq, C_ = q.shape
+
+    def flat(t, name, rows):
+        if tuple(t.shape) != (B, rows, C_) or t.stride(2) != 1 or (rows > 1 and B > 1 and t.stride(0) != rows * t.stride(1)):
+            raise ValueError(f"ip_attn: {name} must be a [{B}][{rows}][{C_}] view with a contiguous last dim and stride(0) == rows * "
+                             f"stride(1) (it is not copied), got shape {tuple(t.shape)} strides {t.stride()}")
+        ld = t.stride(1) if rows > 1 else (t.stride(0) if B > 1 else C_)
+        return t.as_strided((B * rows, C_), (ld, 1), t.storage_offset())
+    adapters = [(flat(k, f"ks[{a}]", k.shape[1]), flat(v, f"vs[{a}]", k.shape[1]), int(n), k.shape[1], float(s))
+                for a, (k, v, n, s) in enumerate(zip(ks, vs, num_tokens, scales))]
+    ops.ip_attention_accumulate(flat(out, "out", Sq), flat(q, "q", Sq), adapters, B=B, H=heads, D=C_ // heads, Sq=Sq, scale=scale)
+
+
+@ip_attn.register_fake
+def _(out, q, ks, vs, num_tokens, scales, heads, scale):
+    return None
+
+
 @torch.library.custom_op(f"{NAMESPACE}::resample_u8", mutates_args=(), device_types="cuda")
 def resample_u8(src: torch.Tensor, height: int, width: int, resample: str) -> torch.Tensor:
     """PIL.Image.resize((width, height), resample) of packed uint8 [B][H][W][C] images, C = 1 or 3, to the bit (da_resample_u8);
@@ -232,3 +262,4 @@ def _(src, height, width, nchw):
 
 OPS = ("gemm", "conv2d_nhwc", "flash_attn", "groupnorm", "layernorm", "euler_step", "dpmpp_2m_step", "euler_ancestral_step",
        "vae_moments_tile_blend", "freeu", "temporal_attn", "resample_u8", "gather_resize")
+IN_PLACE_OPS = ("ip_attn",)    # accumulate into their first argument; OPS above are the functional ones

@@ -131,7 +131,37 @@ class UNet2DConditionModel(PretrainedMixin):
 
     def graph_token(self) -> tuple:
         """What ``forward`` bakes into a captured step by value, besides the weights: FreeU's four floats while a stage is on."""
-        return () if self._freeu_stage(0) is None else ("freeu",) + tuple(float(v) for v in self._freeu)
+        freeu = () if self._freeu_stage(0) is None else ("freeu",) + tuple(float(v) for v in self._freeu)
+        return freeu if self._ip is None else freeu + ("ip", self._ip_generation) + self._ip_scales
+
+    # ------------------------------------------------------------------------------------------------------------
+    # IP-Adapter (loaders/unet.py _load_ip_adapter_weights; diffusers_amd/ip_adapter.py)
+    # ------------------------------------------------------------------------------------------------------------
+    _ip = None            # one ip_adapter.ImageProjection per loaded adapter (the reference's encoder_hid_proj), or None
+    _ip_scales = ()       # one float per adapter, read by value by every cross-attention: part of graph_token()
+    _ip_generation = 0
+
+    @property
+    def encoder_hid_proj(self):
+        """The image projection layers of the loaded IP-Adapters (MultiIPAdapterImageProjection's list), or None."""
+        return self._ip
+
+    def _load_ip_adapter_weights(self, state_dicts):
+        """One or several ``{"image_proj": ..., "ip_adapter": {"1.to_k_ip.weight", ...}}`` checkpoints: an image projection each, and
+        ``to_k_ip | to_v_ip`` of every cross-attention as one stacked weight.  ``forward`` then needs
+        ``added_cond_kwargs["image_embeds"]``.  Scales start at 1.0 (``set_ip_adapter_scale``)."""
+        from . import ip_adapter
+        if not self._built:
+            raise RuntimeError("UNet2DConditionModel: call load_state_dict() first")
+        ip_adapter.load_into_unet(self, state_dicts)
+
+    def _unload_ip_adapter(self):
+        from . import ip_adapter
+        ip_adapter.unload_from_unet(self)
+
+    def set_ip_adapter_scale(self, scale):
+        from . import ip_adapter
+        ip_adapter.set_scales(self, scale)
 
     # AnimateDiff: ``(MotionAdapter, num_frames)`` while a ``motion_adapter.UNetMotionModel`` forward runs -- a motion module after
     # every (resnet, attention) pair of the down and up blocks and after the mid block's attention; None for the plain U-Net
@@ -232,6 +262,11 @@ class UNet2DConditionModel(PretrainedMixin):
         if encoder_attention_mask is not None:
             bias = encoder_mask_bias(encoder_attention_mask.to(encoder_hidden_states.device), B, skv)
         kvs = [tr.precompute_kv(ehs_pad, B, skv, skv_alloc, bias) for tr in self._transformers()]
+        if self._ip is not None:
+            from . import ip_adapter
+            ip_adapter.image_kv(self, added_cond_kwargs, B, kvs)      # step-invariant too: CrossKV.ip of every cross-attention
+        elif (added_cond_kwargs or {}).get("image_embeds") is not None:
+            raise ValueError("`added_cond_kwargs['image_embeds']` was passed but no IP-Adapter is loaded (_load_ip_adapter_weights)")
         aug = None
         if self.config.addition_embed_type == "text_time":
             aug = self._text_time_embedding(added_cond_kwargs, B)
@@ -270,8 +305,10 @@ class UNet2DConditionModel(PretrainedMixin):
                 return False
             return (t.data_ptr(), t._version, tuple(t.shape), t.dtype)
         added = added_cond_kwargs or {}
+        images = added.get("image_embeds")
+        images = () if images is None else (images,) if torch.is_tensor(images) else tuple(images)
         key = (ident(encoder_hidden_states), ident(added.get("text_embeds")), ident(added.get("time_ids")),
-               ident(encoder_attention_mask), ident(timestep_cond))
+               ident(encoder_attention_mask), ident(timestep_cond)) + tuple(ident(t) for t in images) + (self._ip_generation,)
         cacheable = not any(k is False for k in key)
         hit = getattr(self, "_cond_cache", None)
         if cacheable and hit is not None and hit[0] == key:
@@ -285,7 +322,7 @@ class UNet2DConditionModel(PretrainedMixin):
             return cond
         # the cache holds references to the keyed tensors, so their storage (and data_ptr) cannot be recycled under it
         self._cond_cache = (key, cond, (encoder_hidden_states, added.get("text_embeds"), added.get("time_ids"),
-                                        encoder_attention_mask, timestep_cond))
+                                        encoder_attention_mask, timestep_cond) + images)
         return cond
 
     @staticmethod

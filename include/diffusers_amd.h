@@ -397,6 +397,37 @@ typedef struct da_attention_temporal_params {
 int da_attention_temporal_bf16(const da_attention_temporal_params* p, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------------
+ * IP-Adapter image-prompt attention (attention_ip.hip): the image branch of the decoupled cross-attention
+ * (attention_processor.py IPAdapterAttnProcessor2_0), accumulated IN PLACE onto the output of the text cross-attention:
+ *   out[b, s, h, :] = bf16( float(out[b, s, h, :]) + sum_a scale[a] * softmax_n(sm_scale * q[b, s, h] . k[a][b, n, h]) v[a][b, n, h, :] )
+ *   q / out: element (b, s, h, d) at ptr + (b*Sq + s)*row_stride + h*D + d (own row stride each), the layout da_attention_bf16
+ *   reads and writes.  k[a] / v[a]: token-major, element (b, n, h, d) at ptr + (b*n_alloc[a] + n)*row_stride[a] + h*D + d, the
+ *   n[a] <= n_alloc[a] first tokens of a batch valid; V is not transposed.
+ *   Supported: 1 <= A <= DA_IP_MAX_ADAPTERS, 1 <= n[a] <= 32, D in {64, 96, 160} (the padded head sizes; padded channels are zero),
+ *   any B, H, Sq >= 1 (B*Sq < 2^31); strides in elements, multiples of 8 and >= H*D, bases 16-byte aligned.  Anything else:
+ *   DA_ERR_UNSUPPORTED and no launch; a NULL pointer: DA_ERR_INVALID.  An adapter with scale[a] == 0 is skipped; with every scale 0
+ *   nothing launches and out keeps its bits (DA_OK).  Bytes outside columns [0, H*D) of the B*Sq rows of out are not written;
+ *   nothing outside the named blocks is read.  Softmax in fp32; P is rounded to bf16 once and the row sum is taken from the rounded
+ *   P; the sum over adapters and the add to out are fp32, rounded to bf16 once.  No workspace; the result depends on the inputs
+ *   alone.  The entry has no DA_FN_* plan number (DA_ABI_VERSION stays 9): a step with an IP-Adapter runs eagerly or as a captured
+ *   HIP graph, not as a launch plan.
+ * ------------------------------------------------------------------------------------------------------------------ */
+#define DA_IP_MAX_ADAPTERS 4
+typedef struct da_attention_ip_params {
+  const void* q;
+  void* out;
+  const void* k[DA_IP_MAX_ADAPTERS];
+  const void* v[DA_IP_MAX_ADAPTERS];
+  int n[DA_IP_MAX_ADAPTERS], n_alloc[DA_IP_MAX_ADAPTERS];
+  int k_row_stride[DA_IP_MAX_ADAPTERS], v_row_stride[DA_IP_MAX_ADAPTERS];
+  float scale[DA_IP_MAX_ADAPTERS];
+  int A, B, H, D, Sq;
+  int q_row_stride, o_row_stride;
+  float sm_scale;
+} da_attention_ip_params;
+int da_attention_ip_bf16(const da_attention_ip_params* p, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------------
  * Normalisation (norm.hip)
  *   da_groupnorm_nhwc_bf16   nn.GroupNorm(G, C, eps) [+ SiLU when act == DA_ACT_SILU] on channels-last [B][HW][C].
  *                            Replaces resnet.py:326-327,:350,:362, transformer_2d.py:466, unet_2d_condition.py:1228-1229,
