@@ -52,6 +52,7 @@ _EXPORTS = {
     "from_reference_config": "config_utils",
     "CLIPTextModel": "text_encoders",
     "CLIPTextModelWithProjection": "text_encoders",
+    "CLIPVisionModelWithProjection": "vision_encoders",
     "T5EncoderModel": "text_encoders",
     "UMT5EncoderModel": "text_encoders",
 }

@@ -142,6 +142,8 @@ PASS_THROUGH = {
                       "refuses under a recording",
     "da_gather_resize": "resizes an input tensor once per call, in front of the encoder and outside any recorded step; "
                         "ops.gather_resize refuses under a recording",
+    "da_clip_patch_embed": "the front of the CLIP vision encoder: runs once per call on the image prompt, outside any recorded step; "
+                           "ops.clip_patch_embed refuses under a recording",
 }
 
 
@@ -218,6 +220,8 @@ SIGNATURES = {
     "da_resample_u8_route": (_i, [_i, _i, _i, _i, _i, _i, _i, _i, _i, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_longlong)]),
     "da_resample_u8": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _vp, _ll, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "da_gather_resize": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
+    "da_clip_patch_embed": (_i, [_vp, _i, _i, _i, _i, _i, _i, _f, _f, _f, _f, _f, _f, _vp, _vp, _vp, _vp, _vp, _f, _vp, _i, _vp, _i, _i, _i,
+                                 _i, _i, _vp]),
     "da_plan_create": (_i, [C.POINTER(PlanOp), _i, C.POINTER(C.c_void_p)]),
     "da_plan_launch": (_i, [_vp, _vp, C.POINTER(C.c_int)]),
     "da_plan_relocate": (_i, [_vp, _i, C.POINTER(C.c_void_p), C.POINTER(C.c_ulonglong), C.POINTER(C.c_void_p),
@@ -234,6 +238,7 @@ POSTERIOR_MOMENTS, POSTERIOR_MEAN, POSTERIOR_SAMPLE, POSTERIOR_NOISE = 0, 1, 2, 
 LATENTS_SHIFT, LATENTS_SCALE = 1, 2
 FREEU_AUTO, FREEU_RESIDENT, FREEU_TWO_LAUNCH = 0, 1, 2   # da_freeu_nhwc_bf16 `path`
 RESAMPLE_AUTO, RESAMPLE_ONE_LAUNCH, RESAMPLE_TWO_LAUNCH = 0, 1, 2   # da_resample_u8 `route`
+CLIP_IMAGE_U8, CLIP_IMAGE_F32 = 0, 1   # da_clip_patch_embed `mode`
 
 ABI_VERSION = 9              # include/diffusers_amd.h DA_ABI_VERSION
 _lib = None

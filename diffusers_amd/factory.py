@@ -108,6 +108,18 @@ def build_ip_adapter_state_dict(unet_config: dict, num_tokens: int = 4, seed: in
     return nest(dinit.random_state_dict(ip_adapter_param_shapes(unet_config, num_tokens, image_embed_dim), seed=seed, device=init_device))
 
 
+def build_clip_vision(config: dict, seed: int = 8, device="cuda", init_device: Optional[str] = None, state_dict=None):
+    """A ``CLIPVisionModelWithProjection`` (vision_encoders.py) for a ``transformers`` CLIPVisionConfig dict with seeded random
+    weights (the per-layer LayerNorm scales around 1), and its ``state_dict`` in the reference's names."""
+    from .vision_encoders import CLIPVisionModelWithProjection, clip_vision_param_shapes
+    if state_dict is None:
+        state_dict = dinit.random_state_dict(clip_vision_param_shapes(config), seed=seed, device=init_device or "cpu")
+        for k, v in state_dict.items():
+            if k.endswith(("layer_norm1.weight", "layer_norm2.weight")):
+                state_dict[k] = (1.0 + 0.1 * v.float()).to(v.dtype)
+    return CLIPVisionModelWithProjection(config).load_state_dict(state_dict, device=device), state_dict
+
+
 def _with_ip_adapter(pipe, ip_adapter, unet_config, seed: int):
     """The factories' ``ip_adapter=`` switch: False, True (one adapter of 4 tokens) or a list of token counts, one adapter each;
     CLIP image embeddings are 64 wide for the tiny U-Nets (cross_attention_dim 64), 1024 otherwise."""

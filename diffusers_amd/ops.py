@@ -1945,6 +1945,73 @@ def gather_resize(src: torch.Tensor, size, *, nchw: bool) -> torch.Tensor:
     return dst
 
 
+# ---- the front of the CLIP vision encoder (csrc/clip_patch_embed.hip) ----------------------------------------------------------------
+def pack_clip_patch_weight(w: torch.Tensor) -> torch.Tensor:
+    """``embeddings.patch_embedding.weight`` [hidden][3][P][P] -> [hidden][Kp] bf16: K = 3 P P in (c, i, j) order (the tensor's own),
+    zero-padded to Kp = ceil32(K).  Once at load."""
+    if w.dim() != 4 or w.shape[1] != 3 or w.shape[2] != w.shape[3]:
+        raise ValueError(f"pack_clip_patch_weight: a [hidden][3][P][P] convolution weight is required, got {tuple(w.shape)}")
+    K = 3 * w.shape[2] * w.shape[3]
+    out = torch.zeros((w.shape[0], (K + 31) // 32 * 32), device=w.device, dtype=bf16)
+    out[:, :K] = w.reshape(w.shape[0], K)
+    return out
+
+
+def clip_patch_embed(image: torch.Tensor, weight: torch.Tensor, class_embedding: torch.Tensor, position_embedding: torch.Tensor,
+                     gamma: torch.Tensor, beta: torch.Tensor, eps: float, *, patch: int, size: Optional[int] = None, crop=(0, 0),
+                     mean=(0.0, 0.0, 0.0), std=(1.0, 1.0, 1.0), out: Optional[torch.Tensor] = None,
+                     emb_out=False):
+    """da_clip_patch_embed: image -> the first CLIP vision layer's input, one launch.  ``image``: uint8 [B][Hs][Ws][3] (then ``size`` is
+    the crop's side S, ``crop`` = (top, left), a pixel is ``(u8 / 255 - mean) / std``) or float32 pixel_values [B][3][S][S].
+    ``weight``: :func:`pack_clip_patch_weight`.  Returns ``(x_out, emb_out or None)``, [B * S_alloc][hidden] bf16, S_alloc =
+    ceil16(1 + (S / patch)^2): LayerNorm(class / patch embedding + position) with zero padding rows, and the same rows before the
+    LayerNorm where ``emb_out`` is True or a tensor to write."""
+    _refuse_recording("clip_patch_embed", "da_clip_patch_embed")
+    for t, nm in ((weight, "weight"), (class_embedding, "class_embedding"), (position_embedding, "position_embedding"),
+                  (gamma, "gamma"), (beta, "beta")):
+        _req(t, nm)
+        if not t.is_contiguous():
+            raise ValueError(f"clip_patch_embed: {nm} must be contiguous")
+    require_hip(image, "image", dtypes=(torch.uint8, torch.float32))
+    row = image.stride(1) if image.dim() == 4 and image.dtype == torch.uint8 else 0         # uint8: rows may be strided
+    if image.dim() != 4 or not (image.is_contiguous() or (row and image.stride() == (image.shape[1] * row, row, 3, 1))):
+        raise ValueError(f"clip_patch_embed: a uint8 [B][H][W][3] (packed pixels, images H rows apart) or contiguous float32 "
+                         f"[B][3][S][S] image is required, got {tuple(image.shape)} with strides {image.stride()}")
+    hidden, P = weight.shape[0], int(patch)
+    if image.dtype == torch.uint8:
+        mode, (B, Hs, Ws, ch) = L.CLIP_IMAGE_U8, image.shape
+        S = int(size) if size is not None else min(Hs, Ws)
+    else:
+        mode, (B, ch, Hs, Ws) = L.CLIP_IMAGE_F32, image.shape
+        S = Hs
+        if Hs != Ws or (size is not None and int(size) != S):
+            raise ValueError(f"clip_patch_embed: float32 pixel_values must be [B][3][S][S], got {tuple(image.shape)}")
+    G = S // max(P, 1)
+    n = 1 + G * G
+    if ch != 3 or weight.shape[1] != (3 * P * P + 31) // 32 * 32 or class_embedding.numel() != hidden or gamma.numel() != hidden or \
+            beta.numel() != hidden or tuple(position_embedding.shape) != (n, hidden):
+        raise ValueError("clip_patch_embed: 3 image channels, weight [hidden][ceil32(3 P P)], class_embedding / gamma / beta [hidden] and "
+                         f"position_embedding [{n}][hidden] are required")
+    S_alloc = (n + 15) // 16 * 16
+    if out is None:
+        out = torch.empty((B * S_alloc, hidden), device=image.device, dtype=bf16)
+    if emb_out is True:
+        emb_out = torch.empty((B * S_alloc, hidden), device=image.device, dtype=bf16)
+    elif emb_out is False:
+        emb_out = None
+    for t, nm in ((out, "out"), (emb_out, "emb_out")):
+        if t is not None:
+            _req(t, nm)
+            if tuple(t.shape) != (B * S_alloc, hidden) or t.stride(1) != 1:
+                raise ValueError(f"clip_patch_embed: {nm} must be [{B * S_alloc}][{hidden}] with contiguous rows")
+    L.check(L.load().da_clip_patch_embed(image.data_ptr(), mode, Hs, Ws, row, int(crop[0]), int(crop[1]),
+                                         *(float(m) for m in mean), *(1.0 / float(s) for s in std), weight.data_ptr(),
+                                         class_embedding.data_ptr(), position_embedding.data_ptr(), gamma.data_ptr(), beta.data_ptr(),
+                                         float(eps), out.data_ptr(), out.stride(0), _ptr(emb_out),
+                                         0 if emb_out is None else emb_out.stride(0), B, S, P, hidden, _stream()), "da_clip_patch_embed")
+    return out, emb_out
+
+
 def vae_posterior_latents(x: torch.Tensor, strides, *, batch: int, hw: int, latent_channels: int, mode: int,
                           wq: Optional[torch.Tensor] = None, bq: Optional[torch.Tensor] = None, eps1: Optional[torch.Tensor] = None,
                           eps2: Optional[torch.Tensor] = None, shift: Optional[float] = None, scale: Optional[float] = None,

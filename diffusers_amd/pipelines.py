@@ -622,8 +622,10 @@ class _LatentDiffusionBase(_VaeTilingMixin, _StepCallbacks, _CapturedStepLoop, P
                                           "pass `ip_adapter_image_embeds`")
             images = ip_adapter_image if isinstance(ip_adapter_image, (list, tuple)) else [ip_adapter_image]
             ip_adapter_image_embeds = []
-            for img in images:                       # once per call, outside the step, in torch
-                e = self.image_encoder(img).image_embeds[None]
+            from .vision_encoders import CLIPVisionModelWithProjection
+            engine = isinstance(self.image_encoder, CLIPVisionModelWithProjection)
+            for img in images:                       # once per call, outside the step: the engine's encoder, or a torch module
+                e = (self.image_encoder.encode_image(img) if engine else self.image_encoder(img).image_embeds)[None]
                 ip_adapter_image_embeds.append(torch.cat([torch.zeros_like(e), e]))
         embeds = [ip_adapter_image_embeds] if torch.is_tensor(ip_adapter_image_embeds) else list(ip_adapter_image_embeds)
         if len(embeds) != len(self.unet._ip) or any(not torch.is_tensor(e) or e.dim() != 3 for e in embeds):

@@ -64,6 +64,8 @@ def _pad_rows(S: int) -> int:
 class _SelfAttention:
     """q / k / v / out projections + flash attention over [B * S_alloc][C] token matrices."""
 
+    head = 64                             # the kernel's head size (vision_encoders._PaddedSelfAttention: 64 / 96 / 128)
+
     def __init__(self, wq, wk, wv, wo, bq=None, bk=None, bv=None, bo=None, heads: int = 1, scale: Optional[float] = None):
         inner = wq.shape[0]
         if inner % heads or inner // heads != 64:
@@ -79,7 +81,7 @@ class _SelfAttention:
         qk, vt = ops.linear_pair({"x": x, "w": self.wqk, "bias": self.bqk},
                                  {"x": self.wv, "w": x, "bias_rows": self.bv})
         inner = self.inner
-        kw = dict(H=self.heads, D=64, Sq=S, Skv=S, Skv_alloc=S_alloc, q_row_stride=2 * inner, k_row_stride=2 * inner,
+        kw = dict(H=self.heads, D=self.head, Sq=S, Skv=S, Skv_alloc=S_alloc, q_row_stride=2 * inner, k_row_stride=2 * inner,
                   q_batch_stride=S_alloc * 2 * inner, k_batch_stride=S_alloc * 2 * inner, vt_ld=B * S_alloc,
                   vt_batch_stride=S_alloc, scale=self.scale, causal=causal)
         if S_alloc == S:

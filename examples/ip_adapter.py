@@ -2,10 +2,11 @@
 
     python examples/ip_adapter.py /path/to/stable-diffusion-v1-5 /path/to/ip-adapter_sd15.safetensors out.pt
 
-The engine does not run the CLIP vision encoder: ``ip_adapter_image_embeds`` is what ``CLIPVisionModelWithProjection(...).image_embeds``
-gives for the prompt image -- one tensor [2][num_images][1024] per adapter, the negative (zeros) first -- computed once, outside the
-step.  Here it is random, as are the text embeddings, so the script needs no tokenizer or encoder; put your own in their place.  With a
-torch encoder in ``pipe.image_encoder`` the call also takes ``ip_adapter_image=`` (a preprocessed pixel tensor)."""
+``ip_adapter_image_embeds`` is what ``CLIPVisionModelWithProjection(...).image_embeds`` gives for the prompt image -- one tensor
+[2][num_images][1024] per adapter, the negative (zeros) first -- computed once, outside the step.  Here it is random, as are the text
+embeddings, so the script needs no tokenizer or encoder; put your own in their place.  With a fourth and fifth argument -- a local
+CLIP vision directory (config.json, model.safetensors, preprocessor_config.json) and an image file -- the engine's own encoder is attached
+and the call takes the image itself: ``ip_adapter_image=``."""
 import sys
 
 import torch
@@ -29,6 +30,12 @@ if __name__ == "__main__":
     other = [torch.cat([torch.zeros_like(image), torch.randn((1, 1, 1024), generator=g).to(torch.bfloat16)])]
     second = pipe(prompt_embeds=text, negative_prompt_embeds=negative, ip_adapter_image_embeds=other, num_inference_steps=25,
                   generator=g).images
-    torch.save({"first": first.cpu(), "second": second.cpu()}, out_file)
+    results = {"first": first.cpu(), "second": second.cpu()}
+    if len(sys.argv) > 5:
+        from PIL import Image
+        pipe.image_encoder = da.CLIPVisionModelWithProjection.from_pretrained(sys.argv[4])
+        results["image"] = pipe(prompt_embeds=text, negative_prompt_embeds=negative, ip_adapter_image=Image.open(sys.argv[5]),
+                                num_inference_steps=25, generator=g).images.cpu()
+    torch.save(results, out_file)
 
     pipe.unload_ip_adapter()                                # the pipeline as it was: cross-attention takes its usual route again

@@ -874,6 +874,33 @@ int da_gather_resize(const void* src, void* dst, const int* yidx, const int* xid
                      int elem_bytes, int nchw, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------------
+ * The front of a CLIP vision transformer in one launch (csrc/clip_patch_embed.hip; vision_encoders.py): CLIPImageProcessor's
+ * centre crop, rescale and normalise, the P x P stride-P patch convolution (3 -> hidden, no bias), the class token, the position
+ * embedding and pre_layrnorm, written as the padded token matrix the first encoder layer reads.
+ *   image     mode DA_CLIP_IMAGE_U8: packed uint8 [B][Hs][Ws][3] (what da_resample_u8 writes), rows image_row_stride bytes apart,
+ *             images Hs rows apart; the S x S crop starts at (top, left); a pixel is (u8 / 255 - mean_c) * inv_std_c in fp32.
+ *             mode DA_CLIP_IMAGE_F32: float32 [B][3][S][S] pixel_values, normalised already (Hs, Ws, image_row_stride, top, left,
+ *             mean and inv_std are not read).  Either way the pixel is rounded to bf16 as the MFMA operand.
+ *   weight    [hidden][Kp] bf16, K = 3 P P in the reference's (c, i, j) order, zero-padded to Kp = ceil32(K).
+ *   class_embedding [hidden], position_embedding [1 + G G][hidden], gamma / beta [hidden] (pre_layrnorm): bf16.  G = S / P.
+ *   x_out     [B * S_alloc][hidden] bf16, rows x_ld apart, S_alloc = ceil16(1 + G G): row b S_alloc = LN(class + pos[0]), row
+ *             b S_alloc + 1 + p = LN(patch_p . W + pos[1 + p]), rows 1 + G G .. S_alloc - 1 of every image zeros.
+ *   emb_out   NULL or the same shape (rows emb_ld apart): the same rows BEFORE the LayerNorm (hidden_states[0]), padding rows zeros.
+ * fp32 accumulation over K, + pos in fp32, LayerNorm statistics (mean, then the squared differences) in fp32 over the un-rounded row,
+ * one rounding to bf16 per output element.  Nothing else is written.  DA_ERR_INVALID: a required pointer NULL, a mode outside the
+ * two.  DA_ERR_UNSUPPORTED and no launch: hidden % 128 != 0 or hidden > 1664, S % P != 0, Kp > 3072, x_ld / emb_ld no multiple of 8
+ * or below hidden, weight / embeddings / gamma / beta / x_out / emb_out not 16-byte (f32 image: 4-byte) aligned, a crop that leaves
+ * the source, image_row_stride < 3 Ws, a size <= 0.  Runs once per call, outside any recorded step: no DA_FN_* plan number
+ * (DA_ABI_VERSION stays 9); its wrapper refuses inside a plan recording.
+ * ------------------------------------------------------------------------------------------------------------------ */
+#define DA_CLIP_IMAGE_U8 0
+#define DA_CLIP_IMAGE_F32 1
+int da_clip_patch_embed(const void* image, int mode, int Hs, int Ws, int image_row_stride, int top, int left, float mean_r, float mean_g,
+                        float mean_b, float inv_std_r, float inv_std_g, float inv_std_b, const void* weight, const void* class_embedding,
+                        const void* position_embedding, const void* gamma, const void* beta, float eps, void* x_out, int x_ld,
+                        void* emb_out, int emb_ld, int B, int S, int P, int hidden, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------------
  * Launch plans: a recorded sequence of the launch entry points above, owned by the library and replayed by ONE call --
  * the C-ABI form of the denoising step the Python pipelines capture into a HIP graph (the reference's per-step work,
  * pipeline_stable_diffusion_xl.py:1186-1250: scale_model_input, the U-Net forward, the CFG combine, scheduler.step; and the
