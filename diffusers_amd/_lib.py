@@ -106,6 +106,17 @@ class AttentionIPParams(C.Structure):
     ]
 
 
+class AttentionResamplerParams(C.Structure):
+    _fields_ = [
+        ("q", C.c_void_p), ("k0", C.c_void_p), ("v0", C.c_void_p), ("k1", C.c_void_p), ("v1", C.c_void_p), ("out", C.c_void_p),
+        ("B", C.c_int), ("H", C.c_int), ("D", C.c_int), ("Nq", C.c_int),
+        ("S0", C.c_int), ("S0_alloc", C.c_int), ("S1", C.c_int), ("S1_alloc", C.c_int),
+        ("q_row_stride", C.c_int), ("k0_row_stride", C.c_int), ("v0_row_stride", C.c_int), ("k1_row_stride", C.c_int),
+        ("v1_row_stride", C.c_int), ("o_row_stride", C.c_int),
+        ("scale", C.c_float),
+    ]
+
+
 # ---- launch plans (include/diffusers_amd.h "launch plans"; csrc/plan.hip) ----
 PLAN_MAX_ARGS = 16
 FN_IDS = {name: i + 1 for i, name in enumerate((
@@ -144,6 +155,8 @@ PASS_THROUGH = {
                         "ops.gather_resize refuses under a recording",
     "da_clip_patch_embed": "the front of the CLIP vision encoder: runs once per call on the image prompt, outside any recorded step; "
                            "ops.clip_patch_embed refuses under a recording",
+    "da_attention_resampler_bf16": "the attention of IP-Adapter Plus's Resampler projection: runs once per call on the image prompt, "
+                                   "in front of the captured step; ops.resampler_attention refuses under a recording",
 }
 
 
@@ -172,6 +185,7 @@ SIGNATURES = {
     "da_attention_split_plan": (_ll, [C.POINTER(AttentionParams), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "da_attention_temporal_bf16": (_i, [C.POINTER(AttentionTemporalParams), _vp]),
     "da_attention_ip_bf16": (_i, [C.POINTER(AttentionIPParams), _vp]),
+    "da_attention_resampler_bf16": (_i, [C.POINTER(AttentionResamplerParams), _vp]),
     "da_groupnorm_workspace_bytes": (C.c_size_t, [_i, _i, _i, _i]),
     "da_groupnorm_sync_bytes": (C.c_size_t, []),
     "da_groupnorm_nhwc_bf16": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _i, _vp, _vp]),

@@ -101,11 +101,20 @@ def build_motion_adapter(unet_config: dict, seed: int = 4, device="cuda", init_d
 
 
 def build_ip_adapter_state_dict(unet_config: dict, num_tokens: int = 4, seed: int = 6, image_embed_dim: int = 1024,
-                                init_device: str = "cpu"):
+                                init_device: str = "cpu", plus: bool = False, dim: int = 768, depth: int = 4):
     """A seeded plain IP-Adapter checkpoint for ``unet_config`` in the reference's ``{"image_proj": ..., "ip_adapter": ...}`` form
-    (``to_k_ip`` / ``to_v_ip`` of every cross-attention, numbered as loaders/unet.py numbers them)."""
-    from .ip_adapter import ip_adapter_param_shapes, nest
-    return nest(dinit.random_state_dict(ip_adapter_param_shapes(unet_config, num_tokens, image_embed_dim), seed=seed, device=init_device))
+    (``to_k_ip`` / ``to_v_ip`` of every cross-attention, numbered as loaders/unet.py numbers them).  ``plus=True``: a plus checkpoint,
+    whose ``image_proj`` is a perceiver Resampler of ``num_tokens`` latents, width ``dim`` (``dim / 64`` heads) and ``depth`` layers
+    over ``image_embed_dim``-wide hidden states; its LayerNorm scales are around 1."""
+    from .ip_adapter import ip_adapter_param_shapes, ip_adapter_plus_param_shapes, nest
+    if not plus:
+        return nest(dinit.random_state_dict(ip_adapter_param_shapes(unet_config, num_tokens, image_embed_dim), seed=seed, device=init_device))
+    sd = dinit.random_state_dict(ip_adapter_plus_param_shapes(unet_config, num_tokens, image_embed_dim, dim, depth), seed=seed,
+                                 device=init_device)
+    for k, v in sd.items():
+        if k.startswith("image_proj.layers.") and k.endswith(".1.0.weight"):    # the feed-forward's LayerNorm has no "norm" in its name
+            sd[k] = (1.0 + 0.1 * v.float()).to(v.dtype)
+    return nest(sd)
 
 
 def build_clip_vision(config: dict, seed: int = 8, device="cuda", init_device: Optional[str] = None, state_dict=None):
@@ -121,12 +130,18 @@ def build_clip_vision(config: dict, seed: int = 8, device="cuda", init_device: O
 
 
 def _with_ip_adapter(pipe, ip_adapter, unet_config, seed: int):
-    """The factories' ``ip_adapter=`` switch: False, True (one adapter of 4 tokens) or a list of token counts, one adapter each;
-    CLIP image embeddings are 64 wide for the tiny U-Nets (cross_attention_dim 64), 1024 otherwise."""
+    """The factories' ``ip_adapter=`` switch: False, True (one adapter of 4 tokens) or a list with one entry per adapter: a token
+    count for a base adapter, ``"plus"`` for a plus (Resampler) one.  CLIP image embeddings are 64 wide for the tiny U-Nets
+    (cross_attention_dim 64), 1024 otherwise; a tiny plus adapter has 8 latents, width 128 and 2 layers over 128-wide hidden states,
+    a full one the published 16 latents and 4 layers over ViT-H's 1280 (width 768 for SD 1.5, 1280 for SDXL)."""
     if ip_adapter:
-        tokens = [4] if ip_adapter is True else list(ip_adapter)
-        emb = 64 if unet_config["cross_attention_dim"] <= 64 else 1024
-        pipe.load_ip_adapter([build_ip_adapter_state_dict(unet_config, t, seed + 6 + i, emb) for i, t in enumerate(tokens)])
+        tokens = [4] if ip_adapter is True else ["plus"] if ip_adapter == "plus" else list(ip_adapter)
+        tiny = unet_config["cross_attention_dim"] <= 64
+        emb = 64 if tiny else 1024
+        plus = dict(plus=True, num_tokens=8, image_embed_dim=128, dim=128, depth=2) if tiny else \
+            dict(plus=True, num_tokens=16, image_embed_dim=1280, dim=768 if unet_config["cross_attention_dim"] == 768 else 1280)
+        pipe.load_ip_adapter([build_ip_adapter_state_dict(unet_config, seed=seed + 6 + i, **plus) if t == "plus" else
+                              build_ip_adapter_state_dict(unet_config, t, seed + 6 + i, emb) for i, t in enumerate(tokens)])
     return pipe
 
 

@@ -1,6 +1,8 @@
 """IP-Adapter (https://arxiv.org/abs/2308.06721) on the engine: the checkpoint's key numbering, the image projection, loading into a
 ``UNet2DConditionModel`` and the image keys / values of a call.  The attention itself is ``layers.Attention`` (``attach_ip``,
-``precompute_ip_kv``) on ``ops.ip_attention_accumulate`` (csrc/attention_ip.hip).
+``precompute_ip_kv``) on ``ops.ip_attention_accumulate`` (csrc/attention_ip.hip).  The plus checkpoints project with a perceiver
+:class:`Resampler` (models/embeddings.py ``IPAdapterPlusImageProjection``) on ``ops.resampler_attention``
+(csrc/attention_resampler.hip); the per-step half is the same.
 
 Reference: loaders/unet.py ``_convert_ip_adapter_attn_to_diffusers`` / ``_load_ip_adapter_weights`` (a checkpoint is
 ``{"image_proj": {...}, "ip_adapter": {"1.to_k_ip.weight": ..., "1.to_v_ip.weight": ..., "3.to_k_ip.weight": ...}}``: the number
@@ -106,6 +108,107 @@ class ImageProjection:
         return y.view(B, n_img * self.num_tokens, self.cross_dim)
 
 
+_RESAMPLER_TOP = ("latents", "proj_in.weight", "proj_in.bias", "proj_out.weight", "proj_out.bias", "norm_out.weight", "norm_out.bias")
+_RESAMPLER_LAYER = ("0.norm1.weight", "0.norm1.bias", "0.norm2.weight", "0.norm2.bias", "0.to_q.weight", "0.to_kv.weight",
+                    "0.to_out.weight", "1.0.weight", "1.0.bias", "1.1.weight", "1.3.weight")
+RESAMPLER_HEAD_DIM = 64     # every published Resampler; the head size of da_attention_resampler_bf16
+RESAMPLER_MAX_LATENTS = 16  # one query tile of da_attention_resampler_bf16
+
+
+def ip_adapter_plus_param_shapes(config, num_tokens: int = 16, image_embed_dim: int = 1280, dim: int = 768, depth: int = 4,
+                                 ff_mult: int = 4) -> Dict[str, tuple]:
+    """Shapes of a plus (Resampler) IP-Adapter checkpoint for a U-Net config in the original key layout: ``image_proj.layers.i.0`` is
+    the perceiver attention (``norm1`` the image side, ``norm2`` the latents, ``to_kv`` the K rows, then the V rows),
+    ``image_proj.layers.i.1`` the feed-forward (``.0`` LayerNorm, ``.1`` up, ``.3`` down).  ``heads = dim / 64``."""
+    cross = config["cross_attention_dim"]
+    shapes = {"image_proj.latents": (1, num_tokens, dim), "image_proj.proj_in.weight": (dim, image_embed_dim),
+              "image_proj.proj_in.bias": (dim,), "image_proj.proj_out.weight": (cross, dim), "image_proj.proj_out.bias": (cross,),
+              "image_proj.norm_out.weight": (cross,), "image_proj.norm_out.bias": (cross,)}
+    for i in range(depth):
+        pre = f"image_proj.layers.{i}."
+        for n in ("0.norm1", "0.norm2", "1.0"):
+            shapes[pre + n + ".weight"] = shapes[pre + n + ".bias"] = (dim,)
+        shapes[pre + "0.to_q.weight"] = shapes[pre + "0.to_out.weight"] = (dim, dim)
+        shapes[pre + "0.to_kv.weight"] = (2 * dim, dim)
+        shapes[pre + "1.1.weight"], shapes[pre + "1.3.weight"] = (ff_mult * dim, dim), (dim, ff_mult * dim)
+    for i, width in enumerate(cross_attention_widths(config)):
+        shapes[f"ip_adapter.{2 * i + 1}.to_k_ip.weight"] = shapes[f"ip_adapter.{2 * i + 1}.to_v_ip.weight"] = (width, cross)
+    return shapes
+
+
+def is_resampler(sd: Dict[str, torch.Tensor]) -> bool:
+    """An ``image_proj`` dict that is not a plain ImageProjection: a plus Resampler, complete or not, or one of the FaceID kinds."""
+    return any(k in sd for k in _RESAMPLER_KEYS) or "proj.0.weight" in sd
+
+
+class Resampler:
+    """models/embeddings.py IPAdapterPlusImageProjection, the projection of the plus checkpoints: ``depth`` perceiver layers in which
+    ``num_tokens`` learned latents attend to the vision encoder's penultimate hidden states and to themselves, then a feed-forward.
+    ``[B][n_img][S0][embed]`` -> ``[B][n_img * num_tokens][cross_dim]``, the call contract of :class:`ImageProjection` (the images of a
+    sample are folded into the batch and back; their tokens end up adjacent).
+
+    Per layer: two LayerNorm launches, the stacked ``to_k | to_v`` projection of the image rows, ONE stacked ``to_q | to_k | to_v``
+    projection of the latent rows, ``ops.resampler_attention`` on the column blocks of those two outputs (no cat, no transpose),
+    ``to_out`` with the residual epilogue, LayerNorm, FF up with the exact-GELU epilogue, FF down with the residual epilogue."""
+
+    def __init__(self, sd: Dict[str, torch.Tensor], cross_dim: int, device):
+        faceid = [k for k in sd if k in _RESAMPLER_KEYS[2:] or k == "proj.0.weight"]
+        if faceid:
+            raise NotImplementedError(f"IP-Adapter Resampler / FaceID projections with the key {faceid[0]!r} (FaceID, FaceID-plus, "
+                                      "full-face) are not built: only the plus Resampler and the base ImageProjection")
+        depth = 1 + max([int(k.split(".")[1]) for k in sd if k.startswith("layers.") and k.split(".")[1].isdigit()], default=-1)
+        want = set(_RESAMPLER_TOP) | {f"layers.{i}.{n}" for i in range(depth) for n in _RESAMPLER_LAYER}
+        if depth == 0 or set(sd) != want:
+            odd = sorted(want - set(sd)) or sorted(set(sd) - want) or ["layers.0.0.to_q.weight"]
+            raise NotImplementedError(f"IP-Adapter Resampler projection: the checkpoint is not a complete plus Resampler, key "
+                                      f"{odd[0]!r} is {'missing' if odd[0] in want else 'unexpected'}")
+        w = {k: v.to(device=device, dtype=bf16).contiguous() for k, v in sd.items()}
+        self.latents = w["latents"][0].contiguous()                       # [Nq][dim]
+        self.num_tokens, self.dim = self.latents.shape
+        self.embed_dim, self.cross_dim, self.depth = w["proj_in.weight"].shape[1], cross_dim, depth
+        inner = w["layers.0.0.to_q.weight"].shape[0]
+        self.heads, self.inner = inner // RESAMPLER_HEAD_DIM, inner
+        if inner % RESAMPLER_HEAD_DIM or not 1 <= self.num_tokens <= RESAMPLER_MAX_LATENTS:
+            raise NotImplementedError(f"IP-Adapter Resampler with {self.num_tokens} latents and an attention width of {inner}: heads of "
+                                      f"{RESAMPLER_HEAD_DIM} channels and 1 .. {RESAMPLER_MAX_LATENTS} latents are supported")
+        if w["proj_out.weight"].shape[0] != cross_dim:
+            raise ValueError(f"IP-Adapter Resampler projects to {w['proj_out.weight'].shape[0]} channels, the U-Net's "
+                             f"cross_attention_dim is {cross_dim}")
+        self.proj_in, self.proj_out = (w["proj_in.weight"], w["proj_in.bias"]), (w["proj_out.weight"], w["proj_out.bias"])
+        self.norm_out = (w["norm_out.weight"], w["norm_out.bias"])
+        self.layers = []
+        for i in range(depth):
+            g = lambda n: w[f"layers.{i}.{n}"]  # noqa: E731
+            self.layers.append(dict(ln0=(g("0.norm1.weight"), g("0.norm1.bias")), ln1=(g("0.norm2.weight"), g("0.norm2.bias")),
+                                    kv=g("0.to_kv.weight"), qkv=torch.cat([g("0.to_q.weight"), g("0.to_kv.weight")]).contiguous(),
+                                    out=g("0.to_out.weight"), ff_ln=(g("1.0.weight"), g("1.0.bias")), up=g("1.1.weight"),
+                                    down=g("1.3.weight")))
+
+    def __call__(self, embeds: torch.Tensor) -> torch.Tensor:
+        if embeds.dim() != 4 or embeds.shape[3] != self.embed_dim:
+            raise ValueError(f"image_embeds of a plus (Resampler) adapter must be [batch][num_images][tokens][{self.embed_dim}] (the "
+                             f"vision encoder's hidden_states[-2]), got {tuple(embeds.shape)}")
+        B, n_img, S0, _ = embeds.shape
+        Nq, inner = self.num_tokens, self.inner
+        if n_img * Nq > MAX_TOKENS:
+            raise NotImplementedError(f"{n_img} images x {Nq} tokens: more than {MAX_TOKENS} image tokens per adapter")
+        Bf = B * n_img
+        x = embeds.to(device=self.latents.device, dtype=bf16).reshape(Bf * S0, self.embed_dim).contiguous()
+        x = ops.linear(x, *self.proj_in)
+        lat = self.latents.repeat(Bf, 1)
+        for ly in self.layers:
+            e, l = ops.layer_norm(x, *ly["ln0"], 1e-5), ops.layer_norm(lat, *ly["ln1"], 1e-5)
+            kv0, qkv1 = ops.linear(e, ly["kv"]), ops.linear(l, ly["qkv"])
+            a = ops.resampler_attention(qkv1[:, :inner], kv0[:, :inner], kv0[:, inner:], qkv1[:, inner:2 * inner], qkv1[:, 2 * inner:],
+                                        B=Bf, H=self.heads, Nq=Nq, S0=S0, S0_alloc=S0, S1=Nq, S1_alloc=Nq,
+                                        scale=RESAMPLER_HEAD_DIM ** -0.5)
+            lat = ops.linear(a, ly["out"], residual=lat)
+            h = ops.linear(ops.layer_norm(lat, *ly["ff_ln"], 1e-5), ly["up"], act=L.ACT_GELU_ERF)
+            lat = ops.linear(h, ly["down"], residual=lat)
+        y = ops.layer_norm(ops.linear(lat, *self.proj_out), *self.norm_out, 1e-5)
+        return y.view(B, n_img * Nq, self.cross_dim)
+
+
 def cross_attention_layers(unet) -> list:
     """The cross-attention ``layers.Attention`` objects of a loaded U-Net in checkpoint order: down, up, mid."""
     trs = [t for st in unet.down for t in st["attns"]] + [t for st in unet.up for t in st["attns"]] + list(unet.mid["attns"])
@@ -113,15 +216,17 @@ def cross_attention_layers(unet) -> list:
 
 
 def load_into_unet(unet, state_dicts) -> None:
-    """``UNet2DConditionModel._load_ip_adapter_weights``: one ImageProjection and one ``to_k_ip | to_v_ip`` pair per layer for each
-    checkpoint; the scales start at 1.0."""
+    """``UNet2DConditionModel._load_ip_adapter_weights``: one image projection (a :class:`Resampler` for a plus checkpoint, an
+    :class:`ImageProjection` otherwise; the two kinds mix freely) and one ``to_k_ip | to_v_ip`` pair per layer for each checkpoint; the
+    scales start at 1.0."""
     if isinstance(state_dicts, dict):
         state_dicts = [state_dicts]
     sds = [nest(sd) for sd in state_dicts]
     if not 1 <= len(sds) <= L.IP_MAX_ADAPTERS:
         raise NotImplementedError(f"{len(sds)} IP-Adapters: 1 .. {L.IP_MAX_ADAPTERS} at once are supported")
     layers = cross_attention_layers(unet)
-    proj = [ImageProjection(sd["image_proj"], unet.config.cross_attention_dim, unet.device) for sd in sds]
+    proj = [(Resampler if is_resampler(sd["image_proj"]) else ImageProjection)(sd["image_proj"], unet.config.cross_attention_dim, unet.device)
+            for sd in sds]
     for sd in sds:
         want = {f"{2 * i + 1}.to_{c}_ip.weight" for i in range(len(layers)) for c in "kv"}
         if set(sd["ip_adapter"]) != want:
@@ -159,7 +264,7 @@ def image_kv(unet, added_cond_kwargs, batch: int, kvs) -> None:
     embeds = (added_cond_kwargs or {}).get("image_embeds")
     if embeds is None:
         raise ValueError("an IP-Adapter is loaded: `added_cond_kwargs['image_embeds']` (a list, one [batch][num_images][emb] tensor per "
-                         "adapter) is required")
+                         "adapter, [batch][num_images][tokens][emb] for a plus adapter) is required")
     embeds = [embeds] if torch.is_tensor(embeds) else list(embeds)
     if len(embeds) != len(unet._ip) or any(e.shape[0] != batch for e in embeds):
         raise ValueError(f"image_embeds: expected {len(unet._ip)} tensors of batch {batch}, got {[tuple(e.shape) for e in embeds]}")

@@ -856,6 +856,45 @@ def ip_attention_accumulate(out: torch.Tensor, q: torch.Tensor, adapters, *, B: 
     return out
 
 
+def resampler_attention(q: torch.Tensor, k0: torch.Tensor, v0: torch.Tensor, k1: Optional[torch.Tensor], v1: Optional[torch.Tensor], *,
+                        B: int, H: int, Nq: int, S0: int, S0_alloc: int, S1: int, S1_alloc: int, scale: Optional[float] = None,
+                        out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """da_attention_resampler_bf16 (csrc/attention_resampler.hip): ``out = softmax(scale * q [k0; k1]^T) [v0; v1]`` per (batch, head),
+    the attention of IP-Adapter Plus's Resampler.  ``q`` / ``out``: [B*Nq][H*64] bf16 views with a free row stride each, head h at
+    columns h*64 .. h*64 + 64.  ``k0`` / ``v0``: token-major [B*S0_alloc][H*64] views, the first ``S0`` rows of a batch valid;
+    ``k1`` / ``v1``: [B*S1_alloc][H*64] with ``S1`` valid rows, or None with S1 = 0.  Nothing is concatenated or transposed.
+    1 <= Nq <= 16, 0 <= S1 <= 16, head size 64 (anything else: DA_ERR_UNSUPPORTED from the library); row strides that are no multiple
+    of 8 elements and bases that are not 16-byte aligned are refused here by name.  The entry has no plan number: refused while a
+    launch plan is being recorded.  Returns ``out``."""
+    if getattr(L._tls, "recorder", None) is not None:
+        raise RuntimeError("resampler_attention: not replayable by a launch plan (da_attention_resampler_bf16 has no DA_FN_* number); "
+                           "the Resampler runs once per call, outside the recorded step")
+    D = 64
+    width = H * D
+    if out is None:
+        out = torch.empty((B * Nq, width), device=q.device, dtype=bf16)
+    p = L.AttentionResamplerParams()
+    operands = [("q", q, B * Nq), ("out", out, B * Nq), ("k0", k0, B * S0_alloc), ("v0", v0, B * S0_alloc)]
+    if S1 > 0 or k1 is not None or v1 is not None:
+        operands += [("k1", k1, B * S1_alloc), ("v1", v1, B * S1_alloc)]
+    for name, t, rows in operands:
+        if t is None:
+            raise ValueError(f"resampler_attention: {name} is required with S1 = {S1}")
+        _req(t, name)
+        ld = _rows2d(t, name)
+        if tuple(t.shape) != (rows, width):
+            raise ValueError(f"resampler_attention: {name} must be [{rows}][{width}], got {tuple(t.shape)}")
+        if ld % 8 or t.data_ptr() % 16:
+            raise ValueError(f"resampler_attention: {name} needs a row stride that is a multiple of 8 elements and a 16-byte aligned "
+                             f"base (16-byte loads and stores), got row stride {ld} and address % 16 = {t.data_ptr() % 16}")
+        setattr(p, name, t.data_ptr())
+        setattr(p, ("o" if name == "out" else name) + "_row_stride", ld)
+    p.B, p.H, p.D, p.Nq, p.S0, p.S0_alloc, p.S1, p.S1_alloc = B, H, D, Nq, S0, S0_alloc, S1, S1_alloc
+    p.scale = (D ** -0.5) if scale is None else scale
+    L.check(L.load().da_attention_resampler_bf16(C.byref(p), _stream()), "da_attention_resampler_bf16")
+    return out
+
+
 def softmax_rows(scores: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Row softmax of fp32 scores [M][N] -> bf16.  ``out`` may be wider than N (row stride free): columns >= N are left
     untouched, so a zero-initialised [M][ceil64(N)] buffer is a valid K-padded GEMM operand.  Any N; the row strides of

@@ -584,8 +584,9 @@ class _LatentDiffusionBase(_VaeTilingMixin, _StepCallbacks, _CapturedStepLoop, P
 
     def load_ip_adapter(self, pretrained_model_name_or_path_or_dict, subfolder=None, weight_name=None, **kwargs):
         """One IP-Adapter or a list of them (at most four): a checkpoint dict, or a local ``.safetensors`` file with ``image_proj.`` /
-        ``ip_adapter.`` keys.  The image encoder is not loaded: pass ``ip_adapter_image_embeds=``, or put a torch encoder into
-        ``pipe.image_encoder``."""
+        ``ip_adapter.`` keys; base (ImageProjection) and plus (Resampler) checkpoints, mixed freely.  The image encoder is not loaded:
+        pass ``ip_adapter_image_embeds=``, or put an encoder into ``pipe.image_encoder`` (a plus adapter takes its
+        ``hidden_states[-2]``)."""
         from .ip_adapter import read_ip_adapter
         if kwargs:
             raise TypeError(f"load_ip_adapter: unexpected arguments {sorted(kwargs)} (local files only: no hub options)")
@@ -616,21 +617,39 @@ class _LatentDiffusionBase(_VaeTilingMixin, _StepCallbacks, _CapturedStepLoop, P
             return
         if not self._ip_loaded():
             raise ValueError("`ip_adapter_image` / `ip_adapter_image_embeds` need an IP-Adapter: call load_ip_adapter() first")
+        from .ip_adapter import Resampler
+        plus = [isinstance(p, Resampler) for p in self.unet._ip]    # a plus adapter takes hidden states, not the pooled embedding
         if ip_adapter_image_embeds is None:
             if self.image_encoder is None:
                 raise NotImplementedError("`ip_adapter_image`: the pipeline has no `image_encoder` (CLIP vision runs outside this engine); "
                                           "pass `ip_adapter_image_embeds`")
             images = ip_adapter_image if isinstance(ip_adapter_image, (list, tuple)) else [ip_adapter_image]
+            if len(images) != len(plus):
+                raise ValueError(f"`ip_adapter_image` must be one image (or list of images) per adapter: {len(plus)} are loaded, got "
+                                 f"{len(images)}")
             ip_adapter_image_embeds = []
             from .vision_encoders import CLIPVisionModelWithProjection
-            engine = isinstance(self.image_encoder, CLIPVisionModelWithProjection)
-            for img in images:                       # once per call, outside the step: the engine's encoder, or a torch module
-                e = (self.image_encoder.encode_image(img) if engine else self.image_encoder(img).image_embeds)[None]
-                ip_adapter_image_embeds.append(torch.cat([torch.zeros_like(e), e]))
+            enc = self.image_encoder
+            engine = isinstance(enc, CLIPVisionModelWithProjection)
+            for img, hidden in zip(images, plus):    # once per call, outside the step: the engine's encoder, or a torch module
+                if not hidden:
+                    e = (enc.encode_image(img) if engine else enc(img).image_embeds)[None]
+                    ip_adapter_image_embeds.append(torch.cat([torch.zeros_like(e), e]))
+                    continue
+                # a plus adapter: the penultimate hidden states; the negative is the encoder on an all-zero image
+                # (pipeline_stable_diffusion.py encode_image, output_hidden_states=True: `torch.zeros_like(image)`)
+                if engine:
+                    e = enc.encode_image(img, output_hidden_states=True, return_embeds=False).hidden_states[-2]
+                    size = enc.config.image_size
+                    zeros = torch.zeros((e.shape[0], 3, size, size), device=e.device)
+                else:
+                    e, zeros = enc(img, output_hidden_states=True).hidden_states[-2], torch.zeros_like(img)
+                neg = enc(zeros, output_hidden_states=True).hidden_states[-2]
+                ip_adapter_image_embeds.append(torch.stack([neg, e]))
         embeds = [ip_adapter_image_embeds] if torch.is_tensor(ip_adapter_image_embeds) else list(ip_adapter_image_embeds)
-        if len(embeds) != len(self.unet._ip) or any(not torch.is_tensor(e) or e.dim() != 3 for e in embeds):
-            raise ValueError(f"`ip_adapter_image_embeds` must be a list of {len(self.unet._ip)} tensors [2 or 1][num_images][emb] "
-                             "(negative first with classifier-free guidance)")
+        if len(embeds) != len(plus) or any(not torch.is_tensor(e) or e.dim() != (4 if h else 3) for e, h in zip(embeds, plus)):
+            raise ValueError(f"`ip_adapter_image_embeds` must be a list of {len(plus)} tensors [2 or 1][num_images][emb] "
+                             "([2 or 1][num_images][tokens][emb] for a plus adapter; negative first with classifier-free guidance)")
         self._ip_call = embeds
 
     def _image_embeds(self, batch: int):
@@ -641,9 +660,10 @@ class _LatentDiffusionBase(_VaeTilingMixin, _StepCallbacks, _CapturedStepLoop, P
                 if e.shape[0] != 2:
                     raise ValueError("with classifier-free guidance `ip_adapter_image_embeds` tensors are [2][num_images][emb]: "
                                      "negative, then positive")
-                e = torch.cat([e[:1].repeat(batch // 2, 1, 1), e[1:].repeat(batch // 2, 1, 1)])
+                ones = (1,) * (e.dim() - 1)
+                e = torch.cat([e[:1].repeat(batch // 2, *ones), e[1:].repeat(batch // 2, *ones)])
             else:
-                e = e[-1:].repeat(batch, 1, 1)
+                e = e[-1:].repeat(batch, *((1,) * (e.dim() - 1)))
             out.append(e.to(device=self.device, dtype=bf16).contiguous())
         return out
 

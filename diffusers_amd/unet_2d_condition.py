@@ -137,7 +137,7 @@ class UNet2DConditionModel(PretrainedMixin):
     # ------------------------------------------------------------------------------------------------------------
     # IP-Adapter (loaders/unet.py _load_ip_adapter_weights; diffusers_amd/ip_adapter.py)
     # ------------------------------------------------------------------------------------------------------------
-    _ip = None            # one ip_adapter.ImageProjection per loaded adapter (the reference's encoder_hid_proj), or None
+    _ip = None            # one ip_adapter.ImageProjection / Resampler per loaded adapter (the reference's encoder_hid_proj), or None
     _ip_scales = ()       # one float per adapter, read by value by every cross-attention: part of graph_token()
     _ip_generation = 0
 

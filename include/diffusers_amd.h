@@ -428,6 +428,33 @@ typedef struct da_attention_ip_params {
 int da_attention_ip_bf16(const da_attention_ip_params* p, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------------
+ * Resampler attention (attention_resampler.hip): the attention of IP-Adapter Plus's perceiver Resampler (models/embeddings.py
+ * IPAdapterPlusImageProjection), at most 16 queries over keys / values from TWO token-major sources that are never concatenated:
+ *   out[b, :, h] = softmax(scale * q[b, :, h] . [k0[b]; k1[b]]^T) [v0[b]; v1[b]]
+ *   q / out: element (b, n, h, d) at ptr + (b*Nq + n)*row_stride + h*D + d.  Source s in {0, 1}: element (b, j, h, d) of ks / vs at
+ *   ptr + (b*Ss_alloc + j)*row_stride + h*D + d, the first Ss rows of a batch valid (the rest is never read); V is not transposed.
+ *   Every operand has its own row stride: k and v may be the two column halves of one stacked to_k | to_v projection output.
+ *   Supported: D == 64, 1 <= Nq <= 16, 1 <= S0 <= S0_alloc, 0 <= S1 <= 16 (S1 == 0: k1 / v1 may be NULL and are not looked at),
+ *   any B, H >= 1; strides in elements, multiples of 8 and >= H*D, bases 16-byte aligned.  Anything else: DA_ERR_UNSUPPORTED and
+ *   no launch; a NULL required pointer: DA_ERR_INVALID.  Bytes outside columns [0, H*D) of the B*Nq rows of out are not written.
+ *   Softmax in fp32 over 32-key blocks dealt to four waves; P is rounded to bf16 once and the row sum is taken from the rounded P;
+ *   the waves' partial results are merged in wave order.  No workspace; the result depends on the inputs alone.  The entry has no
+ *   DA_FN_* plan number (DA_ABI_VERSION stays 9): the Resampler runs once per call, in front of the denoising loop.
+ * ------------------------------------------------------------------------------------------------------------------ */
+typedef struct da_attention_resampler_params {
+  const void* q;
+  const void* k0;
+  const void* v0;
+  const void* k1;
+  const void* v1;
+  void* out;
+  int B, H, D, Nq, S0, S0_alloc, S1, S1_alloc;
+  int q_row_stride, k0_row_stride, v0_row_stride, k1_row_stride, v1_row_stride, o_row_stride;
+  float scale;
+} da_attention_resampler_params;
+int da_attention_resampler_bf16(const da_attention_resampler_params* p, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------------
  * Normalisation (norm.hip)
  *   da_groupnorm_nhwc_bf16   nn.GroupNorm(G, C, eps) [+ SiLU when act == DA_ACT_SILU] on channels-last [B][HW][C].
  *                            Replaces resnet.py:326-327,:350,:362, transformer_2d.py:466, unet_2d_condition.py:1228-1229,
