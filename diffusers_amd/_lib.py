@@ -117,6 +117,19 @@ class AttentionResamplerParams(C.Structure):
     ]
 
 
+FP8_TILE_AUTO, FP8_TILE_256x256, FP8_TILE_128x256 = 0, 1, 2   # DA_FP8_TILE_*
+
+
+class GemmFp8Params(C.Structure):
+    _fields_ = [
+        ("A", C.c_void_p), ("B", C.c_void_p), ("scale_a", C.c_void_p), ("scale_b", C.c_void_p), ("C", C.c_void_p),
+        ("bias", C.c_void_p), ("bias_rows", C.c_void_p), ("gate", C.c_void_p), ("residual", C.c_void_p),
+        ("M", C.c_int), ("N", C.c_int), ("K", C.c_int),
+        ("lda", C.c_int), ("ldb", C.c_int), ("ldc", C.c_int), ("ldr", C.c_int), ("ld_gate", C.c_int),
+        ("rows_per_batch", C.c_int), ("act", C.c_int), ("tile", C.c_int),
+    ]
+
+
 # ---- launch plans (include/diffusers_amd.h "launch plans"; csrc/plan.hip) ----
 PLAN_MAX_ARGS = 16
 FN_IDS = {name: i + 1 for i, name in enumerate((
@@ -155,6 +168,10 @@ PASS_THROUGH = {
                         "ops.gather_resize refuses under a recording",
     "da_clip_patch_embed": "the front of the CLIP vision encoder: runs once per call on the image prompt, outside any recorded step; "
                            "ops.clip_patch_embed refuses under a recording",
+    "da_quantize_rows_e4m3": "part of a FLUX step with fp8 linears enabled, which runs eagerly or as a captured HIP graph: a plan number "
+                             "belongs to a later ABI bump; ops.quantize_rows_fp8 refuses under a recording",
+    "da_gemm_fp8": "part of a FLUX step with fp8 linears enabled, which runs eagerly or as a captured HIP graph: a plan number belongs "
+                   "to a later ABI bump; ops.linear_fp8 refuses under a recording",
     "da_attention_resampler_bf16": "the attention of IP-Adapter Plus's Resampler projection: runs once per call on the image prompt, "
                                    "in front of the captured step; ops.resampler_attention refuses under a recording",
 }
@@ -186,6 +203,8 @@ SIGNATURES = {
     "da_attention_temporal_bf16": (_i, [C.POINTER(AttentionTemporalParams), _vp]),
     "da_attention_ip_bf16": (_i, [C.POINTER(AttentionIPParams), _vp]),
     "da_attention_resampler_bf16": (_i, [C.POINTER(AttentionResamplerParams), _vp]),
+    "da_quantize_rows_e4m3": (_i, [_vp, _ll, _vp, _ll, _vp, _i, _i, _vp]),
+    "da_gemm_fp8": (_i, [C.POINTER(GemmFp8Params), _vp]),
     "da_groupnorm_workspace_bytes": (C.c_size_t, [_i, _i, _i, _i]),
     "da_groupnorm_sync_bytes": (C.c_size_t, []),
     "da_groupnorm_nhwc_bf16": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _i, _vp, _vp]),

@@ -1853,6 +1853,91 @@ def freeu(hidden: torch.Tensor, skip: torch.Tensor, *, s: float, b: float, path:
 
 
 # ---- image resizing (csrc/resample.hip) ------------------------------------------------------------------------------------------
+def _refuse_recording_fp8(what: str, entry: str) -> None:
+    if getattr(L._tls, "recorder", None) is not None:
+        raise RuntimeError(f"{what}: not replayable by a launch plan ({entry} has no DA_FN_* number); a step with fp8 linears runs "
+                           "eagerly or as a captured HIP graph")
+
+
+def quantize_rows_fp8(x: torch.Tensor):
+    """da_quantize_rows_e4m3 (csrc/gemm_fp8.hip): bf16 ``x`` [R][K] (row stride free, a multiple of 8 elements) -> ``(q, scale)``,
+    ``q`` [R][K] ``torch.float8_e4m3fn`` and ``scale`` [R] fp32 with ``x ~ scale[:, None] * q``: per row ``scale = amax / 448`` (1 for a
+    zero row) and ``q = e4m3(clamp(x * (1 / scale), +-448))``, round to nearest even.  K must be a multiple of 128 (what
+    :func:`linear_fp8` reads).  Activations are quantised per token, weights [N][K] per output channel by the same call."""
+    _refuse_recording_fp8("quantize_rows_fp8", "da_quantize_rows_e4m3")
+    _req(x, "x")
+    ld = _rows2d(x, "x")
+    R, K = x.shape
+    if K < 128 or K % 128:
+        raise ValueError(f"quantize_rows_fp8: K = {K} must be a multiple of 128 (one fp8 MFMA step)")
+    if ld % 8 or x.data_ptr() % 16:
+        raise ValueError(f"quantize_rows_fp8: x needs a row stride that is a multiple of 8 elements and a 16-byte aligned base (16-byte "
+                         f"loads), got row stride {ld} and address % 16 = {x.data_ptr() % 16}")
+    q = torch.empty((R, K), device=x.device, dtype=torch.float8_e4m3fn)
+    scale = torch.empty((R,), device=x.device, dtype=torch.float32)
+    L.check(L.load().da_quantize_rows_e4m3(x.data_ptr(), ld, q.data_ptr(), K, scale.data_ptr(), R, K, _stream()), "da_quantize_rows_e4m3")
+    return q, scale
+
+
+def linear_fp8(a_q: torch.Tensor, a_scale: torch.Tensor, w_q: torch.Tensor, w_scale: torch.Tensor, bias: Optional[torch.Tensor] = None,
+               bias_rows: Optional[torch.Tensor] = None, act: Optional[int] = None, gate: Optional[torch.Tensor] = None,
+               rows_per_batch: Optional[int] = None, residual: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None, *,
+               tile: int = L.FP8_TILE_AUTO) -> torch.Tensor:
+    """da_gemm_fp8 (csrc/gemm_fp8.hip): ``out[m][n] = epilogue(a_scale[m] * w_scale[n] * sum_k a_q[m][k] * w_q[n][k])``, bf16.
+    ``a_q`` [M][K] / ``w_q`` [N][K]: ``torch.float8_e4m3fn`` with K contiguous and 16-byte aligned rows (:func:`quantize_rows_fp8`);
+    the two operands are interchangeable (the transposed-V projection passes the weight as ``a_q`` and its bias as ``bias_rows``).
+    Epilogue as :func:`linear` orders it -- ``+ bias[n] + bias_rows[m]``, ``act`` (None or ACT_GELU_TANH), ``* gate[m //
+    rows_per_batch][n]``, ``+ residual[m][n]`` -- but carried in fp32 and rounded to bf16 ONCE.  ``out`` may be a view with a wider
+    row stride; nothing outside its [M][N] is written.  K must be a multiple of 128."""
+    _refuse_recording_fp8("linear_fp8", "da_gemm_fp8")
+    f8 = torch.float8_e4m3fn
+    _req(a_q, "a_q", f8), _req(w_q, "w_q", f8), _req(a_scale, "a_scale", torch.float32), _req(w_scale, "w_scale", torch.float32)
+    M, K = a_q.shape
+    N, Kw = w_q.shape
+    if K != Kw:
+        raise ValueError(f"linear_fp8: K mismatch {K} vs {Kw}")
+    if K < 128 or K % 128:
+        raise ValueError(f"linear_fp8: K = {K} must be a multiple of 128 (one fp8 MFMA step)")
+    p = L.GemmFp8Params()
+    p.lda, p.ldb = _rows2d(a_q, "a_q"), _rows2d(w_q, "w_q")
+    for name, t, ld in (("a_q", a_q, p.lda), ("w_q", w_q, p.ldb)):
+        if ld % 16 or t.data_ptr() % 16:
+            raise ValueError(f"linear_fp8: {name} needs a row stride that is a multiple of 16 bytes and a 16-byte aligned base (16-byte "
+                             f"LDS-DMA pieces), got row stride {ld} and address % 16 = {t.data_ptr() % 16}")
+    if tuple(a_scale.shape) != (M,) or tuple(w_scale.shape) != (N,) or not a_scale.is_contiguous() or not w_scale.is_contiguous():
+        raise ValueError(f"linear_fp8: a_scale / w_scale must be contiguous [{M}] / [{N}], got {tuple(a_scale.shape)} / {tuple(w_scale.shape)}")
+    if act not in (None, L.ACT_NONE, L.ACT_GELU_TANH):
+        raise ValueError("linear_fp8: act must be None or ACT_GELU_TANH")
+    if out is None:
+        out = torch.empty((M, N), device=a_q.device, dtype=bf16)
+    _req(out, "out")
+    if tuple(out.shape) != (M, N):
+        raise ValueError(f"linear_fp8: out must be [{M}][{N}], got {tuple(out.shape)}")
+    p.A, p.B, p.scale_a, p.scale_b, p.C = a_q.data_ptr(), w_q.data_ptr(), a_scale.data_ptr(), w_scale.data_ptr(), out.data_ptr()
+    p.M, p.N, p.K, p.ldc = M, N, K, _rows2d(out, "out")
+    for name, t, n in (("bias", bias, N), ("bias_rows", bias_rows, M)):
+        if t is not None:
+            _req(t, name)
+            if tuple(t.shape) != (n,) or not t.is_contiguous():
+                raise ValueError(f"linear_fp8: {name} must be a contiguous [{n}], got {tuple(t.shape)}")
+    p.bias, p.bias_rows = _ptr(bias), _ptr(bias_rows)
+    rpb = int(rows_per_batch or 0)
+    if gate is not None:
+        _req(gate, "gate")
+        nb = (M + rpb - 1) // rpb if rpb else 1
+        if gate.dim() != 2 or gate.shape[1] != N or gate.shape[0] < nb:
+            raise ValueError(f"linear_fp8: gate must be [>= {nb}][{N}] bf16, got {tuple(gate.shape)}")
+        p.gate, p.ld_gate = gate.data_ptr(), _rows2d(gate, "gate")
+    if residual is not None:
+        _req(residual, "residual")
+        if tuple(residual.shape) != (M, N):
+            raise ValueError(f"linear_fp8: residual must be [{M}][{N}], got {tuple(residual.shape)}")
+        p.residual, p.ldr = residual.data_ptr(), _rows2d(residual, "residual")
+    p.rows_per_batch, p.act, p.tile = rpb, int(act or L.ACT_NONE), int(tile)
+    L.check(L.load().da_gemm_fp8(C.byref(p), _stream()), "da_gemm_fp8")
+    return out
+
+
 def _lanczos(x: float) -> float:
     if not -3.0 <= x < 3.0:
         return 0.0

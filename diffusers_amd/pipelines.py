@@ -2159,6 +2159,20 @@ class FluxPipeline(_VaeTilingMixin, _StepCallbacks, _CapturedStepLoop, PipelineL
         sch.step_inplace(v, latents)
         return latents
 
+    def enable_fp8_linears(self):
+        """``FluxTransformer2DModel.enable_fp8_linears``: the block linears of the step on the fp8 MFMA GEMM (opt-in; the next call
+        captures a new step; ``use_graph="plan"`` is refused while it is on)."""
+        self.transformer.enable_fp8_linears()
+
+    def disable_fp8_linears(self):
+        self.transformer.disable_fp8_linears()
+
+    def _denoise(self, latents, step_args: tuple, num_steps: int, use_graph, begin: int = 0):
+        if use_graph == "plan" and self.transformer.graph_token():
+            raise NotImplementedError('use_graph="plan" with fp8 linears enabled: da_gemm_fp8 / da_quantize_rows_e4m3 have no launch-plan '
+                                      "number; call with use_graph=True (captured HIP graph) or False, or disable_fp8_linears() first")
+        return super()._denoise(latents, step_args, num_steps, use_graph, begin=begin)
+
     def _graph_key_extra(self):
         """Addresses of static inputs a subclass's captured step reads besides the latents, embeddings and conditioning."""
         return ()

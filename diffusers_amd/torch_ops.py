@@ -23,6 +23,8 @@ name ends in ``_``).  Registration happens on import of this module (``import di
     torch.ops.mi355x.ip_attn(o, q, [k_ip], [v_ip], [4], [0.6], 20, None)      # IP-Adapter image branch, added onto `o` in place
     small = torch.ops.mi355x.resample_u8(img_u8_nhwc, 768, 1024, "lanczos")   # PIL.Image.resize, to the bit
     small = torch.ops.mi355x.gather_resize(img, 768, 1024, True)              # F.interpolate (nearest), NCHW
+    q, s = torch.ops.mi355x.quantize_rows_fp8(x)                              # per-row e4m3 + fp32 scale
+    y = torch.ops.mi355x.gemm_fp8(q, s, w_q, w_s, bias, 0)                    # F.linear on the fp8 MFMA
 """
 from __future__ import annotations
 
@@ -260,6 +262,30 @@ def _(src, height, width, nchw):
     return src.new_empty((B, src.shape[1], height, width) if nchw else (B, height, width, src.shape[3]))
 
 
+@torch.library.custom_op(f"{NAMESPACE}::quantize_rows_fp8", mutates_args=(), device_types="cuda")
+def quantize_rows_fp8(x: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Per-row e4m3 quantisation of a bf16 matrix [R][K] (da_quantize_rows_e4m3): returns (q float8_e4m3fn [R][K], scale fp32 [R])."""
+    return ops.quantize_rows_fp8(x)
+
+
+@quantize_rows_fp8.register_fake
+def _(x):
+    return x.new_empty(x.shape, dtype=torch.float8_e4m3fn), x.new_empty((x.shape[0],), dtype=torch.float32)
+
+
+@torch.library.custom_op(f"{NAMESPACE}::gemm_fp8", mutates_args=(), device_types="cuda")
+def gemm_fp8(a_q: torch.Tensor, a_scale: torch.Tensor, w_q: torch.Tensor, w_scale: torch.Tensor, bias: Optional[torch.Tensor],
+             act: int) -> torch.Tensor:
+    """out[M][N] = act(a_scale[m] w_scale[n] (a_q[M][K] @ w_q[N][K]^T) + bias), bf16, on the fp8 MFMA (da_gemm_fp8); act = DA_ACT_NONE
+    or DA_ACT_GELU_TANH."""
+    return ops.linear_fp8(a_q, a_scale, w_q, w_scale, bias, act=act)
+
+
+@gemm_fp8.register_fake
+def _(a_q, a_scale, w_q, w_scale, bias, act):
+    return a_q.new_empty((a_q.shape[0], w_q.shape[0]), dtype=bf16)
+
+
 OPS = ("gemm", "conv2d_nhwc", "flash_attn", "groupnorm", "layernorm", "euler_step", "dpmpp_2m_step", "euler_ancestral_step",
-       "vae_moments_tile_blend", "freeu", "temporal_attn", "resample_u8", "gather_resize")
+       "vae_moments_tile_blend", "freeu", "temporal_attn", "resample_u8", "gather_resize", "quantize_rows_fp8", "gemm_fp8")
 IN_PLACE_OPS = ("ip_attn",)    # accumulate into their first argument; OPS above are the functional ones

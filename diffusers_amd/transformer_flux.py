@@ -125,6 +125,7 @@ class FluxTransformer2DModel(PretrainedMixin):
         w = Weights(state_dict, device)
         self.device = torch.device(device)
         self._new_weights_generation()
+        self._fp8 = False                # (fp8 copies belong to the weights they were made from)
         self.time_embedder = TimestepEmbedding(w, "time_text_embed.timestep_embedder")
         self.text_embedder = TimestepEmbedding(w, "time_text_embed.text_embedder")  # Linear -> SiLU -> Linear as well
         self.context_embedder = Linear(w, "context_embedder")
@@ -140,6 +141,61 @@ class FluxTransformer2DModel(PretrainedMixin):
 
     def to(self, *args, **kwargs):
         return check_to(self, args, kwargs)
+
+    # ------------------------------------------------------------------------------------------------------------
+    # FP8 (e4m3) linears: opt-in, default off (csrc/gemm_fp8.hip)
+    # ------------------------------------------------------------------------------------------------------------
+    _fp8 = False
+
+    def _fp8_layers(self):
+        """(state_dict name, holder, attribute) of every block weight the step reads through ``ops.linear``."""
+        for i, blk in enumerate(self.double):
+            p = f"transformer_blocks.{i}"
+            yield from ((f"{p}.attn.to_q|to_k", blk.img, "wqk"), (f"{p}.attn.to_v", blk.img, "wv"),
+                        (f"{p}.attn.add_q_proj|add_k_proj", blk.txt, "wqk"), (f"{p}.attn.add_v_proj", blk.txt, "wv"),
+                        (f"{p}.attn.to_out.0", blk.to_out, "weight"), (f"{p}.attn.to_add_out", blk.to_add_out, "weight"),
+                        (f"{p}.ff.net.0.proj", blk.ff0, "weight"), (f"{p}.ff.net.2", blk.ff2, "weight"),
+                        (f"{p}.ff_context.net.0.proj", blk.ffc0, "weight"), (f"{p}.ff_context.net.2", blk.ffc2, "weight"))
+        for i, blk in enumerate(self.single):
+            p = f"single_transformer_blocks.{i}"
+            yield from ((f"{p}.proj_mlp", blk.proj_mlp, "weight"), (f"{p}.attn.to_q|to_k", blk.qkv, "wqk"),
+                        (f"{p}.attn.to_v", blk.qkv, "wv"), (f"{p}.proj_out", blk.proj_out, "weight"))
+
+    def enable_fp8_linears(self):
+        """Run the block linears -- double blocks: q|k, v, to_out and both feed-forward projections of the image and the text stream;
+        single blocks: proj_mlp, q|k, v, proj_out -- on the fp8 MFMA GEMM: weights are quantised HERE, once, to e4m3 with one fp32 scale
+        per output channel; activations per token in front of every such linear (one ``ops.quantize_rows_fp8`` launch per activation,
+        shared by the linears that read it).  x_embedder, context_embedder, the final proj_out, the modulation projections, attention,
+        norms and RoPE stay bf16.  The bf16 weights are KEPT, so :meth:`disable_fp8_linears` restores the bf16 path to the bit; the
+        price is the fp8 copies on top: one byte per quantised weight, half again of those weights' bf16 size (FLUX.1: 8.6 G
+        parameters, 8.6 GB).  Every quantised layer needs an input width that is a multiple of 128.  Captured steps are re-captured
+        (the flag is part of the graph key); ``use_graph="plan"`` is refused while it is on."""
+        if not self._built:
+            raise RuntimeError("FluxTransformer2DModel: call load_state_dict() first")
+        layers = list(self._fp8_layers())
+        for name, holder, attr in layers:
+            k = getattr(holder, attr).shape[1]
+            if k % 128:
+                raise ValueError(f"enable_fp8_linears: {name} has an input width of {k}, not a multiple of 128 (one fp8 MFMA step)")
+        for name, holder, attr in layers:
+            if getattr(holder, "_fp8_w", None) is None:
+                holder._fp8_w = {}
+            if attr not in holder._fp8_w:
+                holder._fp8_w[attr] = ops.quantize_rows_fp8(getattr(holder, attr))
+        self._fp8 = True
+        return self
+
+    def disable_fp8_linears(self):
+        """Back to the bf16 linears (bit-identical to a model that never enabled fp8) and free the fp8 weight copies."""
+        if self._built:
+            for _, holder, _ in self._fp8_layers():
+                holder._fp8_w = None
+        self._fp8 = False
+        return self
+
+    def graph_token(self) -> tuple:
+        """What ``forward`` bakes into a captured step by value, besides the weights."""
+        return ("fp8",) if self._fp8 else ()
 
     def eval(self):
         return self
@@ -237,6 +293,21 @@ class FluxTransformer2DModel(PretrainedMixin):
         def chunk(t_, i):
             return t_[:, i * C:(i + 1) * C]
 
+        fp8 = self._fp8
+
+        def quant(x):                    # one launch per activation; every linear that reads `x` shares it
+            return ops.quantize_rows_fp8(x) if fp8 else None
+
+        def lin(x, xq, holder, attr, bias, **kw):
+            if xq is None:
+                return ops.linear(x, getattr(holder, attr), bias, **kw)
+            return ops.linear_fp8(*xq, *holder._fp8_w[attr], bias, **kw)
+
+        def lin_t(holder, attr, x, xq, bias_rows, out=None):     # V^T = W_v . X^T: the weight is the M operand
+            if xq is None:
+                return ops.linear(getattr(holder, attr), x, bias_rows=bias_rows, out=out)
+            return ops.linear_fp8(*holder._fp8_w[attr], *xq, bias_rows=bias_rows, out=out)
+
         def attention(qk, vt, out=None):
             return ops.attention(qk, qk[:, C:], vt, B=B, H=Hh, D=D, Sq=S, Skv=S, Skv_alloc=S, q_row_stride=2 * C,
                                  k_row_stride=2 * C, q_batch_stride=S * 2 * C, k_batch_stride=S * 2 * C, vt_ld=B * S,
@@ -255,9 +326,10 @@ class FluxTransformer2DModel(PretrainedMixin):
                     n = ops.layer_norm(x, None, None, 1e-6, mod_scale=chunk(m, 1)[b:b + 1],
                                        mod_shift=chunk(m, 0)[b:b + 1], rows_per_batch=x.shape[0])
                     qk_rows = rows(qk, b, which)
-                    ops.linear(n, pw.wqk, pw.bqk, out=qk_rows)
+                    nq8 = quant(n)
+                    lin(n, nq8, pw, "wqk", pw.bqk, out=qk_rows)
                     lo = b * S + (0 if which == "txt" else St)
-                    ops.linear(pw.wv, n, bias_rows=pw.bv, out=vt[:, lo: lo + x.shape[0]])
+                    lin_t(pw, "wv", n, nq8, pw.bv, out=vt[:, lo: lo + x.shape[0]])
                     ops.rmsnorm_rope_(qk_rows, heads=Hh, head_dim=D, col_offsets=(0, C), weights=(nq, nk), eps=1e-6,
                                       cos=cos, sin=sin, rope_row0=(0 if which == "txt" else St))
             o = attention(qk, vt)
@@ -267,14 +339,15 @@ class FluxTransformer2DModel(PretrainedMixin):
                 for which, m, to_out, f0, f2 in (("img", mi, blk.to_out, blk.ff0, blk.ff2),
                                                  ("txt", mc, blk.to_add_out, blk.ffc0, blk.ffc2)):
                     x, n_rows = rows(Hbuf, b, which), (St if which == "txt" else Si)
-                    ops.linear(rows(o, b, which), to_out.weight, to_out.bias, gate=chunk(m, 2)[b:b + 1],
-                               rows_per_batch=n_rows, residual=x, out=rows(H2, b, which))
+                    o_rows = rows(o, b, which)
+                    lin(o_rows, quant(o_rows), to_out, "weight", to_out.bias, gate=chunk(m, 2)[b:b + 1],
+                        rows_per_batch=n_rows, residual=x, out=rows(H2, b, which))
                     x2 = rows(H2, b, which)
                     n2 = ops.layer_norm(x2, None, None, 1e-6, mod_scale=chunk(m, 4)[b:b + 1],
                                         mod_shift=chunk(m, 3)[b:b + 1], rows_per_batch=n_rows)
-                    h = ops.linear(n2, f0.weight, f0.bias, act=L.ACT_GELU_TANH)
-                    ops.linear(h, f2.weight, f2.bias, gate=chunk(m, 5)[b:b + 1], rows_per_batch=n_rows, residual=x2,
-                               out=rows(H3, b, which))
+                    h = lin(n2, quant(n2), f0, "weight", f0.bias, act=L.ACT_GELU_TANH)
+                    lin(h, quant(h), f2, "weight", f2.bias, gate=chunk(m, 5)[b:b + 1], rows_per_batch=n_rows, residual=x2,
+                        out=rows(H3, b, which))
             Hbuf = H3
 
         # ---- single-stream blocks (transformer_flux.py:383-412) on the joint sequence ----
@@ -282,14 +355,15 @@ class FluxTransformer2DModel(PretrainedMixin):
             m = ops.linear_small_m(temb, blk.norm.weight, blk.norm.bias, act_in=L.ACT_SILU)              # (B, 3C)
             n = ops.layer_norm(Hbuf, None, None, 1e-6, mod_scale=chunk(m, 1), mod_shift=chunk(m, 0), rows_per_batch=S)
             cat = torch.empty((B * S, 5 * C), device=dev, dtype=bf16)                                     # [attn | mlp]
-            ops.linear(n, blk.proj_mlp.weight, blk.proj_mlp.bias, act=L.ACT_GELU_TANH, out=cat[:, C:])
-            qk = ops.linear(n, blk.qkv.wqk, blk.qkv.bqk)
-            vt = ops.linear(blk.qkv.wv, n, bias_rows=blk.qkv.bv)
+            nq8 = quant(n)
+            lin(n, nq8, blk.proj_mlp, "weight", blk.proj_mlp.bias, act=L.ACT_GELU_TANH, out=cat[:, C:])
+            qk = lin(n, nq8, blk.qkv, "wqk", blk.qkv.bqk)
+            vt = lin_t(blk.qkv, "wv", n, nq8, blk.qkv.bv)
             ops.rmsnorm_rope_(qk, heads=Hh, head_dim=D, col_offsets=(0, C), weights=(blk.norm_q, blk.norm_k), eps=1e-6,
                               cos=cos, sin=sin, rope_row0=0, rows_per_batch=S)
             attention(qk, vt, out=cat[:, :C])
-            Hbuf = ops.linear(cat, blk.proj_out.weight, blk.proj_out.bias, gate=chunk(m, 2), rows_per_batch=S,
-                              residual=Hbuf)
+            Hbuf = lin(cat, quant(cat), blk.proj_out, "weight", blk.proj_out.bias, gate=chunk(m, 2), rows_per_batch=S,
+                       residual=Hbuf)
 
         # ---- AdaLayerNormContinuous (scale first, then shift; normalization.py:346-351) + proj_out on the image rows ----
         emb = ops.linear_small_m(temb, self.norm_out.weight, self.norm_out.bias, act_in=L.ACT_SILU)       # (B, 2C)

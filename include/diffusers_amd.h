@@ -455,6 +455,40 @@ typedef struct da_attention_resampler_params {
 int da_attention_resampler_bf16(const da_attention_resampler_params* p, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------------
+ * FP8 linears (gemm_fp8.hip): OCP e4m3 operands (torch.float8_e4m3fn), one fp32 scale per row of either operand.
+ *   da_quantize_rows_e4m3   bf16 x[rows][K] (row stride ldx elements) -> e4m3 q[rows][K] (row stride ldq bytes) and fp32 scale[rows]:
+ *                           amax = max |x| over the row; scale = amax / 448 (1 when amax == 0); q = e4m3_rne(clamp(x * (1 / scale),
+ *                           +-448)), every step one fp32 operation.  K % 128 == 0, ldx % 8 == 0, x 16-byte and q / ldq 8-byte aligned.
+ *   da_gemm_fp8             C[m][n] = epilogue(scale_a[m] * scale_b[n] * sum_k A[m][k] * B[n][k]): both operands row-major with K
+ *                           contiguous, fp32 accumulation on v_mfma_f32_16x16x128_f8f6f4, bf16 out.  Epilogue in fp32, rounded to bf16
+ *                           once: + bias[n] + bias_rows[m], DA_ACT_GELU_TANH, * gate[m / rows_per_batch][n], + residual[m][n]
+ *                           (rows_per_batch == 0: one batch).  K % 128 == 0, K >= 128; lda / ldb multiples of 16 bytes, A / B 16-byte
+ *                           aligned; anything else: DA_ERR_UNSUPPORTED and no launch.  Bytes of C outside [M][N] are not written.
+ *   Neither entry has a DA_FN_* plan number (DA_ABI_VERSION stays 9): they run eagerly or inside a captured HIP graph.
+ * ------------------------------------------------------------------------------------------------------------------ */
+#define DA_FP8_TILE_AUTO 0
+#define DA_FP8_TILE_256x256 1 /* 8 waves of 128 x 64, two 64 KiB stages */
+#define DA_FP8_TILE_128x256 2 /* 8 waves of 64 x 64, three 48 KiB stages */
+typedef struct da_gemm_fp8_params {
+  const void* A;         /* e4m3 [M][lda] */
+  const void* B;         /* e4m3 [N][ldb] */
+  const void* scale_a;   /* fp32 [M] */
+  const void* scale_b;   /* fp32 [N] */
+  void* C;               /* bf16 [M][ldc] */
+  const void* bias;      /* bf16 [N] or NULL */
+  const void* bias_rows; /* bf16 [M] or NULL */
+  const void* gate;      /* bf16 [M / rows_per_batch][ld_gate] or NULL */
+  const void* residual;  /* bf16 [M][ldr] or NULL */
+  int M, N, K;
+  int lda, ldb, ldc, ldr, ld_gate;
+  int rows_per_batch;
+  int act;  /* DA_ACT_NONE or DA_ACT_GELU_TANH */
+  int tile; /* DA_FP8_TILE_* */
+} da_gemm_fp8_params;
+int da_quantize_rows_e4m3(const void* x, long long ldx, void* q, long long ldq, void* scale, int rows, int K, void* stream);
+int da_gemm_fp8(const da_gemm_fp8_params* p, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------------
  * Normalisation (norm.hip)
  *   da_groupnorm_nhwc_bf16   nn.GroupNorm(G, C, eps) [+ SiLU when act == DA_ACT_SILU] on channels-last [B][HW][C].
  *                            Replaces resnet.py:326-327,:350,:362, transformer_2d.py:466, unet_2d_condition.py:1228-1229,
