@@ -130,6 +130,19 @@ class GemmFp8Params(C.Structure):
     ]
 
 
+class AttentionFp8Params(C.Structure):
+    _fields_ = [
+        ("q8", C.c_void_p), ("k8", C.c_void_p), ("vt8", C.c_void_p), ("sq", C.c_void_p), ("sk", C.c_void_p), ("sv", C.c_void_p),
+        ("out", C.c_void_p),
+        ("B", C.c_int), ("H", C.c_int), ("Sq", C.c_int), ("Skv", C.c_int), ("S8", C.c_int), ("D", C.c_int),
+        ("q_batch_stride", C.c_longlong), ("k_batch_stride", C.c_longlong), ("vt_batch_stride", C.c_longlong),
+        ("o_batch_stride", C.c_longlong), ("sq_batch_stride", C.c_longlong), ("sk_batch_stride", C.c_longlong),
+        ("vt_ld", C.c_longlong),
+        ("q_row_stride", C.c_int), ("k_row_stride", C.c_int), ("o_row_stride", C.c_int),
+        ("scale", C.c_float),
+    ]
+
+
 # ---- launch plans (include/diffusers_amd.h "launch plans"; csrc/plan.hip) ----
 PLAN_MAX_ARGS = 16
 FN_IDS = {name: i + 1 for i, name in enumerate((
@@ -172,6 +185,10 @@ PASS_THROUGH = {
                              "belongs to a later ABI bump; ops.quantize_rows_fp8 refuses under a recording",
     "da_gemm_fp8": "part of a FLUX step with fp8 linears enabled, which runs eagerly or as a captured HIP graph: a plan number belongs "
                    "to a later ABI bump; ops.linear_fp8 refuses under a recording",
+    "da_attention_fp8_prepare": "part of a Wan / FLUX step with fp8 attention enabled, which runs eagerly or as a captured HIP graph: a "
+                                "plan number belongs to a later ABI bump; ops.attention_fp8_prepare refuses under a recording",
+    "da_attention_fp8": "part of a Wan / FLUX step with fp8 attention enabled, which runs eagerly or as a captured HIP graph: a plan "
+                        "number belongs to a later ABI bump; ops.attention_fp8 refuses under a recording",
     "da_attention_resampler_bf16": "the attention of IP-Adapter Plus's Resampler projection: runs once per call on the image prompt, "
                                    "in front of the captured step; ops.resampler_attention refuses under a recording",
 }
@@ -205,6 +222,8 @@ SIGNATURES = {
     "da_attention_resampler_bf16": (_i, [C.POINTER(AttentionResamplerParams), _vp]),
     "da_quantize_rows_e4m3": (_i, [_vp, _ll, _vp, _ll, _vp, _i, _i, _vp]),
     "da_gemm_fp8": (_i, [C.POINTER(GemmFp8Params), _vp]),
+    "da_attention_fp8_prepare": (_i, [_vp, _ll, _vp, _ll, _ll, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
+    "da_attention_fp8": (_i, [C.POINTER(AttentionFp8Params), _vp]),
     "da_groupnorm_workspace_bytes": (C.c_size_t, [_i, _i, _i, _i]),
     "da_groupnorm_sync_bytes": (C.c_size_t, []),
     "da_groupnorm_nhwc_bf16": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _i, _vp, _vp]),

@@ -1938,6 +1938,108 @@ def linear_fp8(a_q: torch.Tensor, a_scale: torch.Tensor, w_q: torch.Tensor, w_sc
     return out
 
 
+def _refuse_recording_fp8_attention(what: str, entry: str) -> None:
+    if getattr(L._tls, "recorder", None) is not None:
+        raise RuntimeError(f"{what}: not replayable by a launch plan ({entry} has no DA_FN_* number); a step with fp8 attention runs "
+                           "eagerly or as a captured HIP graph")
+
+
+def _batched_rows(t: torch.Tensor, name: str, B: int, S: int, width: int):
+    """(row stride, batch stride) in elements of ``t`` = [B*S][width] or [B][S][width] with a contiguous last dim."""
+    if t.dim() == 2 and tuple(t.shape) == (B * S, width) and t.stride(1) == 1:
+        ld = _rows2d(t, name)
+        return ld, S * ld
+    if t.dim() == 3 and tuple(t.shape) == (B, S, width) and t.stride(2) == 1:
+        ld = t.stride(1) if S > 1 else max(t.stride(1), width)
+        return ld, (t.stride(0) if B > 1 else S * ld)
+    raise ValueError(f"{name}: expected [{B * S}][{width}] or [{B}][{S}][{width}] with a contiguous last dim, got shape {tuple(t.shape)} "
+                     f"strides {t.stride()}")
+
+
+def attention_fp8_prepare(qk: torch.Tensor, vt: torch.Tensor, *, B: int, S: int, H: int, out=None):
+    """da_attention_fp8_prepare (csrc/attention_fp8.hip): ``qk`` bf16 [B*S][2C] (q | k after RMSNorm + RoPE, C = 128 H) and ``vt`` bf16
+    [C][B*S] (V transposed, batch b at columns b*S ..) -> ``(q8, k8, vt8, sq, sk, sv)``: q8 / k8 ``torch.float8_e4m3fn`` [B*S][C] with
+    sq / sk fp32 [B*S][H] (one scale per token and head), vt8 e4m3 [C][B*S8] with sv fp32 [B][C] (one scale per batch and channel),
+    S8 = S rounded up to a multiple of 128 and the bytes of keys [S, S8) zero.  ``scale = amax / 448`` (1 for a zero row), ``q =
+    e4m3(clamp(x * (1 / scale), +-448))``.  ``out``: the six tensors to write (contiguous), else they are allocated."""
+    _refuse_recording_fp8_attention("attention_fp8_prepare", "da_attention_fp8_prepare")
+    _req(qk, "qk"), _req(vt, "vt")
+    ld, vt_ld = _rows2d(qk, "qk"), _rows2d(vt, "vt")
+    if qk.shape[1] != 2 * H * 128:
+        raise ValueError(f"attention_fp8_prepare: head size {qk.shape[1] / (2 * H):g} (qk is {tuple(qk.shape)} for {H} heads): only D = 128 "
+                         "is implemented")
+    C_ = H * 128
+    if qk.shape[0] != B * S or tuple(vt.shape) != (C_, B * S):
+        raise ValueError(f"attention_fp8_prepare: qk must be [{B * S}][{2 * C_}] and vt [{C_}][{B * S}], got {tuple(qk.shape)} and "
+                         f"{tuple(vt.shape)}")
+    if ld % 8 or qk.data_ptr() % 16:
+        raise ValueError(f"attention_fp8_prepare: qk needs a row stride that is a multiple of 8 elements and a 16-byte aligned base (16-byte "
+                         f"loads), got row stride {ld} and address % 16 = {qk.data_ptr() % 16}")
+    S8 = (S + 127) // 128 * 128
+    f8, f32, dev = torch.float8_e4m3fn, torch.float32, qk.device
+    shapes = (((B * S, C_), f8), ((B * S, C_), f8), ((C_, B * S8), f8), ((B * S, H), f32), ((B * S, H), f32), ((B, C_), f32))
+    if out is None:
+        out = tuple(torch.empty(s, device=dev, dtype=d) for s, d in shapes)
+    for t, (s, d), name in zip(out, shapes, ("q8", "k8", "vt8", "sq", "sk", "sv")):
+        _req(t, name, d)
+        if tuple(t.shape) != s or not t.is_contiguous():
+            raise ValueError(f"attention_fp8_prepare: out {name} must be a contiguous {list(s)}, got {tuple(t.shape)} strides {t.stride()}")
+    q8, k8, vt8, sq, sk, sv = out
+    L.check(L.load().da_attention_fp8_prepare(qk.data_ptr(), ld, vt.data_ptr(), vt_ld, S, q8.data_ptr(), k8.data_ptr(), vt8.data_ptr(),
+                                              sq.data_ptr(), sk.data_ptr(), sv.data_ptr(), B, S, H, 128, _stream()),
+            "da_attention_fp8_prepare")
+    return q8, k8, vt8, sq, sk, sv
+
+
+def attention_fp8(q8: torch.Tensor, k8: torch.Tensor, vt8: torch.Tensor, sq: torch.Tensor, sk: torch.Tensor, sv: torch.Tensor, *, B: int,
+                  H: int, Sq: int, Skv: int, scale: float, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """da_attention_fp8 (csrc/attention_fp8.hip): unmasked flash attention for heads of 128 on the fp8 MFMA, from the operands
+    :func:`attention_fp8_prepare` writes.  ``q8`` [B*Sq][C] or [B][Sq][C] and ``k8`` [B*Skv][C] or [B][Skv][C] e4m3 (views with wider
+    strides are fine: 16-byte aligned rows), ``sq`` / ``sk`` fp32 of the same leading shape x [H], ``vt8`` e4m3 [C][B*S8] with
+    ``S8 >= Skv`` a multiple of 128, ``sv`` fp32 [B][C].  ``out`` bf16 [B*Sq][C] (or [B][Sq][C]); nothing outside it is written.
+    ``p = e4m3(exp2(x - rowmax + 8))``, the row sum taken from the rounded p, fp32 accumulation, one rounding to bf16."""
+    _refuse_recording_fp8_attention("attention_fp8", "da_attention_fp8")
+    f8, f32 = torch.float8_e4m3fn, torch.float32
+    _req(q8, "q8", f8), _req(k8, "k8", f8), _req(vt8, "vt8", f8), _req(sq, "sq", f32), _req(sk, "sk", f32), _req(sv, "sv", f32)
+    D = q8.shape[-1] // H if q8.shape[-1] % H == 0 else 0
+    if D != 128:
+        raise ValueError(f"attention_fp8: head size {q8.shape[-1] / H:g} (q8 is {tuple(q8.shape)} for {H} heads): only D = 128 is implemented")
+    C_ = H * 128
+    p = L.AttentionFp8Params()
+    p.q_row_stride, p.q_batch_stride = _batched_rows(q8, "q8", B, Sq, C_)
+    p.k_row_stride, p.k_batch_stride = _batched_rows(k8, "k8", B, Skv, C_)
+    for name, t, ld, bs in (("q8", q8, p.q_row_stride, p.q_batch_stride), ("k8", k8, p.k_row_stride, p.k_batch_stride)):
+        if ld % 16 or bs % 16 or t.data_ptr() % 16:
+            raise ValueError(f"attention_fp8: {name} needs row and batch strides that are multiples of 16 bytes and a 16-byte aligned base, "
+                             f"got {ld} / {bs} and address % 16 = {t.data_ptr() % 16}")
+    for name, t, S in (("sq", sq, Sq), ("sk", sk, Skv)):
+        ld, bs = _batched_rows(t, name, B, S, H)
+        if ld != H:
+            raise ValueError(f"attention_fp8: {name} rows must be contiguous [{H}], got a row stride of {ld}")
+        setattr(p, f"{name}_batch_stride", bs)
+    vt_ld = _rows2d(vt8, "vt8")
+    S8 = vt8.shape[1] // B
+    if vt8.shape[0] != C_ or vt8.shape[1] != B * S8 or S8 % 128 or S8 < Skv:
+        raise ValueError(f"attention_fp8: vt8 must be [{C_}][{B} * S8] with S8 >= {Skv} a multiple of 128, got {tuple(vt8.shape)}")
+    if vt_ld % 16 or vt8.data_ptr() % 16:
+        raise ValueError(f"attention_fp8: vt8 needs a row stride that is a multiple of 16 bytes and a 16-byte aligned base, got {vt_ld} and "
+                         f"address % 16 = {vt8.data_ptr() % 16}")
+    if tuple(sv.shape) != (B, C_) or not sv.is_contiguous():
+        raise ValueError(f"attention_fp8: sv must be a contiguous [{B}][{C_}], got {tuple(sv.shape)}")
+    if out is None:
+        out = torch.empty((B * Sq, C_), device=q8.device, dtype=bf16)
+    _req(out, "out")
+    p.o_row_stride, p.o_batch_stride = _batched_rows(out, "out", B, Sq, C_)
+    if p.o_row_stride % 4 or p.o_batch_stride % 4 or out.data_ptr() % 8:
+        raise ValueError(f"attention_fp8: out needs row and batch strides that are multiples of 4 elements and an 8-byte aligned base, got "
+                         f"{p.o_row_stride} / {p.o_batch_stride} and address % 8 = {out.data_ptr() % 8}")
+    p.q8, p.k8, p.vt8, p.sq, p.sk, p.sv, p.out = (t.data_ptr() for t in (q8, k8, vt8, sq, sk, sv, out))
+    p.B, p.H, p.Sq, p.Skv, p.S8, p.D = B, H, Sq, Skv, S8, 128
+    p.vt_ld, p.vt_batch_stride, p.scale = vt_ld, S8, float(scale)
+    L.check(L.load().da_attention_fp8(C.byref(p), _stream()), "da_attention_fp8")
+    return out
+
+
 def _lanczos(x: float) -> float:
     if not -3.0 <= x < 3.0:
         return 0.0

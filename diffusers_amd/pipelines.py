@@ -261,6 +261,13 @@ def _model_token(model):
     return (_weights_token(model),) + tuple(extra) if extra else _weights_token(model)
 
 
+def _refuse_plan_with_fp8_attention(model, use_graph) -> None:
+    if use_graph == "plan" and "fp8_attention" in model.graph_token():
+        raise NotImplementedError('use_graph="plan" with fp8 attention enabled: da_attention_fp8 / da_attention_fp8_prepare have no '
+                                  "launch-plan number; call with use_graph=True (captured HIP graph) or False, or "
+                                  "disable_fp8_attention() first")
+
+
 def _key_tail(scheduler, model, sample) -> tuple:
     """The part of every ``_make_graph_key`` that names the scheduler's and the model's side of a captured step: the addresses of
     the coefficient table and of the device step counter, the generation of the packed weights, the scheduler's further device
@@ -2167,10 +2174,19 @@ class FluxPipeline(_VaeTilingMixin, _StepCallbacks, _CapturedStepLoop, PipelineL
     def disable_fp8_linears(self):
         self.transformer.disable_fp8_linears()
 
+    def enable_fp8_attention(self):
+        """``FluxTransformer2DModel.enable_fp8_attention``: the joint attention of the step on the fp8 flash-attention kernel (opt-in,
+        heads of 128; the next call captures a new step; ``use_graph="plan"`` is refused while it is on)."""
+        self.transformer.enable_fp8_attention()
+
+    def disable_fp8_attention(self):
+        self.transformer.disable_fp8_attention()
+
     def _denoise(self, latents, step_args: tuple, num_steps: int, use_graph, begin: int = 0):
-        if use_graph == "plan" and self.transformer.graph_token():
+        if use_graph == "plan" and "fp8" in self.transformer.graph_token():
             raise NotImplementedError('use_graph="plan" with fp8 linears enabled: da_gemm_fp8 / da_quantize_rows_e4m3 have no launch-plan '
                                       "number; call with use_graph=True (captured HIP graph) or False, or disable_fp8_linears() first")
+        _refuse_plan_with_fp8_attention(self.transformer, use_graph)
         return super()._denoise(latents, step_args, num_steps, use_graph, begin=begin)
 
     def _graph_key_extra(self):
@@ -2520,6 +2536,18 @@ class WanPipeline(_VaeTilingMixin, _StepCallbacks, _CapturedStepLoop, PipelineLo
         else:
             sch.step_inplace(v, latents)
         return latents
+
+    def enable_fp8_attention(self):
+        """``WanTransformer3DModel.enable_fp8_attention``: every block's self-attention on the fp8 flash-attention kernel (opt-in,
+        heads of 128; the next call captures a new step; ``use_graph="plan"`` is refused while it is on)."""
+        self.transformer.enable_fp8_attention()
+
+    def disable_fp8_attention(self):
+        self.transformer.disable_fp8_attention()
+
+    def _denoise(self, latents, step_args: tuple, num_steps: int, use_graph, begin: int = 0):
+        _refuse_plan_with_fp8_attention(self.transformer, use_graph)
+        return super()._denoise(latents, step_args, num_steps, use_graph, begin=begin)
 
     def _make_graph_key(self, latents, cond, guidance_scale, do_cfg):
         """Everything a captured step depends on besides the contents of its static buffers: `_step` branches on the latents'

@@ -193,9 +193,28 @@ class FluxTransformer2DModel(PretrainedMixin):
         self._fp8 = False
         return self
 
+    # FP8 (e4m3) joint attention: opt-in, default off, independent of the fp8 linears (csrc/attention_fp8.hip)
+    _fp8_attention = False
+
+    def enable_fp8_attention(self):
+        """Run the joint attention of every double and single block on the fp8 flash-attention kernel: one
+        ``ops.attention_fp8_prepare`` launch quantises q, k (per token and head) and V^T (per batch and channel) to e4m3,
+        ``ops.attention_fp8`` does the rest.  Heads of 128 only.  Captured steps are re-captured (the flag is part of the graph key);
+        ``use_graph="plan"`` is refused while it is on."""
+        if self.config.attention_head_dim != 128:
+            raise ValueError(f"enable_fp8_attention: the fp8 attention kernel serves heads of 128, this model has attention_head_dim = "
+                             f"{self.config.attention_head_dim}")
+        self._fp8_attention = True
+        return self
+
+    def disable_fp8_attention(self):
+        """Back to the bf16 attention kernel (bit-identical to a model that never enabled it)."""
+        self._fp8_attention = False
+        return self
+
     def graph_token(self) -> tuple:
         """What ``forward`` bakes into a captured step by value, besides the weights."""
-        return ("fp8",) if self._fp8 else ()
+        return (("fp8",) if self._fp8 else ()) + (("fp8_attention",) if self._fp8_attention else ())
 
     def eval(self):
         return self
@@ -309,6 +328,9 @@ class FluxTransformer2DModel(PretrainedMixin):
             return ops.linear_fp8(*holder._fp8_w[attr], *xq, bias_rows=bias_rows, out=out)
 
         def attention(qk, vt, out=None):
+            if self._fp8_attention:
+                return ops.attention_fp8(*ops.attention_fp8_prepare(qk, vt, B=B, S=S, H=Hh), B=B, H=Hh, Sq=S, Skv=S, scale=D ** -0.5,
+                                         out=out)
             return ops.attention(qk, qk[:, C:], vt, B=B, H=Hh, D=D, Sq=S, Skv=S, Skv_alloc=S, q_row_stride=2 * C,
                                  k_row_stride=2 * C, q_batch_stride=S * 2 * C, k_batch_stride=S * 2 * C, vt_ld=B * S,
                                  vt_batch_stride=S, scale=D ** -0.5, out=out)

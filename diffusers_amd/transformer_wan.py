@@ -130,6 +130,31 @@ class WanTransformer3DModel(PretrainedMixin):
         return contextlib.nullcontext()
 
     # ------------------------------------------------------------------------------------------------------------
+    # FP8 (e4m3) self-attention: opt-in, default off (csrc/attention_fp8.hip)
+    # ------------------------------------------------------------------------------------------------------------
+    _fp8_attention = False
+
+    def enable_fp8_attention(self):
+        """Run every block's self-attention on the fp8 flash-attention kernel: one ``ops.attention_fp8_prepare`` launch quantises q, k
+        (per token and head) and V^T (per batch and channel) to e4m3, ``ops.attention_fp8`` does the rest.  Heads of 128 only.  The
+        cross-attention (512 text keys) and everything else stay bf16.  Captured steps are re-captured (the flag is part of the
+        graph key); ``use_graph="plan"`` is refused while it is on."""
+        if self.config.attention_head_dim != 128:
+            raise ValueError(f"enable_fp8_attention: the fp8 attention kernel serves heads of 128, this model has attention_head_dim = "
+                             f"{self.config.attention_head_dim}")
+        self._fp8_attention = True
+        return self
+
+    def disable_fp8_attention(self):
+        """Back to the bf16 attention kernel (bit-identical to a model that never enabled it)."""
+        self._fp8_attention = False
+        return self
+
+    def graph_token(self) -> tuple:
+        """What ``forward`` bakes into a captured step by value, besides the weights."""
+        return ("fp8_attention",) if self._fp8_attention else ()
+
+    # ------------------------------------------------------------------------------------------------------------
     def precompute_conditioning(self, encoder_hidden_states: torch.Tensor) -> Dict[str, Any]:
         """Step-invariant work: the text embedder MLP and every block's cross-attention K (RMS-normed) / V^T."""
         ops.require_hip(encoder_hidden_states, "encoder_hidden_states")
@@ -220,9 +245,12 @@ class WanTransformer3DModel(PretrainedMixin):
             vt = ops.linear(blk.wv, n, bias_rows=blk.bv)
             ops.rmsnorm_rope_(qk, heads=Hh, head_dim=D, col_offsets=(0, C), weights=(blk.norm_q, blk.norm_k), eps=eps,
                               cos=cos, sin=sin, rope_row0=0, rows_per_batch=S, norm="across_heads")
-            o = ops.attention(qk, qk[:, C:], vt, B=B, H=Hh, D=D, Sq=S, Skv=S, Skv_alloc=S, q_row_stride=2 * C,
-                              k_row_stride=2 * C, q_batch_stride=S * 2 * C, k_batch_stride=S * 2 * C, vt_ld=B * S,
-                              vt_batch_stride=S, scale=D ** -0.5)
+            if self._fp8_attention:
+                o = ops.attention_fp8(*ops.attention_fp8_prepare(qk, vt, B=B, S=S, H=Hh), B=B, H=Hh, Sq=S, Skv=S, scale=D ** -0.5)
+            else:
+                o = ops.attention(qk, qk[:, C:], vt, B=B, H=Hh, D=D, Sq=S, Skv=S, Skv_alloc=S, q_row_stride=2 * C,
+                                  k_row_stride=2 * C, q_batch_stride=S * 2 * C, k_batch_stride=S * 2 * C, vt_ld=B * S,
+                                  vt_batch_stride=S, scale=D ** -0.5)
             x = ops.linear(o, blk.to_out.weight, blk.to_out.bias, gate=chunk(mod, 2), rows_per_batch=S, residual=x)
             n2 = blk.norm2(x) if blk.norm2 is not None else x
             q = ops.linear(n2, blk.c_q.weight, blk.c_q.bias)

@@ -489,6 +489,40 @@ int da_quantize_rows_e4m3(const void* x, long long ldx, void* q, long long ldq, 
 int da_gemm_fp8(const da_gemm_fp8_params* p, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------------
+ * FP8 flash attention, D = 128 (attention_fp8.hip): unmasked, no bias; the numeric contract is in that file's header.
+ *   da_attention_fp8_prepare  qk bf16 [B*S][qk_ld] (q in columns 0 .. C, k in C .. 2C, C = 128 H) and vt bf16 [C][vt_ld] (batch b at
+ *                             column b * vt_batch_stride, S keys contiguous) -> q8, k8 e4m3 [B*S][C] with sq, sk fp32 [B*S][H] (one
+ *                             scale per token and head, the arithmetic of da_quantize_rows_e4m3 on rows of 128) and vt8 e4m3
+ *                             [C][B*S8] with sv fp32 [B][C] (amax over the S keys of the batch), S8 = S rounded up to a multiple of
+ *                             128, bytes [S, S8) of every batch segment zero.  All six outputs contiguous.  qk_ld % 8 == 0, qk 16-byte
+ *                             aligned; vt needs no alignment beyond bf16's; q8 / k8 / vt8 8-byte aligned.
+ *   da_attention_fp8          out[b][i][h*128 + d] = bf16(sv_d * sum_j p8_ij v8_jd / sum_j p8_ij), p8_ij = e4m3(exp2(x_ij - m_i + 8)),
+ *                             x_ij = log2(e) * scale * sq_i * sk_j * sum_d q8_id k8_jd.  Row / batch strides of q8, k8, vt8 in bytes,
+ *                             of out in bf16 elements, of sq / sk in floats (their rows are [H] contiguous); sv is [B][C] contiguous.
+ *                             Row and batch strides of q8 / k8 / vt8 multiples of 16 bytes and the bases 16-byte aligned; out strides
+ *                             multiples of 4 elements and its base 8-byte aligned; vt8 rows hold 128 * ceil(Skv / 128) <= S8 bytes per
+ *                             batch.  D != 128 or anything else outside this: DA_ERR_UNSUPPORTED and no launch.
+ *   Neither entry has a DA_FN_* plan number (DA_ABI_VERSION stays 9): they run eagerly or inside a captured HIP graph.
+ * ------------------------------------------------------------------------------------------------------------------ */
+typedef struct da_attention_fp8_params {
+  const void* q8;  /* e4m3 [B][Sq][q_row_stride] */
+  const void* k8;  /* e4m3 [B][Skv][k_row_stride] */
+  const void* vt8; /* e4m3 [H*128][vt_ld], batch b at byte b * vt_batch_stride of a row */
+  const void* sq;  /* fp32 [B][Sq][H] */
+  const void* sk;  /* fp32 [B][Skv][H] */
+  const void* sv;  /* fp32 [B][H*128] */
+  void* out;       /* bf16 [B][Sq][o_row_stride] */
+  int B, H, Sq, Skv, S8, D;
+  long long q_batch_stride, k_batch_stride, vt_batch_stride, o_batch_stride, sq_batch_stride, sk_batch_stride;
+  long long vt_ld;
+  int q_row_stride, k_row_stride, o_row_stride;
+  float scale;
+} da_attention_fp8_params;
+int da_attention_fp8_prepare(const void* qk, long long qk_ld, const void* vt, long long vt_ld, long long vt_batch_stride, void* q8, void* k8,
+                             void* vt8, void* sq, void* sk, void* sv, int B, int S, int H, int D, void* stream);
+int da_attention_fp8(const da_attention_fp8_params* p, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------------
  * Normalisation (norm.hip)
  *   da_groupnorm_nhwc_bf16   nn.GroupNorm(G, C, eps) [+ SiLU when act == DA_ACT_SILU] on channels-last [B][HW][C].
  *                            Replaces resnet.py:326-327,:350,:362, transformer_2d.py:466, unet_2d_condition.py:1228-1229,
